@@ -9,7 +9,11 @@ state written to HBM), bracketed by barrier + synchronize on both sides; `value`
 region.  `roofline.achieved` = SURVEY 8(d)'s algorithmic bytes 16(N+1)nx per lane-timestep x the lane-timesteps of one
 launch / that launch's duration by HIP events on the library's own stream.
 
-What the line says about itself:
+A plain run does only what that headline needs: set-up, the settling and warm-up steps, the K timed steps, the outputs of the last
+timed step when --dump-outputs DIR is given, the line.  Everything else below runs with --full only (the sub-options --no-extras,
+--no-pmc, --no-cpu-baseline, --shares-only, --large-batch and --physical-steps trim a --full run).
+
+What a --full line says about itself:
   * `roofline.traffic` is MEASURED IN THIS RUN: before the GPU is touched, rank 0 runs this same script as a child under
     `rocprofv3 --pmc` (separate passes for FETCH_SIZE, WRITE_SIZE and an SQ group, as MI355X_MICROARCH.md prescribes; FETCH_SIZE
     doubled on gfx950) over the same launch shapes, and reads the per-dispatch counters of the timed kernels.  null (with a
@@ -23,7 +27,9 @@ What the line says about itself:
 Multi-GPU: the batch shards embarrassingly (weak scaling: every rank owns `--batch` lanes), no collective in the timed region; one
 RCCL all_gather of the polarization observables afterwards.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  With --dump-outputs DIR, rank 0 also writes what a caller of the timed path receives after its last
+timed step (pnp_get_state, pnp_get_surface, pnp_get_status of its lanes) as DIR/<name>.npy in float64; the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 """
 import argparse
 import csv
@@ -67,6 +73,10 @@ def parse():
     ap.add_argument('--no-pmc', action='store_true', help='skip the rocprofv3 counter passes (roofline.traffic = null)')
     ap.add_argument('--large-batch', type=int, default=8192, help='extra timed run at this batch size; 0 = skip')
     ap.add_argument('--physical-steps', type=int, default=20, help='implicit physical mode on the headline shape; 0 = skip')
+    ap.add_argument('--full', action='store_true',
+                    help='also the records beside the headline: rocprofv3 counters, first launch after upload, per-step launch, large '
+                         'batch, beyond-cache, physical mode, per-rank shares, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy')
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)   # this process is the profiled child
     return ap.parse_args()
 
@@ -294,6 +304,28 @@ def timed_steps(s, nsteps, spl, reps=1):
         s.step(nsteps, spl)
         ms.append(s.timer_stop())
     return float(np.median(ms))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(s, out_dir):
+    """What a caller of the timed path receives after its last step, as out_dir/<name>.npy (float64).  Beyond 64 MB in all, the same
+    fixed, seeded sample of lanes is taken from every array (and its lane indices are written as `lanes`)."""
+    c, v, gv, lv = s.get_state()
+    cs, vs, es = s.get_surface()
+    arrays = {'concentrations': c, 'potential': v, 'potential_gradient': gv, 'potential_laplacian': lv,
+              'surface_concentrations': cs, 'surface_potential': vs, 'surface_field': es, 'status': s.get_status().astype(np.float64)}
+    B = c.shape[0]
+    per_lane = sum(a.nbytes for a in arrays.values()) // B
+    if per_lane * B > DUMP_BUDGET_BYTES:
+        keep = (DUMP_BUDGET_BYTES - 4096) // (per_lane + 8)          # (+8: the lane index; 4096: the .npy headers)
+        lanes = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        arrays = {k: a[lanes] for k, a in arrays.items()}
+        arrays['lanes'] = lanes.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def hbm_record(B, N, nx, steps, launches, ev_ms, pmc):
@@ -636,7 +668,7 @@ def main():
     os.dup2(2, 1)
     # the cpu_baseline leg's checker library: loaded (and, if stale, rebuilt by `make`) BEFORE this process initialises the GPU --
     # no child process may be started afterwards on the GPU box
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import c_oracle as _co
         _co.load()
     # counters first: the child processes must be started before this process initialises the GPU
@@ -646,7 +678,7 @@ def main():
     profiled = any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ) or 'rocprof' in os.environ.get('LD_PRELOAD', '')
     if profiled:
         pmc = {'error': 'this process runs under rocprofv3: no nested counter collection'}
-    elif rank == 0 and world == 1 and not args.no_pmc:
+    elif args.full and rank == 0 and world == 1 and not args.no_pmc:
         pmc = collect_pmc(args)
     import torch
     dist = None
@@ -714,8 +746,9 @@ def main():
     # rate (round 1: 1.45 x slower; its cause -- the dispatch preceding a launch that only just fits -- is removed inside
     # pnp_set_batch since round 2).  The reference's lagged-potential integrator does not survive long runs on
     # this workload (lanes turn NaN after ~3000 steps, in the oracle too), hence the fresh upload before the timed region as well.
-    solver.set_batch(c0, pb, vz, fl)
-    cold_wall, cold_ev = timed(args.steps, args.steps_per_launch)
+    if args.full:
+        solver.set_batch(c0, pb, vz, fl)
+        cold_wall, cold_ev = timed(args.steps, args.steps_per_launch)
     # ---- the timed region of the contract: upload, the W warm-up steps, then exactly K timed steps -----------------------------------
     solver.set_batch(c0, pb, vz, fl)
     solver.step(args.warmup, args.steps_per_launch)
@@ -724,8 +757,10 @@ def main():
     n_launch = (args.steps + args.steps_per_launch - 1) // args.steps_per_launch
     steps_total = world * B * args.steps
     value = steps_total / wall
+    if args.dump_outputs and rank == 0:          # (before the records below step this solver further)
+        dump_outputs(solver, args.dump_outputs)
 
-    extras = rank == 0 and world == 1 and not args.no_extras and not args.shares_only
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and not args.shares_only
     per_step = None
     if extras and args.steps_per_launch != 1:
         solver.step(64, 1)
@@ -761,7 +796,7 @@ def main():
     # compat step per launch and coupled-Newton lane kernels, each with the contract's timed region (common start, MAX over ranks) --
     # the scaling curve on those shapes; at N = 1 the same shapes are the `beyond_cache` / `physical_mode` records below
     shares = None
-    if dist is not None and not args.no_extras:          # (world > 1, or CATINT_FORCE_DIST: the RCCL rehearsal of one rank)
+    if args.full and dist is not None and not args.no_extras:    # (world > 1, or CATINT_FORCE_DIST: the RCCL rehearsal of one rank)
         shares = {}
 
         def lane_bytes_(N_, nx_, fused):      # (as lane_bytes of physical_mode: the lane kernel fuses the update into the back-substitution)
@@ -921,11 +956,12 @@ def main():
             'roofline': roof,
             'timed_region': {'wall_us': wall * 1e6, 'event_us': ev_ms * 1e3, 'host_launch_and_sync_us': wall * 1e6 - ev_ms * 1e3,
                              'event_timesteps_per_s': B * args.steps / (ev_ms * 1e-3), 'wall_over_event': wall / (ev_ms * 1e-3)},
-            'first_launch_after_upload': {'timesteps_per_s_wall': world * B * args.steps / cold_wall,
-                                          'timesteps_per_s_event': B * args.steps / (cold_ev * 1e-3), 'event_us': cold_ev * 1e3,
-                                          'sustained_over_cold': (cold_ev / ev_ms) if ev_ms > 0 else None},
             'lanes_ok': int((status == 0).sum()), 'lanes_total': int(B),
         }
+        if args.full:
+            out['first_launch_after_upload'] = {'timesteps_per_s_wall': world * B * args.steps / cold_wall,
+                                                'timesteps_per_s_event': B * args.steps / (cold_ev * 1e-3), 'event_us': cold_ev * 1e3,
+                                                'sustained_over_cold': (cold_ev / ev_ms) if ev_ms > 0 else None}
         if per_step:
             out['per_step_launch'] = per_step
         if large:
@@ -945,7 +981,7 @@ def main():
             out['start_skew_us'] = start_skew[0] if start_skew else None
         if shares:
             out.update(shares)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(prob, c0, pb, vz, fl, args.method, args.cpu_seconds)
             if args.method == 'Crank-Nicolson':
                 cb['reference_faithful_dense_1core'] = cpu_reference_faithful(prob, c0, pb, vz, fl, args.method)

@@ -1,10 +1,12 @@
 """The one JSON line of bench.py (the driver's contract): keys, types and internal consistency -- on the committed line of the driver's
 command (profiles/, CPU) and on a fresh short run (GPU)."""
+import importlib.util
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -81,3 +83,76 @@ def test_fresh_short_run_prints_one_line_that_keeps_the_contract():
     d = json.loads(lines[0])
     check_line(d, with_cpu=False)
     assert d['steps'] == 4 and d['warmup'] == 1 and d['n_gpus'] == 1
+
+
+def load_bench():
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+class FakeSolver:
+    """The read-back of PnpSolver (get_state / get_surface / get_status) on seeded host arrays."""
+    def __init__(self, B, N, nx):
+        rng = np.random.default_rng(5)
+        self.c, self.v, self.g, self.l = rng.random((B, N, nx)), rng.random((B, nx)), rng.random((B, nx)), rng.random((B, nx))
+        self.cs, self.vs, self.es = self.c[:, :, 0].copy(), self.v[:, 0].copy(), rng.random(B)
+        self.st = (np.arange(B) % 3 == 0).astype(np.int32)
+
+    def get_state(self):
+        return self.c, self.v, self.g, self.l
+
+    def get_surface(self):
+        return self.cs, self.vs, self.es
+
+    def get_status(self):
+        return self.st
+
+
+DUMP_NAMES = ('concentrations', 'potential', 'potential_gradient', 'potential_laplacian', 'surface_concentrations', 'surface_potential',
+              'surface_field', 'status')
+
+
+def test_dump_outputs_writes_every_array_whole_within_the_budget(tmp_path):
+    bench = load_bench()
+    s = FakeSolver(6, 3, 40)
+    bench.dump_outputs(s, str(tmp_path))
+    assert sorted(os.listdir(tmp_path)) == sorted(n + '.npy' for n in DUMP_NAMES)
+    for name, ref in zip(DUMP_NAMES, (s.c, s.v, s.g, s.l, s.cs, s.vs, s.es, s.st)):
+        a = np.load(tmp_path / (name + '.npy'))
+        assert a.dtype == np.float64 and np.array_equal(a, ref), name
+
+
+def test_dump_outputs_beyond_the_budget_keeps_the_same_seeded_lanes_of_every_array(tmp_path, monkeypatch):
+    bench = load_bench()
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 1 << 20)
+    s = FakeSolver(400, 3, 200)                  # 400 lanes x 5.6 KB: twice the budget
+    for d in ('a', 'b'):
+        bench.dump_outputs(s, str(tmp_path / d))
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in os.listdir(tmp_path / 'a')) <= 1 << 20
+    lanes = np.load(tmp_path / 'a' / 'lanes.npy')
+    assert 100 < len(lanes) < 400 and np.all(np.diff(lanes) > 0) and np.array_equal(lanes, np.load(tmp_path / 'b' / 'lanes.npy'))
+    idx = lanes.astype(np.int64)
+    for name, ref in zip(DUMP_NAMES, (s.c, s.v, s.g, s.l, s.cs, s.vs, s.es, s.st)):
+        a = np.load(tmp_path / 'a' / (name + '.npy'))
+        assert a.dtype == np.float64 and np.array_equal(a, ref[idx]), name
+
+
+@pytest.mark.gpu
+def test_fresh_short_run_dumps_the_state_after_its_last_timed_step(tmp_path):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout)
+    check_line(d, with_cpu=False)
+    assert 'cpu_baseline' not in d and 'physical_mode' not in d          # a plain run: the headline only
+    B, N, nx = d['config']['batch_per_gpu'], d['config']['nspecies'], d['config']['nx']
+    shapes = {'concentrations': (B, N, nx), 'potential': (B, nx), 'potential_gradient': (B, nx), 'potential_laplacian': (B, nx),
+              'surface_concentrations': (B, N), 'surface_potential': (B,), 'surface_field': (B,), 'status': (B,)}
+    assert sorted(os.listdir(tmp_path)) == sorted(n + '.npy' for n in shapes)
+    a = {n: np.load(tmp_path / (n + '.npy')) for n in shapes}
+    for n, shape in shapes.items():
+        assert a[n].dtype == np.float64 and a[n].shape == shape and np.isfinite(a[n]).all(), n
+    assert (a['status'] == 0).all() and d['lanes_ok'] == B
+    np.testing.assert_allclose(a['surface_concentrations'], a['concentrations'][:, :, 0], rtol=1e-12)

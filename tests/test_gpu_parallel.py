@@ -78,8 +78,8 @@ def test_bench_under_rccl_with_one_rank_walks_every_collective_of_the_multi_gpu_
     env = dict(os.environ, CATINT_FORCE_DIST='1', CATINT_BENCH_SHARE_DIV='16', RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1',
                MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('CATINT_DIST_BACKEND', None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '1', '--no-pmc', '--no-cpu-baseline',
-                          '--shares-only'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '4', '--warmup', '1', '--no-pmc',
+                          '--no-cpu-baseline', '--shares-only'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout)
     assert d['n_gpus'] == 1 and d['gather']['backend'] == 'nccl' and d['start_skew_us'] == 0.0
@@ -94,8 +94,8 @@ def test_bench_two_ranks_print_one_json_line_with_the_8_gpu_shares():
     per rank (here on 1/16 of the batch)."""
     import json
     env = dict(os.environ, CATINT_DIST_BACKEND='gloo', CATINT_BENCH_SHARE_DIV='16', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--no-pmc',
-                          '--no-cpu-baseline'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--full', '--steps', '4', '--warmup', '1',
+                          '--no-pmc', '--no-cpu-baseline'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout)                       # the WHOLE of stdout is one JSON document
     assert d['n_gpus'] == 2 and len(d['per_rank_timesteps_per_s']) == 2 and d['start_skew_us'] >= 0.0
