@@ -17,6 +17,24 @@
 
 using namespace pnp;
 
+// kernel families of the physical mode, as newton_family picks them: the three lane kernels, then the workgroup-per-point kernels
+// (pnp_newton.hip: pair / team / sweep / row-per-thread, chosen by launch_newton)
+enum NewtonFamily { NF_LANE4 = 0, NF_LANE2, NF_LANE, NF_WORKGROUP };
+constexpr int NUM_LANE_FAMILIES = NF_WORKGROUP;
+
+// per lane family: operating points per group, the kernel choice that forces it, and its supported / sizing / launch functions
+static const struct LaneFamily {
+  int points;
+  int kernel;
+  bool (*supported)(int nb, int nx, int mode);
+  size_t (*rec_doubles)(int nb, int nx);
+  size_t (*state_doubles)(int nb, int nx);
+  hipError_t (*launch)(const NewtonArgs& a, hipStream_t stream);
+} kLaneFamilies[NUM_LANE_FAMILIES] = {
+    {8, NK_LANE4, newton_lane4_supported, newton_lane4_rec_doubles, newton_lane4_state_doubles, launch_newton_lane4},
+    {16, NK_LANE2, newton_lane2_supported, newton_lane2_rec_doubles, newton_lane2_state_doubles, launch_newton_lane2},
+    {32, NK_LANE, newton_lane_supported, newton_lane_rec_doubles, newton_lane_state_doubles, launch_newton_lane}};
+
 struct pnp_handle {
   pnp_config cfg;
   DevArgs a;
@@ -77,12 +95,10 @@ struct pnp_handle {
   // its transport solves
   double* sweep = nullptr;               // sweep kernel: records of the resident teams (allocated on first use)
   int sweep_blocks = 0;
-  double* lane_buf = nullptr;            // lane kernel: batch-innermost state copies + records of lane_groups groups of 32 operating points
-  int64_t lane_groups = 0;
-  double* lane2_buf = nullptr;           // lane-pair kernel: the same for groups of 16
-  int64_t lane2_groups = 0;
-  double* lane4_buf = nullptr;           // lane-quad kernel: the same for groups of 8
-  int64_t lane4_groups = 0;
+  struct LaneWorkspace {                 // lane kernels, one per family (lane_workspace): batch-innermost state copies + records of
+    double* buf = nullptr;               // `groups` groups of the family's operating points per group (allocated on first use)
+    int64_t groups = 0;
+  } lane_ws[NUM_LANE_FAMILIES];
   // lane kernels: which operating point a slot (group, lane) holds -- points ordered by expected Newton iterations, see lane_order
   int32_t* lane_perm = nullptr;          // device [capacity]
   std::vector<float> lane_key;           // |phiM - phi_bulk| per operating point (pnp_set_batch / pnp_set_pb): the order of a first call
@@ -200,8 +216,10 @@ void pnp_destroy(pnp_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->c, (void*)h->lapl[0], (void*)h->lapl[1], (void*)h->v, (void*)h->gradv, (void*)h->rates,
                   (void*)h->pb, (void*)h->vzeta, (void*)h->flux, (void*)h->cbulk, (void*)h->csurf, (void*)h->status,
-                  (void*)h->spec, (void*)h->ytmp, (void*)h->ftmp, (void*)h->c_old, (void*)h->work, (void*)h->iters, (void*)h->stash, (void*)h->rt_dev, (void*)h->rs_dev, (void*)h->c_old2, (void*)h->phi_old2, (void*)h->vol_dev, (void*)h->bdf_acc, (void*)h->wk_k, (void*)h->gw, (void*)h->gv, (void*)h->mol_lapl, (void*)h->scf_d, (void*)h->scf_i, (void*)h->scf_snap, (void*)h->stage, (void*)h->sweep, (void*)h->lane_buf, (void*)h->lane2_buf, (void*)h->lane4_buf, (void*)h->lane_perm, (void*)h->user_mask, (void*)h->ode_buf, (void*)h->ode_int, (void*)h->rkc_d, (void*)h->rkc_i})
+                  (void*)h->spec, (void*)h->ytmp, (void*)h->ftmp, (void*)h->c_old, (void*)h->work, (void*)h->iters, (void*)h->stash, (void*)h->rt_dev, (void*)h->rs_dev, (void*)h->c_old2, (void*)h->phi_old2, (void*)h->vol_dev, (void*)h->bdf_acc, (void*)h->wk_k, (void*)h->gw, (void*)h->gv, (void*)h->mol_lapl, (void*)h->scf_d, (void*)h->scf_i, (void*)h->scf_snap, (void*)h->stage, (void*)h->sweep, (void*)h->lane_perm, (void*)h->user_mask, (void*)h->ode_buf, (void*)h->ode_int, (void*)h->rkc_d, (void*)h->rkc_i})
     if (p) (void)hipFree(p);
+  for (const auto& ws : h->lane_ws)
+    if (ws.buf) (void)hipFree(ws.buf);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -365,7 +383,8 @@ int pnp_set_option(pnp_handle* h, const char* key, const char* value) {
   if (o.newton_exchange_global != h->opt.newton_exchange_global)
     return fail(h, PNP_ESTATE, "pnp_set_option: NEWTON_EXCHANGE sizes the buffers of pnp_create; set CATINT_NEWTON_EXCHANGE before creating the handle");
   // workspaces sized by an option are allocated on first use: an option set afterwards must not outgrow them
-  if ((h->lane_buf || h->lane2_buf || h->lane4_buf) && o.newton_lane_groups != h->opt.newton_lane_groups)
+  const bool lane_ws = std::any_of(std::begin(h->lane_ws), std::end(h->lane_ws), [](const pnp_handle::LaneWorkspace& ws) { return ws.buf != nullptr; });
+  if (lane_ws && o.newton_lane_groups != h->opt.newton_lane_groups)
     return fail(h, PNP_ESTATE, "pnp_set_option: NEWTON_LANE_GROUPS after the lane workspace was allocated");
   if (h->sweep && o.newton_sweep_blocks != h->opt.newton_sweep_blocks)
     return fail(h, PNP_ESTATE, "pnp_set_option: NEWTON_SWEEP_BLOCKS after the sweep workspace was allocated");
@@ -838,12 +857,47 @@ static int64_t newton_effective_batch(const pnp_handle* h) {
   return host_mask ? (h->user_mask_count > 0 ? h->user_mask_count : 1) : h->B;
 }
 
-// will run_newton hand this batch to one of the lane kernels (which take BDF2 steps inside one launch)?
-static bool newton_lane_family(const pnp_handle* h) {
+// the kernel family that runs this handle's batch under options o (the one place the choice is made: run_newton, newton_timesteps,
+// pnp_autotune_default, pnp_tune_placement).  The order matters: newton_lane2_preferred leaves the lane-quad window to
+// newton_lane4_preferred, and newton_lane_preferred the windows of both to them.
+static NewtonFamily newton_family(const pnp_handle* h, const Options& o) {
   const int nb = h->a.N + 1, nx = h->a.nx, variant = newton_variant(h);
   const int64_t n_eff = newton_effective_batch(h);
-  return newton_lane4_preferred(nb, nx, n_eff, variant, h->opt) || newton_lane2_preferred(nb, nx, n_eff, variant, h->opt) ||
-         newton_lane_preferred(nb, nx, n_eff, variant, h->opt);
+  if (newton_lane4_preferred(nb, nx, n_eff, variant, o)) return NF_LANE4;
+  if (newton_lane2_preferred(nb, nx, n_eff, variant, o)) return NF_LANE2;
+  if (newton_lane_preferred(nb, nx, n_eff, variant, o)) return NF_LANE;
+  return NF_WORKGROUP;
+}
+
+static size_t lane_group_doubles(const pnp_handle* h, NewtonFamily f) {
+  const LaneFamily& F = kLaneFamilies[f];
+  return F.rec_doubles(h->a.N + 1, h->a.nx) + F.state_doubles(h->a.N + 1, h->a.nx);
+}
+
+// the workspace of lane family f for a launch: transposed state + records of as many groups as the batch capacity has, capped at
+// 48 GiB (the launcher walks a larger batch in chunks), allocated on first use; cut into the arrays of NewtonArgs
+static int lane_workspace(pnp_handle* h, NewtonFamily f, NewtonArgs& a) {
+  const LaneFamily& F = kLaneFamilies[f];
+  pnp_handle::LaneWorkspace& ws = h->lane_ws[f];
+  const int N = h->a.N, nx = h->a.nx, P = F.points;
+  const size_t per_group = lane_group_doubles(h, f) * sizeof(double);
+  if (!ws.buf) {
+    int64_t groups = (h->cfg.batch_capacity + P - 1) / P;
+    const int64_t fit = (int64_t)(((size_t)48 << 30) / per_group);
+    if (groups > fit) groups = fit;
+    if (h->opt.newton_lane_groups >= 1 && h->opt.newton_lane_groups < groups) groups = h->opt.newton_lane_groups;      // tests: several chunks
+    if (groups < 1) groups = 1;
+    HIP_TRY(h, dev_alloc(h, &ws.buf, (size_t)groups * per_group / sizeof(double)));
+    ws.groups = groups;
+  }
+  const size_t G = (size_t)ws.groups, vp2 = (size_t)((N + 2) / 2 * 2), cp2 = (size_t)((N + 1) / 2 * 2);
+  a.lane_groups = ws.groups;
+  a.lane_ts = ws.buf;
+  a.lane_xs = a.lane_ts + G * vp2 * nx * P;
+  a.lane_tco = a.lane_xs + G * vp2 * nx * P;
+  a.lane_rec = a.lane_tco + G * cp2 * nx * P;
+  a.lane_tcn = a.lane_rec + G * F.rec_doubles(N + 1, nx);
+  return PNP_OK;
 }
 
 // nsteps timesteps of the physical mode: one launch (backward Euler), or one launch per step (BDF2 and / or the predictor)
@@ -855,7 +909,7 @@ static int newton_timesteps(pnp_handle* h, int nsteps) {
   const int64_t B = h->B;
   const size_t cap = (size_t)h->cfg.batch_capacity;
   if (!h->c_old2) HIP_TRY(h, dev_alloc(h, &h->c_old2, cap * N * ldx));
-  if (bdf2 && !pred && newton_lane_family(h)) {
+  if (bdf2 && !pred && newton_family(h, h->opt) != NF_WORKGROUP) {
     // the lane kernels keep the history themselves: ONE launch for all nsteps (the first step of a trajectory is backward Euler
     // from u_0, which becomes the history -- as below), c_old2 is the history's home between launches
     h->nw_bdf2_inline = 1;
@@ -945,75 +999,18 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   a.sides = a.rt ? h->rs_dev : nullptr;
   a.n_wk = h->newton_explicit_kinetics ? 0 : h->n_wk;
   a.lane_mask = h->newton_mask;
-  const int variant = newton_variant(h);
   a.ext_old = (h->nw_ext_old && !stationary) ? 1 : 0;
   a.bdf2 = (h->nw_bdf2_inline && !stationary) ? 1 : 0;
   a.bdf_hist0 = a.bdf2 ? h->nw_bdf_hist0 : 0;
   a.c_old2 = a.bdf2 ? h->c_old2 : nullptr;
   a.opt = &h->opt;
-  const int64_t n_eff = newton_effective_batch(h);
-  const bool use_lane4 = newton_lane4_preferred(N + 1, nx, n_eff, variant, h->opt);
-  const bool use_lane2 = !use_lane4 && newton_lane2_preferred(N + 1, nx, n_eff, variant, h->opt);
-  const bool use_lane = !use_lane4 && !use_lane2 && newton_lane_preferred(N + 1, nx, n_eff, variant, h->opt);
-  if (use_lane4) {
-    const size_t per_group = (newton_lane4_rec_doubles(N + 1, nx) + newton_lane4_state_doubles(N + 1, nx)) * sizeof(double);
-    if (!h->lane4_buf) {
-      int64_t groups = (h->cfg.batch_capacity + 7) / 8;
-      const int64_t fit = (int64_t)(((size_t)48 << 30) / per_group);
-      if (groups > fit) groups = fit;
-      if (h->opt.newton_lane_groups >= 1 && h->opt.newton_lane_groups < groups) groups = h->opt.newton_lane_groups;
-      if (groups < 1) groups = 1;
-      HIP_TRY(h, dev_alloc(h, &h->lane4_buf, (size_t)groups * per_group / sizeof(double)));
-      h->lane4_groups = groups;
-    }
-    const size_t vp2 = (size_t)((N + 2) / 2 * 2), cp2 = (size_t)((N + 1) / 2 * 2);
-    a.lane_groups = h->lane4_groups;
-    a.lane_ts = h->lane4_buf;
-    a.lane_xs = a.lane_ts + (size_t)h->lane4_groups * vp2 * nx * 8;
-    a.lane_tco = a.lane_xs + (size_t)h->lane4_groups * vp2 * nx * 8;
-    a.lane_rec = a.lane_tco + (size_t)h->lane4_groups * cp2 * nx * 8;
-    a.lane_tcn = a.lane_rec + (size_t)h->lane4_groups * newton_lane4_rec_doubles(N + 1, nx);
-  } else if (use_lane2) {
-    const size_t per_group = (newton_lane2_rec_doubles(N + 1, nx) + newton_lane2_state_doubles(N + 1, nx)) * sizeof(double);
-    if (!h->lane2_buf) {
-      int64_t groups = (h->cfg.batch_capacity + 15) / 16;
-      const int64_t fit = (int64_t)(((size_t)48 << 30) / per_group);
-      if (groups > fit) groups = fit;
-      if (h->opt.newton_lane_groups >= 1 && h->opt.newton_lane_groups < groups) groups = h->opt.newton_lane_groups;
-      if (groups < 1) groups = 1;
-      HIP_TRY(h, dev_alloc(h, &h->lane2_buf, (size_t)groups * per_group / sizeof(double)));
-      h->lane2_groups = groups;
-    }
-    const size_t vp2 = (size_t)((N + 2) / 2 * 2), cp2 = (size_t)((N + 1) / 2 * 2);
-    a.lane_groups = h->lane2_groups;
-    a.lane_ts = h->lane2_buf;
-    a.lane_xs = a.lane_ts + (size_t)h->lane2_groups * vp2 * nx * 16;
-    a.lane_tco = a.lane_xs + (size_t)h->lane2_groups * vp2 * nx * 16;
-    a.lane_rec = a.lane_tco + (size_t)h->lane2_groups * cp2 * nx * 16;
-    a.lane_tcn = a.lane_rec + (size_t)h->lane2_groups * newton_lane2_rec_doubles(N + 1, nx);
-  } else if (use_lane) {
-    // one operating point per lane: transposed state + records of as many groups of 32 operating points as the batch capacity has,
-    // capped at 48 GiB (the launcher walks a larger batch in chunks)
-    const size_t per_group = (newton_lane_rec_doubles(N + 1, nx) + newton_lane_state_doubles(N + 1, nx)) * sizeof(double);
-    if (!h->lane_buf) {
-      int64_t groups = (h->cfg.batch_capacity + 31) / 32;
-      const int64_t fit = (int64_t)(((size_t)48 << 30) / per_group);
-      if (groups > fit) groups = fit;
-      if (h->opt.newton_lane_groups >= 1 && h->opt.newton_lane_groups < groups) groups = h->opt.newton_lane_groups;      // tests: several chunks
-      if (groups < 1) groups = 1;
-      HIP_TRY(h, dev_alloc(h, &h->lane_buf, (size_t)groups * per_group / sizeof(double)));
-      h->lane_groups = groups;
-    }
-    a.lane_groups = h->lane_groups;
-    const size_t vp2 = (size_t)((N + 2) / 2 * 2), cp2 = (size_t)((N + 1) / 2 * 2);
-    a.lane_ts = h->lane_buf;
-    a.lane_xs = a.lane_ts + (size_t)h->lane_groups * vp2 * nx * 32;
-    a.lane_tco = a.lane_xs + (size_t)h->lane_groups * vp2 * nx * 32;
-    a.lane_rec = a.lane_tco + (size_t)h->lane_groups * cp2 * nx * 32;
-    a.lane_tcn = a.lane_rec + (size_t)h->lane_groups * newton_lane_rec_doubles(N + 1, nx);
+  const NewtonFamily family = newton_family(h, h->opt);
+  if (family != NF_WORKGROUP) {
+    const int rc = lane_workspace(h, family, a);
+    if (rc != PNP_OK) return rc;
   } else if (newton_sweep_preferred(N + 1, nx, h->B, a.rt ? 2 : (a.mpb ? 1 : 0), h->opt)) {
     // one team (N+1 lanes) per operating point, 64/(N+1) per wave; the workspace holds the records of the resident waves: at
-    // most four per SIMD, all of the batch capacity, and 32 GiB
+    // most four per SIMD, all of the batch capacity, and 32 GiB.  (a.sweep is the decision launch_newton follows: it is set here only.)
     const int64_t tpw = 64 / (N + 1);
     const size_t per_block = newton_sweep_doubles(N + 1, nx) * (size_t)tpw * sizeof(double);
     if (!h->sweep) {
@@ -1050,15 +1047,14 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   int blocks = h->nw_blocks;
   if (h->opt.newton_blocks >= 1 && h->opt.newton_blocks < blocks) blocks = h->opt.newton_blocks;      // tuning: size of the persistent grid
   if ((int64_t)blocks > h->B) blocks = (int)h->B;
-  if (use_lane4 || use_lane2 || use_lane) {
+  if (family != NF_WORKGROUP) {
     const int rc = lane_order(h, a);
     if (rc != PNP_OK) return rc;
     if (a.B == 0) return PNP_OK;        // (a mask without a lane: nothing to solve)
+    HIP_TRY(h, kLaneFamilies[family].launch(a, h->stream));
+  } else {
+    HIP_TRY(h, launch_newton(a, blocks, h->stream));
   }
-  if (use_lane4) HIP_TRY(h, launch_newton_lane4(a, h->stream));
-  else if (use_lane2) HIP_TRY(h, launch_newton_lane2(a, h->stream));
-  else if (use_lane) HIP_TRY(h, launch_newton_lane(a, h->stream));
-  else HIP_TRY(h, launch_newton(a, blocks, h->stream));
   h->steps_done += nsteps;
   h->iters_valid = true;
   return PNP_OK;
@@ -1405,17 +1401,117 @@ static void free_dev(pnp_handle* h, double** p, size_t bytes) {
   *p = nullptr;
 }
 
+// ---- trials of pnp_autotune and pnp_tune_placement: timesteps on the handle's own state, which is put back before every trial and at
+// the end with everything a step moves along (six device arrays and the host's bookkeeping); the copies live for one call and are not
+// counted in dev_bytes
+struct Trials {
+  pnp_handle* h;
+  const char* who;      // the entry point, for the error messages
+  struct {
+    void *live, *kept;
+    size_t bytes;
+  } items[6];
+  int64_t steps0 = 0;
+  bool hist0 = false, iters0 = false;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+
+  Trials(pnp_handle* h_, const char* who_) : h(h_), who(who_) {
+    const size_t nc = (size_t)h->B * h->a.N * h->a.ldx, nv = (size_t)h->B * h->a.ldx, ni = (size_t)h->B;
+    items[0] = {h->c, nullptr, nc * sizeof(double)};
+    items[1] = {h->v, nullptr, nv * sizeof(double)};
+    items[2] = {h->c_old2, nullptr, nc * sizeof(double)};
+    items[3] = {h->phi_old2, nullptr, nv * sizeof(double)};
+    items[4] = {h->status, nullptr, ni * sizeof(int32_t)};
+    items[5] = {h->iters, nullptr, ni * sizeof(int32_t)};
+  }
+  ~Trials() {
+    for (auto& it : items)
+      if (it.kept) (void)hipFree(it.kept);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  hipError_t alloc() {      // the snapshot's memory
+    for (auto& it : items) {
+      if (!it.live) continue;
+      const hipError_t e = hipMalloc(&it.kept, it.bytes);
+      if (e != hipSuccess) {
+        it.kept = nullptr;
+        return e;
+      }
+    }
+    return hipSuccess;
+  }
+  hipError_t copy(bool back) {
+    for (auto& it : items) {
+      if (!it.live || !it.kept) continue;
+      const hipError_t e = hipMemcpyAsync(back ? it.live : it.kept, back ? it.kept : it.live, it.bytes, hipMemcpyDeviceToDevice, h->stream);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  hipError_t begin() {      // take the snapshot, create the two events
+    hipError_t e = copy(false);
+    steps0 = h->steps_done;
+    hist0 = h->bdf_history;
+    iters0 = h->iters_valid;
+    if (e == hipSuccess) e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    return e;
+  }
+  int restore(bool sync = false) {
+    h->steps_done = steps0;
+    h->bdf_history = hist0;
+    h->iters_valid = iters0;
+    if (copy(true) != hipSuccess || (sync && hipStreamSynchronize(h->stream) != hipSuccess))
+      return fail(h, PNP_EDEVICE, std::string(who) + ": restoring the state failed");
+    return PNP_OK;
+  }
+  // the device's clocks settle over ~0.1 s of load: without this the first trials are timed on a cold device (measured: the lane-quad
+  // kernel, first in pnp_autotune's list, 11.7 ms per step against 7.6 ms warm at 8192 x 8 x 512)
+  int warm_up() {
+    int rc = PNP_OK;
+    for (auto t0 = std::chrono::steady_clock::now(); rc == PNP_OK && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(200);) {
+      rc = restore();
+      if (rc == PNP_OK) rc = newton_timesteps(h, 1);
+      if (rc == PNP_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, PNP_EDEVICE, std::string(who) + ": synchronisation failed");
+    }
+    return rc;
+  }
+  // one trial under the handle's current options: a first pass of one timestep (it allocates the workspace and warms the caches), then
+  // nsteps timesteps timed between the two events, both from the snapshot
+  int time(int nsteps, float* ms) {
+    int rc = PNP_OK;
+    for (int pass = 0; pass < 2 && rc == PNP_OK; ++pass) {
+      rc = restore();
+      if (rc == PNP_OK && hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(h, PNP_EDEVICE, std::string(who) + ": hipEventRecord");
+      if (rc == PNP_OK) rc = newton_timesteps(h, pass == 0 ? 1 : nsteps);
+      if (rc == PNP_OK && (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                           hipEventElapsedTime(ms, e0, e1) != hipSuccess))
+        rc = fail(h, PNP_EDEVICE, std::string(who) + ": timing a trial failed");
+    }
+    return rc;
+  }
+};
+
 int32_t pnp_autotune_default(const pnp_handle* h) {
   if (!h || !h->newton || !h->have_batch) return -1;
   Options o = h->opt;
   o.newton_kernel = NK_AUTO;
   o.lane_fused = -1;
-  const int nb = h->a.N + 1, nx = h->a.nx, variant = newton_variant(h);
-  const int64_t n_eff = newton_effective_batch(h);
-  if (newton_lane4_preferred(nb, nx, n_eff, variant, o)) return 0;
-  if (newton_lane2_preferred(nb, nx, n_eff, variant, o)) return 1;
-  if (newton_lane_preferred(nb, nx, n_eff, variant, o)) return 3;      // (timesteps: fused at every batch, pnp_lane.hip: launch_lane_nb)
-  return 4;
+  // (the lane kernel: "lane+fused", fused for timesteps at every batch, pnp_lane.hip: launch_lane_nb)
+  static const int32_t kChoice[] = {0 /* lane4 */, 1 /* lane2 */, 3 /* lane+fused */, 4 /* workgroup */};
+  return kChoice[newton_family(h, o)];
+}
+
+// can kernel choice k (NK_*) run this handle's batch at all?
+static bool newton_kernel_applicable(const pnp_handle* h, int k) {
+  const int nb = h->a.N + 1, nx = h->a.nx;
+  for (const LaneFamily& f : kLaneFamilies)
+    if (k == f.kernel) return f.supported(nb, nx, newton_variant(h));
+  if (k == NK_TEAM) return nb >= 3 && h->work != nullptr;
+  if (k == NK_SWEEP) return nb >= 3;
+  if (k == NK_BOTH) return nb >= 6 && nx >= 8;
+  return true;
 }
 
 int pnp_autotune(pnp_handle* h, int32_t nsteps, double* ms_per_step, int32_t* chosen) {
@@ -1424,91 +1520,25 @@ int pnp_autotune(pnp_handle* h, int32_t nsteps, double* ms_per_step, int32_t* ch
   if (!h->have_batch) return fail(h, PNP_ESTATE, "pnp_autotune: call pnp_set_batch first");
   if (nsteps < 1 || nsteps > 64) return fail(h, PNP_EINVAL, "pnp_autotune: nsteps must be 1 ... 64");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  const int N = h->a.N, nx = h->a.nx, ldx = h->a.ldx, nb = N + 1;
+  const int nb = h->a.N + 1, nx = h->a.nx;
   const int64_t B = h->B;
-  const int variant = newton_variant(h);
-  const size_t nc = (size_t)B * N * ldx, nv = (size_t)B * ldx;
-  // the trial steps run on the handle's own state: it is put back after every trial, with everything a step moves along
-  double *save_c = nullptr, *save_v = nullptr, *save_c2 = nullptr, *save_p2 = nullptr;
-  int32_t *save_st = nullptr, *save_it = nullptr;
-  struct Cleanup {
-    pnp_handle* h;
-    double **a, **b, **c, **d;
-    int32_t **e, **f;
-    ~Cleanup() {
-      for (double** p : {a, b, c, d})
-        if (*p) (void)hipFree(*p);
-      for (int32_t** p : {e, f})
-        if (*p) (void)hipFree(*p);
-    }
-  } cleanup{h, &save_c, &save_v, &save_c2, &save_p2, &save_st, &save_it};
-  HIP_TRY(h, hipMalloc((void**)&save_c, nc * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&save_v, nv * sizeof(double)));
-  HIP_TRY(h, hipMalloc((void**)&save_st, (size_t)B * sizeof(int32_t)));
-  HIP_TRY(h, hipMalloc((void**)&save_it, (size_t)B * sizeof(int32_t)));
-  if (h->c_old2) HIP_TRY(h, hipMalloc((void**)&save_c2, nc * sizeof(double)));
-  if (h->phi_old2) HIP_TRY(h, hipMalloc((void**)&save_p2, nv * sizeof(double)));
-  auto copy = [&](bool back) -> hipError_t {
-    struct {
-      void *live, *kept;
-      size_t bytes;
-    } items[6] = {{h->c, save_c, nc * sizeof(double)},        {h->v, save_v, nv * sizeof(double)},
-                  {h->c_old2, save_c2, nc * sizeof(double)},  {h->phi_old2, save_p2, nv * sizeof(double)},
-                  {h->status, save_st, (size_t)B * sizeof(int32_t)}, {h->iters, save_it, (size_t)B * sizeof(int32_t)}};
-    for (auto& it : items) {
-      if (!it.live || !it.kept) continue;
-      const hipError_t e = hipMemcpyAsync(back ? it.live : it.kept, back ? it.kept : it.live, it.bytes, hipMemcpyDeviceToDevice, h->stream);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  };
-  HIP_TRY(h, copy(false));
+  Trials tr(h, "pnp_autotune");
+  HIP_TRY(h, tr.alloc());
+  HIP_TRY(h, tr.begin());
   const Options opt0 = h->opt;
-  const int64_t steps0 = h->steps_done;
-  const bool hist0 = h->bdf_history, iters0 = h->iters_valid;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIP_TRY(h, hipEventCreate(&e0));
-  HIP_TRY(h, hipEventCreate(&e1));
   double best = -1.0;
-  int best_i = -1, rc = PNP_OK;
+  int best_i = -1;
   int64_t best_ok = -1;
   std::vector<int32_t> st((size_t)B);
-  // the device's clocks settle over ~0.1 s of load: without this the first families tried are timed on a cold device (measured: the
-  // lane-quad kernel, first in the list, 11.7 ms per step against 7.6 ms warm at 8192 x 8 x 512)
-  for (auto t0 = std::chrono::steady_clock::now(); rc == PNP_OK && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(200);) {
-    h->steps_done = steps0;
-    h->bdf_history = hist0;
-    h->iters_valid = iters0;
-    if (copy(true) != hipSuccess) rc = fail(h, PNP_EDEVICE, "pnp_autotune: restoring the state failed");
-    if (rc == PNP_OK) rc = newton_timesteps(h, 1);
-    if (rc == PNP_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, PNP_EDEVICE, "pnp_autotune: synchronisation failed");
-  }
+  int rc = tr.warm_up();
   for (int i = 0; i < PNP_AUTOTUNE_CHOICES && rc == PNP_OK; ++i) {
     if (ms_per_step) ms_per_step[i] = -1.0;
-    const int k = kTuneChoices[i].kernel;
-    const bool applicable = k == NK_LANE4   ? newton_lane4_supported(nb, nx, variant)
-                            : k == NK_LANE2 ? newton_lane2_supported(nb, nx, variant)
-                            : k == NK_LANE  ? newton_lane_supported(nb, nx, variant)
-                            : k == NK_TEAM  ? (nb >= 3 && h->work != nullptr)
-                            : k == NK_SWEEP ? nb >= 3
-                            : k == NK_BOTH  ? (nb >= 6 && nx >= 8)
-                                            : true;
-    if (!applicable) continue;
+    if (!newton_kernel_applicable(h, kTuneChoices[i].kernel)) continue;
     h->opt = opt0;
-    h->opt.newton_kernel = k;
+    h->opt.newton_kernel = kTuneChoices[i].kernel;
     h->opt.lane_fused = kTuneChoices[i].fused;
     float ms = 0.0f;
-    for (int pass = 0; pass < 2 && rc == PNP_OK; ++pass) {      // the first pass allocates the family's workspace and warms the caches
-      h->steps_done = steps0;
-      h->bdf_history = hist0;
-      h->iters_valid = iters0;
-      if (copy(true) != hipSuccess) rc = fail(h, PNP_EDEVICE, "pnp_autotune: restoring the state failed");
-      if (rc == PNP_OK && hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(h, PNP_EDEVICE, "pnp_autotune: hipEventRecord");
-      if (rc == PNP_OK) rc = newton_timesteps(h, pass == 0 ? 1 : nsteps);
-      if (rc == PNP_OK && (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                           hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = fail(h, PNP_EDEVICE, "pnp_autotune: timing a trial failed");
-    }
+    rc = tr.time(nsteps, &ms);
     if (rc != PNP_OK) break;
     if (hipMemcpy(st.data(), h->status, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
       rc = fail(h, PNP_EDEVICE, "pnp_autotune: reading the status failed");
@@ -1525,24 +1555,17 @@ int pnp_autotune(pnp_handle* h, int32_t nsteps, double* ms_per_step, int32_t* ch
       best_ok = ok;
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   h->opt = opt0;
-  h->steps_done = steps0;
-  h->bdf_history = hist0;
-  h->iters_valid = iters0;
-  if (copy(true) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, PNP_EDEVICE, "pnp_autotune: restoring the state failed");
+  const int restored = tr.restore(true);
+  if (restored != PNP_OK) return restored;
   if (rc != PNP_OK) return rc;
   if (best_i < 0) return fail(h, PNP_ESTATE, "pnp_autotune: no kernel family applies");
   h->opt.newton_kernel = kTuneChoices[best_i].kernel;
   h->opt.lane_fused = kTuneChoices[best_i].fused;
   // the workspaces of the families that lost go back to the device
   const int nk = h->opt.newton_kernel;
-  if (nk != NK_LANE) free_dev(h, &h->lane_buf, (size_t)h->lane_groups * (newton_lane_rec_doubles(nb, nx) + newton_lane_state_doubles(nb, nx)) * sizeof(double));
-  if (nk != NK_LANE2)
-    free_dev(h, &h->lane2_buf, (size_t)h->lane2_groups * (newton_lane2_rec_doubles(nb, nx) + newton_lane2_state_doubles(nb, nx)) * sizeof(double));
-  if (nk != NK_LANE4)
-    free_dev(h, &h->lane4_buf, (size_t)h->lane4_groups * (newton_lane4_rec_doubles(nb, nx) + newton_lane4_state_doubles(nb, nx)) * sizeof(double));
+  for (int f = 0; f < NUM_LANE_FAMILIES; ++f)
+    if (nk != kLaneFamilies[f].kernel) free_dev(h, &h->lane_ws[f].buf, (size_t)h->lane_ws[f].groups * lane_group_doubles(h, (NewtonFamily)f) * sizeof(double));
   if (nk == NK_LANE || nk == NK_LANE2 || nk == NK_LANE4 || nk == NK_TEAM)
     free_dev(h, &h->sweep, (size_t)h->sweep_blocks * newton_sweep_doubles(nb, nx) * (size_t)(64 / nb) * sizeof(double));
   if (chosen) *chosen = best_i;
@@ -1563,113 +1586,49 @@ int pnp_tune_placement(pnp_handle* h, int32_t nsteps, int32_t trials, double* ms
   if (nsteps < 1 || nsteps > 64 || trials < 1 || trials > 16) return fail(h, PNP_EINVAL, "pnp_tune_placement: nsteps 1 ... 64, trials 1 ... 16");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   for (int i = 0; i < trials && ms_per_step; ++i) ms_per_step[i] = -1.0;
-  const int N = h->a.N, nx = h->a.nx, ldx = h->a.ldx, nb = N + 1, variant = newton_variant(h);
-  const int64_t B = h->B, n_eff = newton_effective_batch(h);
-  double** bufp = nullptr;
-  int64_t* groupsp = nullptr;
-  size_t per_group = 0;
-  if (newton_lane4_preferred(nb, nx, n_eff, variant, h->opt)) {
-    bufp = &h->lane4_buf, groupsp = &h->lane4_groups, per_group = newton_lane4_rec_doubles(nb, nx) + newton_lane4_state_doubles(nb, nx);
-  } else if (newton_lane2_preferred(nb, nx, n_eff, variant, h->opt)) {
-    bufp = &h->lane2_buf, groupsp = &h->lane2_groups, per_group = newton_lane2_rec_doubles(nb, nx) + newton_lane2_state_doubles(nb, nx);
-  } else if (newton_lane_preferred(nb, nx, n_eff, variant, h->opt)) {
-    bufp = &h->lane_buf, groupsp = &h->lane_groups, per_group = newton_lane_rec_doubles(nb, nx) + newton_lane_state_doubles(nb, nx);
-  }
-  if (!bufp) return PNP_OK;      // (no lane kernel for this batch: nothing to place)
-  const size_t nc = (size_t)B * N * ldx, nv = (size_t)B * ldx;
-  struct Saved {
-    void *live, *kept;
-    size_t bytes;
-  } items[6] = {{h->c, nullptr, nc * sizeof(double)},        {h->v, nullptr, nv * sizeof(double)},
-                {h->c_old2, nullptr, nc * sizeof(double)},  {h->phi_old2, nullptr, nv * sizeof(double)},
-                {h->status, nullptr, (size_t)B * sizeof(int32_t)}, {h->iters, nullptr, (size_t)B * sizeof(int32_t)}};
+  const NewtonFamily family = newton_family(h, h->opt);
+  if (family == NF_WORKGROUP) return PNP_OK;      // (no lane kernel for this batch: nothing to place)
+  pnp_handle::LaneWorkspace& ws = h->lane_ws[family];
+  const size_t per_group = lane_group_doubles(h, family);
+  Trials tr(h, "pnp_tune_placement");
+  if (tr.alloc() != hipSuccess) return fail(h, PNP_ENOMEM, "pnp_tune_placement: no memory for the state snapshot");
+  if (tr.begin() != hipSuccess) return fail(h, PNP_EDEVICE, "pnp_tune_placement: set-up failed");
   std::vector<double*> held;      // the workspaces of the trials so far
-  auto release = [&]() {      // the snapshot, and every workspace but the one the handle keeps
-    for (auto& it : items)
-      if (it.kept) (void)hipFree(it.kept);
-    for (double* p : held)
-      if (p && p != *bufp) {
-        (void)hipFree(p);
-        h->dev_bytes -= (int64_t)((size_t)*groupsp * per_group * sizeof(double));
-      }
-    held.clear();
-  };
-  for (auto& it : items)
-    if (it.live && hipMalloc(&it.kept, it.bytes) != hipSuccess) {
-      it.kept = nullptr;
-      release();
-      return fail(h, PNP_ENOMEM, "pnp_tune_placement: no memory for the state snapshot");
-    }
-  auto copy = [&](bool back) -> bool {
-    for (auto& it : items)
-      if (it.live && it.kept &&
-          hipMemcpyAsync(back ? it.live : it.kept, back ? it.kept : it.live, it.bytes, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-        return false;
-    return true;
-  };
-  const int64_t steps0 = h->steps_done;
-  const bool hist0 = h->bdf_history, iters0 = h->iters_valid;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = PNP_OK, best_i = -1;
+  int rc = tr.warm_up(), best_i = -1;      // (clocks up before the first placement is timed)
   double best = 0.0;
-  double* best_buf = *bufp;
-  if (!copy(false) || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(h, PNP_EDEVICE, "pnp_tune_placement: set-up failed");
-  // (clocks up before the first placement is timed: ~0.2 s of the same launches, see pnp_autotune)
-  for (auto t0 = std::chrono::steady_clock::now(); rc == PNP_OK && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(200);) {
-    h->steps_done = steps0;
-    h->bdf_history = hist0;
-    h->iters_valid = iters0;
-    if (!copy(true)) rc = fail(h, PNP_EDEVICE, "pnp_tune_placement: restoring the state failed");
-    if (rc == PNP_OK) rc = newton_timesteps(h, 1);
-    if (rc == PNP_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, PNP_EDEVICE, "pnp_tune_placement: synchronisation failed");
-  }
+  double* best_buf = ws.buf;
   for (int i = 0; i < trials && rc == PNP_OK; ++i) {
     if (i > 0) {
       // the next placement: run_newton allocates on first use, while the earlier workspaces are still there -- if the device has room for
       // it twice over (other handles and other processes on the device allocate too), else what was measured so far decides
       size_t free_b = 0, total_b = 0;
-      const size_t W = (size_t)*groupsp * per_group * sizeof(double);
+      const size_t W = (size_t)ws.groups * per_group * sizeof(double);
       if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * W + ((size_t)4 << 30)) break;
-      *bufp = nullptr;
+      ws.buf = nullptr;
     }
     float ms = 0.0f;
-    for (int pass = 0; pass < 2 && rc == PNP_OK; ++pass) {      // (the first pass allocates and warms)
-      h->steps_done = steps0;
-      h->bdf_history = hist0;
-      h->iters_valid = iters0;
-      if (!copy(true)) rc = fail(h, PNP_EDEVICE, "pnp_tune_placement: restoring the state failed");
-      if (rc == PNP_OK && hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(h, PNP_EDEVICE, "pnp_tune_placement: hipEventRecord");
-      if (rc == PNP_OK) rc = newton_timesteps(h, pass == 0 ? 1 : nsteps);
-      if (rc == PNP_OK && (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                           hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = fail(h, PNP_EDEVICE, "pnp_tune_placement: timing a trial failed");
-    }
+    rc = tr.time(nsteps, &ms);
     if (rc == PNP_ENOMEM && i > 0) {      // no room for another placement: what was measured so far decides
       rc = PNP_OK;
-      if (*bufp) held.push_back(*bufp);
+      if (ws.buf) held.push_back(ws.buf);
       break;
     }
     if (rc != PNP_OK) break;
-    held.push_back(*bufp);
+    held.push_back(ws.buf);
     const double per_step = (double)ms / nsteps;
     if (ms_per_step) ms_per_step[i] = per_step;
     if (best_i < 0 || per_step < best) {
       best = per_step;
       best_i = i;
-      best_buf = *bufp;
+      best_buf = ws.buf;
     }
   }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (*bufp && std::find(held.begin(), held.end(), *bufp) == held.end()) held.push_back(*bufp);      // (a trial that failed after allocating)
-  *bufp = best_buf;
-  h->steps_done = steps0;
-  h->bdf_history = hist0;
-  h->iters_valid = iters0;
-  const bool restored = copy(true) && hipStreamSynchronize(h->stream) == hipSuccess;
-  release();
-  if (!restored) return fail(h, PNP_EDEVICE, "pnp_tune_placement: restoring the state failed");
-  return rc;
+  if (ws.buf && std::find(held.begin(), held.end(), ws.buf) == held.end()) held.push_back(ws.buf);      // (a trial that failed after allocating)
+  ws.buf = best_buf;
+  const int restored = tr.restore(true);
+  for (double* p : held)      // every workspace but the one the handle keeps
+    if (p != ws.buf) free_dev(h, &p, (size_t)ws.groups * per_group * sizeof(double));
+  return restored != PNP_OK ? restored : rc;
 }
 
 int pnp_step(pnp_handle* h, int32_t nsteps, int32_t steps_per_launch) {

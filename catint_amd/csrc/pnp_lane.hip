@@ -1149,37 +1149,9 @@ hipError_t launch_lane_transpose(const NewtonArgs& a, int64_t ngroups, bool in, 
   return hipGetLastError();
 }
 
-bool newton_lane2_preferred(int nb, int nx, int64_t B, int mode, const Options& opt) {
-  if (!newton_lane2_supported(nb, nx, mode)) return false;
-  if (opt.newton_kernel != NK_AUTO) return opt.newton_kernel == NK_LANE2;
-  // Measured on one device in one call (tools/probe/lane2_probe.sh; N = 8, nx = 512, timesteps/s, lane pair / lane / lane teams):
-  // B = 1024 1.16e5 / 1.00e5 / 1.40e5, 2048 2.40e5 / 1.96e5 / 1.43e5, 4096 4.51e5 / 3.85e5 / 1.44e5, 8192 7.31e5 / 7.07e5 / 1.51e5,
-  // 16 384 0.99e6 / 1.03e6.  Twice the waves for the same batch, but the distribution overhead (selects, DPP moves, duplicated
-  // assembly) leaves a wave's pace only 1.28 x the lane kernel's and two waves on a CU cost each other ~20 %.
-  // Round 4: below 10 240 points the lane-quad kernel (pnp_lane4.hip) is ahead of both; the pair keeps the window up to the lane
-  // kernel's crossover (profiles/r04_lane4_probe.jsonl: B = 12 288 lane pair 9.96e5 / lane 9.55e5 / lane quad 7.78e5; 16 384 1.05e6 /
-  // 1.10e6 / 0.87e6).
-  // End of the window, measured again with the fused lane kernel as the alternative (profiles/r04_family_rates.jsonl; lane pair /
-  // lane fused): N = 8, nx = 512: B = 14 336 1.17e6 / 1.05e6, 16 384 (1024 waves of 16 points: the last batch in one round) 1.25e6 /
-  // 1.19e6, 18 432 0.97e6 / 1.20e6; N = 8, nx = 1024: 16 384 5.6e5 / 5.4e5; N = 6, nx = 1024: 12 288 7.6e5 / 7.4e5, 14 336 7.8e5 / 8.1e5;
-  // N = 6, nx = 512: 12 288 1.62e6 / 1.58e6, 16 384 1.90e6 / 2.04e6.
-  // N = 7, nx = 512 (profiles/r04_family_rates_n5_n7.jsonl): 12 288 1.39e6 / 1.28e6, 14 336 1.44e6 / 1.47e6;  N = 5: 10 240 1.79e6 / 1.86e6,
-  // 12 288 2.12e6 / 2.26e6 -- no window above the lane quad's.
-  return B >= 1280 && B <= (nb >= 9 ? 16384 : (nb >= 7 ? 13311 : 10239));
-}
-
 template <int NB>
 static hipError_t launch_lane_nb(const NewtonArgs& a0, hipStream_t stream) {
-  const int64_t groups = (a0.B + LG - 1) / LG;
-  const int64_t cap = a0.lane_groups > 0 ? a0.lane_groups : 1;
-  for (int64_t g0 = 0; g0 < groups; g0 += cap) {
-    NewtonArgs a = a0;
-    a.lane_group0 = g0;
-    a.lane_lg = LG;
-    a.lane_pivot_limit = lane_pivot_limit(a.opt);
-    const int64_t ng = groups - g0 < cap ? groups - g0 : cap;
-    const dim3 tg((unsigned)ng, (unsigned)((a.nx + 63) / 64));
-    hipLaunchKernelGGL((lane_transpose_kernel<true>), tg, dim3(256), 0, stream, a);
+  return launch_lane_chunks<LG>(a0, stream, [&](const NewtonArgs& a, int64_t ng) {
     // FUSED: update inside the back-substitution, two state copies, no round trip of the Newton update (-8 % of the bytes; a damped
     // iteration walks the back-substitution twice).  Timesteps: at every batch since the records move with non-temporal accesses
     // (tools/probe/family_rates.py -> profiles/r04_family_rates.jsonl, one device, one call, 20-step launches, timesteps/s separate /
@@ -1211,9 +1183,7 @@ static hipError_t launch_lane_nb(const NewtonArgs& a0, hipStream_t stream) {
       else if (mode == 1) hipLaunchKernelGGL((newton_lane_kernel<NB, 1, false>), gk, bk, 0, stream, a);
       else hipLaunchKernelGGL((newton_lane_kernel<NB, 0, false>), gk, bk, 0, stream, a);
     }
-    hipLaunchKernelGGL((lane_transpose_kernel<false>), tg, dim3(256), 0, stream, a);
-  }
-  return hipGetLastError();
+  });
 }
 
 hipError_t launch_newton_lane(const NewtonArgs& a, hipStream_t stream) {

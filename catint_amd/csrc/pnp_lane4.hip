@@ -965,24 +965,13 @@ __global__ __launch_bounds__(64) void newton_lane4_kernel(const NewtonArgs G) {
 
 template <int NB>
 static hipError_t launch_lane4_nb(const NewtonArgs& a0, hipStream_t stream) {
-  const int64_t groups = (a0.B + QG - 1) / QG;
-  const int64_t cap = a0.lane_groups > 0 ? a0.lane_groups : 1;
-  for (int64_t g0 = 0; g0 < groups; g0 += cap) {
-    NewtonArgs a = a0;
-    a.lane_group0 = g0;
-    a.lane_lg = QG;
-    a.lane_pivot_limit = lane_pivot_limit(a.opt);
-    a.lane_stagger = (a.opt && a.opt->lane_stagger >= 0) ? a.opt->lane_stagger : 0;
-    const int64_t ng = groups - g0 < cap ? groups - g0 : cap;
-    hipError_t e = launch_lane_transpose(a, ng, true, stream);
-    if (e != hipSuccess) return e;
+  NewtonArgs as = a0;
+  as.lane_stagger = (as.opt && as.opt->lane_stagger >= 0) ? as.opt->lane_stagger : 0;
+  return launch_lane_chunks<QG>(as, stream, [&](const NewtonArgs& a, int64_t ng) {
     if (a.rt || a.convect) LAUNCH_BDF(2);
     else if (a.mpb) LAUNCH_BDF(1);
     else LAUNCH_BDF(0);
-    e = launch_lane_transpose(a, ng, false, stream);
-    if (e != hipSuccess) return e;
-  }
-  return hipGetLastError();
+  });
 }
 
 hipError_t launch_newton_lane4(const NewtonArgs& a, hipStream_t stream) {

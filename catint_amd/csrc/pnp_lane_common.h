@@ -49,6 +49,27 @@ constexpr double PIVOT_GROWTH_LIMIT = 1e8;
 // (option LANE_PIVOT_LIMIT overrides it: tests set it below one so that every lane trips the monitor)
 inline double lane_pivot_limit(const Options* opt) { return (opt && opt->lane_pivot_limit > 0.0) ? opt->lane_pivot_limit : PIVOT_GROWTH_LIMIT; }
 
+// Host side of every lane family: the batch is walked in chunks of a.lane_groups groups of PG operating points (what the workspace
+// holds); each chunk is transposed in, solved by launch(a, groups of the chunk) -- the family's kernel -- and transposed back out.
+template <int PG, typename Launch>
+inline hipError_t launch_lane_chunks(const NewtonArgs& a0, hipStream_t stream, Launch launch) {
+  const int64_t groups = (a0.B + PG - 1) / PG;
+  const int64_t cap = a0.lane_groups > 0 ? a0.lane_groups : 1;
+  for (int64_t g0 = 0; g0 < groups; g0 += cap) {
+    NewtonArgs a = a0;
+    a.lane_group0 = g0;
+    a.lane_lg = PG;
+    a.lane_pivot_limit = lane_pivot_limit(a.opt);
+    const int64_t ng = groups - g0 < cap ? groups - g0 : cap;
+    hipError_t e = launch_lane_transpose(a, ng, true, stream);
+    if (e != hipSuccess) return e;
+    launch(a, ng);
+    e = launch_lane_transpose(a, ng, false, stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipGetLastError();
+}
+
 struct LaneParams {
   double sig[PNP_NEWTON_MAX_SPECIES], peq[PNP_NEWTON_MAX_SPECIES];
   double pe[PNP_NEWTON_MAX_SPECIES], rs[PNP_NEWTON_MAX_SPECIES];      // MODE 2: convection v dx / D_k, reaction scale dx^2 / D_k

@@ -2340,7 +2340,8 @@ static hipError_t launch_newton_nb(const NewtonArgs& a, int blocks, hipStream_t 
   const bool generic = opt.newton_kernel == NK_GENERIC;     // forces the row-per-thread kernel (tests)
   const int tp = generic ? 0 : newton_pair_threads(NB, a.nx);
   if constexpr (NB >= 3) {
-    if (a.sweep && a.sweep_blocks > 0 && newton_sweep_preferred(NB, a.nx, a.B, a.rt ? 2 : (a.mpb ? 1 : 0), opt)) {
+    // (run_newton hands over the sweep workspace exactly when newton_sweep_preferred holds for this batch)
+    if (a.sweep && a.sweep_blocks > 0) {
       if constexpr (NB >= 6) {
         if (newton_sweep_two_sided(NB, a.nx, a.B, a.rt ? 2 : (a.mpb ? 1 : 0), opt)) return launch_sweep2<NB>(a, stream);
       }
