@@ -76,8 +76,10 @@ struct pnp_handle {
   int nw_ext_old = 0;                       // set around a prepared step: c_old is given (BDF2 combination or c_n under the predictor)
   double nw_sig_scale = 1.0;                // ... and 1/dt carries the factor 3/2 of BDF2
   int nw_bdf2_inline = 0, nw_bdf_hist0 = 0; // set around a launch of several BDF2 steps by a lane kernel, which keeps the history itself
-  bool bdf_history = false;                 // c_old2 holds the level before the current state (false after an upload, a change of
-                                            // time_order, a stationary solve or patched lanes: the next step is backward Euler)
+  std::vector<uint8_t> lane_hist;           // per lane: c_old2 (phi_old2) holds the level before its current state (cleared by an upload
+                                            // and a change of time_order / predictor for every lane, by a stationary solve or patch for
+                                            // the lanes it touched: their next step is backward Euler)
+  int nw_family = -1;                       // >= 0: the family every launch of one pnp_step call uses (sized by the caller's mask)
   ReactionSides* rs_dev = nullptr;          // the table flattened per reaction side (lane kernels)
   int rs_max_exponent = 0;
   int n_wk = 0;
@@ -110,9 +112,13 @@ struct pnp_handle {
   double* scf_snap = nullptr;            // (N + 1) ldx B doubles: per-lane state of the last converged transport solve
   int32_t* scf_i = nullptr;              // 3 B flags + 65 counters
   const int32_t* newton_mask = nullptr;  // lanes to solve (null: all)
+  const int32_t* newton_mask_host = nullptr;  // ... its host copy, when the host has one (not the SCF loop's device flags): a masked
+  int64_t newton_mask_count = 0;         // solve is sized (kernel choice, lane groups) by the lanes it solves
   int32_t* user_mask = nullptr;          // pnp_set_lane_mask's copy
-  std::vector<int32_t> user_mask_host;   // ... and on the host: a masked solve is sized (kernel choice, lane groups) by the lanes it solves
+  std::vector<int32_t> user_mask_host;
   int64_t user_mask_count = 0;
+  int32_t* sub_mask = nullptr;           // device [2][capacity]: the active lanes of a call without / with a history, when both occur
+  std::vector<int32_t> sub_mask_host;    // ... [2][B]
   bool newton_explicit_kinetics = false; // the wall-kinetics table feeds the prescribed fluxes instead of the Jacobian
   int cur = 0;  // lapl[cur] = charge row of the current state; lapl[1-cur] = row used by the last step
   // pnp_step with several launches in one call: the batch is cut into row chunks whose launch sequences run on streams of their own
@@ -216,7 +222,7 @@ void pnp_destroy(pnp_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->c, (void*)h->lapl[0], (void*)h->lapl[1], (void*)h->v, (void*)h->gradv, (void*)h->rates,
                   (void*)h->pb, (void*)h->vzeta, (void*)h->flux, (void*)h->cbulk, (void*)h->csurf, (void*)h->status,
-                  (void*)h->spec, (void*)h->ytmp, (void*)h->ftmp, (void*)h->c_old, (void*)h->work, (void*)h->iters, (void*)h->stash, (void*)h->rt_dev, (void*)h->rs_dev, (void*)h->c_old2, (void*)h->phi_old2, (void*)h->vol_dev, (void*)h->bdf_acc, (void*)h->wk_k, (void*)h->gw, (void*)h->gv, (void*)h->mol_lapl, (void*)h->scf_d, (void*)h->scf_i, (void*)h->scf_snap, (void*)h->stage, (void*)h->sweep, (void*)h->lane_perm, (void*)h->user_mask, (void*)h->ode_buf, (void*)h->ode_int, (void*)h->rkc_d, (void*)h->rkc_i})
+                  (void*)h->spec, (void*)h->ytmp, (void*)h->ftmp, (void*)h->c_old, (void*)h->work, (void*)h->iters, (void*)h->stash, (void*)h->rt_dev, (void*)h->rs_dev, (void*)h->c_old2, (void*)h->phi_old2, (void*)h->vol_dev, (void*)h->bdf_acc, (void*)h->wk_k, (void*)h->gw, (void*)h->gv, (void*)h->mol_lapl, (void*)h->scf_d, (void*)h->scf_i, (void*)h->scf_snap, (void*)h->stage, (void*)h->sweep, (void*)h->lane_perm, (void*)h->user_mask, (void*)h->sub_mask, (void*)h->ode_buf, (void*)h->ode_int, (void*)h->rkc_d, (void*)h->rkc_i})
     if (p) (void)hipFree(p);
   for (const auto& ws : h->lane_ws)
     if (ws.buf) (void)hipFree(ws.buf);
@@ -556,6 +562,7 @@ int pnp_set_batch(pnp_handle* h, int64_t B, const double* c0, const double* pb, 
   const int N = h->a.N, nx = h->a.nx, ldx = h->a.ldx;
   h->B = B;
   h->newton_mask = nullptr;      // (a lane mask belongs to the batch it was set for)
+  h->newton_mask_host = nullptr;
   h->a.B = B;
   // One contiguous upload into a staging buffer; unpack_state_kernel writes the pitched rows (zero pads: they travel through
   // the kernels untouched), the bulk Dirichlet values = last grid point of the initial state (calculator_old.py:540) and the
@@ -575,7 +582,7 @@ int pnp_set_batch(pnp_handle* h, int64_t B, const double* c0, const double* pb, 
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->have_batch = true;
     h->steps_done = 0;
-    h->bdf_history = false;
+    h->lane_hist.assign((size_t)B, 0);
     // lane kernels: the iteration counters were just zeroed (unpack_state_kernel), so the first solve of this batch deals the
     // operating points by their wall-to-bulk potential difference
     h->iters_valid = false;
@@ -734,7 +741,7 @@ static int lane_order(pnp_handle* h, NewtonArgs& a) {
   if (!h->lane_perm_keep) h->lane_perm_B = 0;
   // a solve restricted by pnp_set_lane_mask (the rerun ladder's confirming solve: a handful of recovered lanes): only the lanes it solves
   // are dealt to slots, and the launch covers ceil(n / points per group) groups instead of the whole batch
-  const bool masked = h->newton_mask && h->newton_mask == h->user_mask && (int64_t)h->user_mask_host.size() == B && h->user_mask_count < B;
+  const bool masked = h->newton_mask && h->newton_mask_host && h->newton_mask_count < B;
   if ((h->opt.lane_order == 0 || B < 64) && !masked) return PNP_OK;
   if (h->lane_perm_keep && h->lane_perm && h->lane_perm_B > 0) {      // the order of this call's first launch
     a.lane_perm = h->lane_perm;
@@ -772,7 +779,7 @@ static int lane_order(pnp_handle* h, NewtonArgs& a) {
   if (masked) {      // keep the order, drop the lanes that are not solved
     size_t n = 0;
     for (int64_t s_ = 0; s_ < B; ++s_)
-      if (h->user_mask_host[(size_t)perm[(size_t)s_]] != 0) perm[n++] = perm[(size_t)s_];
+      if (h->newton_mask_host[(size_t)perm[(size_t)s_]] != 0) perm[n++] = perm[(size_t)s_];
     for (size_t s_ = n; s_ < (size_t)B; ++s_) perm[s_] = perm[n > 0 ? n - 1 : 0];
     a.B = (int64_t)n;
   }
@@ -790,15 +797,16 @@ static int lane_order(pnp_handle* h, NewtonArgs& a) {
 // 2 u_n - u_n-1 of the two previous levels (concentrations and potential) instead of from u_n -- the start of a BDF stepper; same
 // equations, same stopping rule, fewer iterations.  A concentration is not extrapolated below a tenth of its value, and a point whose
 // extrapolated ions would fill more than 90 % of the volume keeps u_n.  One launch per timestep: the previous-level combination and the
-// start are prepared here (one thread per grid point), the kernels take c_old as given.
+// start are prepared here (one thread per grid point), the kernels take c_old as given.  Lanes outside `mask` (null: none) are neither
+// read nor written: the history is per lane.
 __global__ void step_prepare_kernel(double* __restrict__ c, double* __restrict__ c2, double* __restrict__ cold, double* __restrict__ phi,
                                     double* __restrict__ phi2, int N, int ldx, int nx, int64_t B, int bdf2, int predictor,
-                                    const double* __restrict__ vol /* [N] device copy, or null */) {
+                                    const double* __restrict__ vol /* [N] device copy, or null */, const int32_t* __restrict__ mask) {
   const int64_t total = B * (int64_t)ldx;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = t / ldx;
     const int i = (int)(t - b * ldx);
-    if (i >= nx) continue;
+    if (i >= nx || (mask && !mask[b])) continue;
     double fill = 0.0;
     if (predictor) {
       for (int k = 0; k < N; ++k) {
@@ -826,10 +834,24 @@ __global__ void step_prepare_kernel(double* __restrict__ c, double* __restrict__
     }
   }
 }
-// per-lane bookkeeping over the launches of one call: iteration counts add up, the worst status stays
-__global__ void bdf2_accumulate_kernel(int32_t* __restrict__ acc, int32_t* __restrict__ iters, int32_t* __restrict__ status, int64_t B, int last) {
+// the first step of a lane's trajectory under a mask: its state u_0 becomes its history (without a mask: two copies of the whole batch)
+__global__ void history_start_kernel(const double* __restrict__ c, double* __restrict__ c2, const double* __restrict__ phi,
+                                     double* __restrict__ phi2 /* null: no predictor */, int N, int ldx, int64_t B,
+                                     const int32_t* __restrict__ mask) {
+  const int64_t total = B * (int64_t)ldx;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = t / ldx;
+    const int i = (int)(t - b * ldx);
+    if (!mask[b]) continue;
+    for (int k = 0; k < N; ++k) c2[((size_t)b * N + k) * ldx + i] = c[((size_t)b * N + k) * ldx + i];
+    if (phi2) phi2[(size_t)b * ldx + i] = phi[(size_t)b * ldx + i];
+  }
+}
+// per-lane bookkeeping over the launches of one call: iteration counts add up, the worst status stays (lanes outside `mask`: untouched)
+__global__ void bdf2_accumulate_kernel(int32_t* __restrict__ acc, int32_t* __restrict__ iters, int32_t* __restrict__ status, int64_t B, int last,
+                                       const int32_t* __restrict__ mask) {
   const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (b >= B) return;
+  if (b >= B || (mask && !mask[b])) return;
   const int32_t it = acc[b] + iters[b], st = status[b] > acc[B + b] ? status[b] : acc[B + b];
   acc[b] = it;
   acc[B + b] = st;
@@ -853,8 +875,8 @@ static int newton_variant(const pnp_handle* h) {
 // (a solve restricted to a few lanes by pnp_set_lane_mask is sized by those lanes: the workgroup-per-point kernels skip masked-out
 // points at once, the lane kernels would walk every group)
 static int64_t newton_effective_batch(const pnp_handle* h) {
-  const bool host_mask = h->newton_mask && h->newton_mask == h->user_mask && (int64_t)h->user_mask_host.size() == h->B;
-  return host_mask ? (h->user_mask_count > 0 ? h->user_mask_count : 1) : h->B;
+  const bool host_mask = h->newton_mask && h->newton_mask_host;
+  return host_mask ? (h->newton_mask_count > 0 ? h->newton_mask_count : 1) : h->B;
 }
 
 // the kernel family that runs this handle's batch under options o (the one place the choice is made: run_newton, newton_timesteps,
@@ -900,7 +922,28 @@ static int lane_workspace(pnp_handle* h, NewtonFamily f, NewtonArgs& a) {
   return PNP_OK;
 }
 
-// nsteps timesteps of the physical mode: one launch (backward Euler), or one launch per step (BDF2 and / or the predictor)
+// launches of one call restricted to a mask of the handle's own (the active lanes of one history class), set around run_newton
+struct MaskScope {
+  pnp_handle* h;
+  const int32_t *dev, *host;
+  int64_t count;
+  MaskScope(pnp_handle* h_, const int32_t* d, const int32_t* hm, int64_t n)
+      : h(h_), dev(h_->newton_mask), host(h_->newton_mask_host), count(h_->newton_mask_count) {
+    h->newton_mask = d;
+    h->newton_mask_host = hm;
+    h->newton_mask_count = n;
+  }
+  ~MaskScope() {
+    h->newton_mask = dev;
+    h->newton_mask_host = host;
+    h->newton_mask_count = count;
+  }
+};
+
+// nsteps timesteps of the physical mode: one launch (backward Euler), or one launch per step (BDF2 and / or the predictor).
+// The history is per lane (lane_hist): a lane's first step is backward Euler from u_0, which becomes its history, whatever the other
+// lanes do.  A call whose active lanes all have a history, or none has, makes the launches of one batch; one that mixes them starts with
+// a launch for each class under masks of its own (sub_mask) -- the device code never sees more than one class.
 static int newton_timesteps(pnp_handle* h, int nsteps) {
   const bool bdf2 = h->np.time_order == 2, pred = h->np.predictor == 1;
   if ((!bdf2 && !pred) || nsteps < 1) return run_newton(h, nsteps, false, 0.0, 0);
@@ -909,16 +952,75 @@ static int newton_timesteps(pnp_handle* h, int nsteps) {
   const int64_t B = h->B;
   const size_t cap = (size_t)h->cfg.batch_capacity;
   if (!h->c_old2) HIP_TRY(h, dev_alloc(h, &h->c_old2, cap * N * ldx));
-  if (bdf2 && !pred && newton_family(h, h->opt) != NF_WORKGROUP) {
+  // the lanes of this call (the caller's mask) by history
+  const int32_t* um = h->newton_mask ? h->newton_mask_host : nullptr;
+  if ((int64_t)h->lane_hist.size() != B) h->lane_hist.assign((size_t)B, 0);
+  int64_t n_act = 0, n_hist = 0;
+  for (int64_t b = 0; b < B; ++b)
+    if (!um || um[b]) {
+      ++n_act;
+      n_hist += h->lane_hist[(size_t)b] ? 1 : 0;
+    }
+  const bool mixed = n_hist > 0 && n_hist < n_act, all_hist = n_act > 0 && n_hist == n_act;
+  const int32_t *m_new = nullptr, *m_old = nullptr;      // device: the active lanes without / with a history (mixed calls)
+  if (mixed) {
+    if (!h->sub_mask) HIP_TRY(h, dev_alloc(h, &h->sub_mask, cap * 2));
+    h->sub_mask_host.assign((size_t)B * 2, 0);
+    for (int64_t b = 0; b < B; ++b)
+      if (!um || um[b]) h->sub_mask_host[(size_t)(h->lane_hist[(size_t)b] ? B + b : b)] = 1;
+    HIP_TRY(h, hipMemcpyAsync(h->sub_mask, h->sub_mask_host.data(), (size_t)B * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    m_new = h->sub_mask;
+    m_old = h->sub_mask + B;
+  }
+  auto mark = [&] {      // the active lanes have a history from here on
+    for (int64_t b = 0; b < B; ++b)
+      if (!um || um[b]) h->lane_hist[(size_t)b] = 1;
+  };
+  // every launch of the call runs the family the caller's mask sizes (a class of a mixed call is no batch of its own)
+  struct Pin {
+    pnp_handle* h;
+    ~Pin() {
+      h->nw_family = -1;
+      h->nw_bdf2_inline = 0;
+      h->nw_bdf_hist0 = 0;
+      h->nw_ext_old = 0;
+      h->nw_sig_scale = 1.0;
+    }
+  } pin{h};
+  h->nw_family = newton_family(h, h->opt);
+  auto accumulate = [&](int last) -> int {
+    hipLaunchKernelGGL(bdf2_accumulate_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->bdf_acc, h->iters, h->status, B,
+                       last, h->newton_mask);
+    HIP_TRY(h, hipGetLastError());
+    return PNP_OK;
+  };
+  int rc = PNP_OK;
+  if (bdf2 && !pred && h->nw_family != NF_WORKGROUP) {
     // the lane kernels keep the history themselves: ONE launch for all nsteps (the first step of a trajectory is backward Euler
     // from u_0, which becomes the history -- as below), c_old2 is the history's home between launches
     h->nw_bdf2_inline = 1;
-    h->nw_bdf_hist0 = (h->steps_done == 0 || !h->bdf_history) ? 0 : 1;
-    const int rc = run_newton(h, nsteps, false, 0.0, 0);
-    h->nw_bdf2_inline = 0;
-    h->nw_bdf_hist0 = 0;
+    if (!mixed) {
+      h->nw_bdf_hist0 = all_hist ? 1 : 0;
+      rc = run_newton(h, nsteps, false, 0.0, 0);
+    } else {
+      // one step for each class, then the rest of the call for all of them
+      if (!h->bdf_acc) HIP_TRY(h, dev_alloc(h, &h->bdf_acc, cap * 2));
+      HIP_TRY(h, hipMemsetAsync(h->bdf_acc, 0, (size_t)B * 2 * sizeof(int32_t), h->stream));
+      for (int g = 0; g < 2 && rc == PNP_OK; ++g) {
+        MaskScope ms(h, g ? m_old : m_new, h->sub_mask_host.data() + (g ? B : 0), g ? n_hist : n_act - n_hist);
+        h->nw_bdf_hist0 = g;
+        rc = run_newton(h, 1, false, 0.0, 0);
+      }
+      if (rc == PNP_OK) rc = accumulate(nsteps == 1 ? 1 : 0);
+      if (rc == PNP_OK && nsteps > 1) {
+        h->nw_bdf_hist0 = 1;
+        rc = run_newton(h, nsteps - 1, false, 0.0, 0);
+        if (rc == PNP_OK) rc = accumulate(1);
+      }
+    }
     if (rc != PNP_OK) return rc;
-    h->bdf_history = true;
+    mark();
     return PNP_OK;
   }
   if (pred && !h->phi_old2) HIP_TRY(h, dev_alloc(h, &h->phi_old2, cap * ldx));
@@ -930,35 +1032,61 @@ static int newton_timesteps(pnp_handle* h, int nsteps) {
     pnp_handle* h;
     ~KeepPerm() { h->lane_perm_keep = false; }
   } keep_guard{h};
-  for (int s = 0; s < nsteps; ++s) {
-    h->lane_perm_keep = s > 0;
-    if (h->steps_done == 0 || !h->bdf_history) {      // first step of a trajectory: backward Euler from u_0, which becomes the history
+  // first step of a trajectory: backward Euler from u_0, which becomes the history (mask: the lanes that take it, null: all)
+  auto first_step = [&](const int32_t* mask) -> int {
+    if (!mask) {
       HIP_TRY(h, hipMemcpyAsync(h->c_old2, h->c, n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
       if (pred) HIP_TRY(h, hipMemcpyAsync(h->phi_old2, h->v, (size_t)B * ldx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-      const int rc = run_newton(h, 1, false, 0.0, 0);
-      if (rc != PNP_OK) return rc;
-      h->bdf_history = true;
     } else {
-      hipLaunchKernelGGL(step_prepare_kernel, dim3(2048), dim3(256), 0, h->stream, h->c, h->c_old2, h->c_old, h->v, h->phi_old2, N, ldx, nx, B,
-                         bdf2 ? 1 : 0, pred ? 1 : 0, (const double*)(pred && h->mpb ? h->vol_dev : nullptr));
+      hipLaunchKernelGGL(history_start_kernel, dim3(2048), dim3(256), 0, h->stream, (const double*)h->c, h->c_old2, (const double*)h->v,
+                         pred ? h->phi_old2 : nullptr, N, ldx, B, mask);
       HIP_TRY(h, hipGetLastError());
-      h->nw_ext_old = 1;
-      h->nw_sig_scale = bdf2 ? 1.5 : 1.0;
-      const int rc = run_newton(h, 1, false, 0.0, 0);
-      h->nw_ext_old = 0;
-      h->nw_sig_scale = 1.0;
-      if (rc != PNP_OK) return rc;
     }
-    hipLaunchKernelGGL(bdf2_accumulate_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->bdf_acc, h->iters, h->status, B,
-                       s + 1 == nsteps ? 1 : 0);
+    return run_newton(h, 1, false, 0.0, 0);
+  };
+  // a step with the history at hand: previous-level combination and start prepared, then one launch
+  auto next_step = [&](const int32_t* mask) -> int {
+    hipLaunchKernelGGL(step_prepare_kernel, dim3(2048), dim3(256), 0, h->stream, h->c, h->c_old2, h->c_old, h->v, h->phi_old2, N, ldx, nx, B,
+                       bdf2 ? 1 : 0, pred ? 1 : 0, (const double*)(pred && h->mpb ? h->vol_dev : nullptr), mask);
     HIP_TRY(h, hipGetLastError());
+    h->nw_ext_old = 1;
+    h->nw_sig_scale = bdf2 ? 1.5 : 1.0;
+    const int r = run_newton(h, 1, false, 0.0, 0);
+    h->nw_ext_old = 0;
+    h->nw_sig_scale = 1.0;
+    return r;
+  };
+  for (int s = 0; s < nsteps; ++s) {
+    h->lane_perm_keep = s > (mixed ? 1 : 0);
+    if (s == 0 && mixed) {
+      {
+        MaskScope ms(h, m_new, h->sub_mask_host.data(), n_act - n_hist);
+        rc = first_step(m_new);
+      }
+      if (rc == PNP_OK) {
+        MaskScope ms(h, m_old, h->sub_mask_host.data() + B, n_hist);
+        rc = next_step(m_old);
+      }
+    } else if (s == 0 && !all_hist) {
+      rc = first_step(h->newton_mask);
+    } else {
+      rc = next_step(h->newton_mask);
+    }
+    if (rc != PNP_OK) return rc;
+    if (s == 0) mark();
+    rc = accumulate(s + 1 == nsteps ? 1 : 0);
+    if (rc != PNP_OK) return rc;
   }
   return PNP_OK;
 }
 
 // physical mode: nsteps backward-Euler steps (stationary: one solve with 1/dt = 0) in one launch
 static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, int maxit) {
-  if (stationary) h->bdf_history = false;      // (a stationary solve moves the state off the trajectory)
+  if (stationary) {      // (a stationary solve moves the lanes it solves off their trajectories; the SCF loop's lanes: pnp_scf_cycle)
+    if ((int64_t)h->lane_hist.size() != h->B) h->lane_hist.assign((size_t)h->B, 0);
+    for (int64_t b = 0; b < h->B; ++b)
+      if (!h->newton_mask || (h->newton_mask_host && h->newton_mask_host[b])) h->lane_hist[(size_t)b] = 0;
+  }
   NewtonArgs a;
   memset(&a, 0, sizeof(a));
   const int N = h->a.N, nx = h->a.nx;
@@ -1004,7 +1132,7 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   a.bdf_hist0 = a.bdf2 ? h->nw_bdf_hist0 : 0;
   a.c_old2 = a.bdf2 ? h->c_old2 : nullptr;
   a.opt = &h->opt;
-  const NewtonFamily family = newton_family(h, h->opt);
+  const NewtonFamily family = h->nw_family >= 0 ? (NewtonFamily)h->nw_family : newton_family(h, h->opt);
   if (family != NF_WORKGROUP) {
     const int rc = lane_workspace(h, family, a);
     if (rc != PNP_OK) return rc;
@@ -1068,7 +1196,7 @@ int pnp_set_newton(pnp_handle* h, const pnp_newton_params* p, const double* mpb_
   if (p->wall_bc == 1 && !(p->stern_capacitance > 0)) return fail(h, PNP_EINVAL, "pnp_set_newton: Stern capacitance must be positive");
   if (p->maxit < 1 || !(p->tol > 0)) return fail(h, PNP_EINVAL, "pnp_set_newton: maxit >= 1 and tol > 0 required");
   if (p->time_order < 0 || p->time_order > 2) return fail(h, PNP_EINVAL, "pnp_set_newton: time_order must be 0, 1 (backward Euler) or 2 (BDF2)");
-  if (p->time_order != h->np.time_order || p->predictor != h->np.predictor) h->bdf_history = false;
+  if (p->time_order != h->np.time_order || p->predictor != h->np.predictor) std::fill(h->lane_hist.begin(), h->lane_hist.end(), (uint8_t)0);
   if (p->predictor != 0 && p->predictor != 1) return fail(h, PNP_EINVAL, "pnp_set_newton: predictor must be 0 or 1");
   h->np = *p;
   h->mpb = false;
@@ -1278,7 +1406,11 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
   const int every = p->check_every > 0 ? (p->check_every < 32 ? p->check_every : 32) : 8;
   int rc = PNP_OK;
   int32_t left = 1;
-  h->newton_mask = a.active;
+  // the loop's stationary solves restrict themselves to the lanes still active: those active now leave their trajectories
+  if ((int64_t)h->lane_hist.size() != B) h->lane_hist.assign((size_t)B, 0);
+  for (int64_t b = 0; b < B; ++b)
+    if (s->active[b]) h->lane_hist[(size_t)b] = 0;
+  const MaskScope caller_mask(h, a.active, nullptr, 0);      // (the caller's mask is back in force on return)
   h->newton_explicit_kinetics = true;
   for (int istep = p->istep + 1; istep <= p->max_iter && rc == PNP_OK; ++istep) {
     a.istep = istep;
@@ -1300,7 +1432,6 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
     }
     if (e != hipSuccess) rc = fail(h, PNP_EDEVICE, std::string("pnp_scf_cycle: ") + hipGetErrorString(e));
   }
-  h->newton_mask = nullptr;
   h->newton_explicit_kinetics = false;
   if (rc != PNP_OK) return rc;
   int32_t last = 0;
@@ -1351,7 +1482,9 @@ int pnp_set_lanes(pnp_handle* h, int64_t n, const int64_t* lanes, const double* 
   for (int64_t i = 0; i < n; ++i)
     if (lanes[i] < 0 || lanes[i] >= h->B) return fail(h, PNP_EINVAL, "pnp_set_lanes: lane index out of range");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  h->bdf_history = false;        // (the patched lanes have no previous time level of their own: the next BDF2 step starts over)
+  // (the patched lanes have no previous time level of their own: their next BDF2 / predictor step starts over; the others keep theirs)
+  if ((int64_t)h->lane_hist.size() != h->B) h->lane_hist.assign((size_t)h->B, 0);
+  for (int64_t i = 0; i < n; ++i) h->lane_hist[(size_t)lanes[i]] = 0;
   const int N = h->a.N, nx = h->a.nx, ldx = h->a.ldx;
   const size_t w = (size_t)nx * sizeof(double), dp = (size_t)ldx * sizeof(double);
   // a handful of lanes: one strided copy per lane (N rows of the concentrations, one of the potential), all on the handle's stream
@@ -1371,6 +1504,7 @@ int pnp_set_lane_mask(pnp_handle* h, const int32_t* mask) {
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   if (!mask) {
     h->newton_mask = nullptr;
+    h->newton_mask_host = nullptr;
     return PNP_OK;
   }
   h->user_mask_host.assign(mask, mask + h->B);
@@ -1380,6 +1514,8 @@ int pnp_set_lane_mask(pnp_handle* h, const int32_t* mask) {
   HIP_TRY(h, hipMemcpyAsync(h->user_mask, mask, (size_t)h->B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->newton_mask = h->user_mask;
+  h->newton_mask_host = h->user_mask_host.data();
+  h->newton_mask_count = h->user_mask_count;
   return PNP_OK;
 }
 
@@ -1412,7 +1548,8 @@ struct Trials {
     size_t bytes;
   } items[6];
   int64_t steps0 = 0;
-  bool hist0 = false, iters0 = false;
+  std::vector<uint8_t> hist0;
+  bool iters0 = false;
   hipEvent_t e0 = nullptr, e1 = nullptr;
 
   Trials(pnp_handle* h_, const char* who_) : h(h_), who(who_) {
@@ -1452,7 +1589,7 @@ struct Trials {
   hipError_t begin() {      // take the snapshot, create the two events
     hipError_t e = copy(false);
     steps0 = h->steps_done;
-    hist0 = h->bdf_history;
+    hist0 = h->lane_hist;
     iters0 = h->iters_valid;
     if (e == hipSuccess) e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -1460,7 +1597,7 @@ struct Trials {
   }
   int restore(bool sync = false) {
     h->steps_done = steps0;
-    h->bdf_history = hist0;
+    h->lane_hist = hist0;
     h->iters_valid = iters0;
     if (copy(true) != hipSuccess || (sync && hipStreamSynchronize(h->stream) != hipSuccess))
       return fail(h, PNP_EDEVICE, std::string(who) + ": restoring the state failed");

@@ -309,10 +309,13 @@ int pnp_set_potential(pnp_handle* h, const double* phi);
 /* Overwrite the state (concentrations c[n][N][nx], potential phi[n][nx]) of the n lanes lanes[0..n) and leave every other lane, the
  * iteration counters, the bulk values and the status flags alone: how a lane recovered elsewhere -- on a finer continuation ramp or
  * a finer mesh, the reference's rerun ladder (catint/calculator.py:466-531) -- comes back into the batch without the whole state
- * crossing PCIe.  phi may be NULL (potential rows unchanged). */
+ * crossing PCIe.  phi may be NULL (potential rows unchanged).  A lane's BDF2 / predictor history is its own: the patched lanes
+ * restart with a backward-Euler step, every other lane keeps its history. */
 int pnp_set_lanes(pnp_handle* h, int64_t n, const int64_t* lanes, const double* c, const double* phi);
 /* Restrict the following pnp_step / pnp_solve_stationary / pnp_solve_surface calls of the physical mode to the lanes with a non-zero
- * mask[b] (the others keep state, status and iteration counters); mask == NULL: all lanes again.  The mask is copied. */
+ * mask[b] (the others keep state, status, iteration counters and their BDF2 / predictor history: a masked-out call is a skipped call);
+ * mask == NULL: all lanes again.  A lane's history is its own: a stationary solve restarts only the lanes it solves (their next step is
+ * backward Euler).  pnp_scf_cycle runs its own lane activity and leaves this mask in force.  The mask is copied. */
 int pnp_set_lane_mask(pnp_handle* h, const int32_t* mask /* [B] or NULL */);
 
 /* Debug: the order in which the most recent lane-kernel launch of this handle dealt the operating points to its slots (slot s = group *
