@@ -29,7 +29,10 @@ def relerr(a, b):
 
 
 # ---- configs[4]: 65536 lanes over 8 GPUs -> 8192 lanes per GPU, 8 species, 4096 points ----------------------------------------
-def test_config5_share_physical_mode_sweep_kernel_8192_lanes():
+def test_config5_share_physical_mode_lane4_kernel_8192_lanes():
+    """One GPU's share of configs[4]: 8192 lanes x 8 size-modified species x 4096 points, Stern wall, two implicit timesteps -- the
+    library's choice at this batch is the lane-quad kernel (pnp_lane4.hip); the sampled lanes solved again as a small batch take a
+    workgroup-per-point kernel."""
     B, N, nx = 8192, 8, 4096
     prob, c0, pb, vz, fl = make_batch(B, N, nx, seed=8, phi_max=0.2, dt_factor=0.1)
     pb = np.nan_to_num(pb)
@@ -40,12 +43,13 @@ def test_config5_share_physical_mode_sweep_kernel_8192_lanes():
                              batch_capacity=len(idx)) as s:
             s.set_newton(**kw)
             s.set_batch(c0[idx], pb[idx], vz[idx], fl[idx])
+            assert s.default_family() == ('lane4' if len(idx) == B else 'workgroup')
             s.step(steps)
             cs, vs, es = s.get_surface()
             full = s.get_state() if len(idx) <= 64 else None
             return cs, vs, s.newton_iterations(), s.get_status(), full
 
-    cs, vs, its, st, _ = solve(np.arange(B), 2)                     # the library's choice at this batch: the lane kernel (pnp_lane.hip)
+    cs, vs, its, st, _ = solve(np.arange(B), 2)                     # the library's choice at this batch: the lane-quad kernel (pnp_lane4.hip)
     assert np.all(st == 0) and np.all(np.isfinite(cs)) and cs.min() > 0 and its.min() >= 4 and its.max() <= 2 * 50
     # lane permutation: teams pick the lanes up in another order, results must follow the lanes
     perm = np.random.default_rng(3).permutation(B)
@@ -60,7 +64,7 @@ def test_config5_share_physical_mode_sweep_kernel_8192_lanes():
         assert sum(rit) == its[b], (b, rit, its[b])
         assert np.abs(cs[b] - rc[:, 0]).max() <= 2e-9 * np.abs(rc).max()
         assert abs(vs[b] - rphi[0]) <= 2e-9 * 0.2
-    # the same lanes solved as a small batch (lane-team kernel): whole profiles against the oracle, surface values against the sweep
+    # the same lanes solved as a small batch (workgroup-per-point kernel): whole profiles against the oracle, surface values against the sweep
     cs3, vs3, its3, st3, full = solve(sub, 2)
     assert np.array_equal(its3, its[sub]) and np.abs(cs3 - cs[sub]).max() <= 1e-9 * np.abs(cs).max()
     b = sub[1]
@@ -70,8 +74,8 @@ def test_config5_share_physical_mode_sweep_kernel_8192_lanes():
     assert np.abs(full[0][1] - rc).max() <= 2e-9 * np.abs(rc).max() and np.abs(full[1][1] - rphi).max() <= 2e-9 * 0.2
 
 
-def test_half_size_batch_of_large_blocks_lane_kernel_and_both_sweeps():
-    """4096 lanes x 8 size-modified species x 512 points: the library's choice is the lane kernel (one operating point per lane) --
+def test_half_size_batch_of_large_blocks_lane4_kernel_and_both_sweeps():
+    """4096 lanes x 8 size-modified species x 512 points: the library's choice is the lane-quad kernel (pnp_lane4.hip) --
     lane permutation property, sampled lanes against the oracle incl. iteration counts, and the same lanes through the one-sided and
     the two-sided sweep kernels (lane teams; 585 / 1366 waves)."""
     B, N, nx = 4096, 8, 512
@@ -84,6 +88,8 @@ def test_half_size_batch_of_large_blocks_lane_kernel_and_both_sweeps():
                              batch_capacity=len(idx)) as s:
             s.set_newton(**kw)
             s.set_batch(c0[idx], pb[idx], vz[idx], fl[idx])
+            if len(idx) == B:
+                assert s.default_family() == 'lane4'
             s.step(steps)
             cs, vs, es = s.get_surface()
             return cs, vs, s.newton_iterations(), s.get_status()

@@ -47,7 +47,9 @@ def make_lanes(N, nx, B, seed, phi_lo=-0.15, phi_hi=0.15, points_per_debye=6.0, 
 
 
 def run_both(N, nx, B, seed, dt=None, nsteps=1, stationary=True, newton_kw=None, flux=None, reactions=None, wall_kinetics=None, x=None,
-             velocity=0.0, **lane_kw):
+             velocity=0.0, lanes=None, **lane_kw):
+    """The batch on the GPU and (lanes: a list of operating points; None: all of them) on the oracle: (c, phi, iterations, status) of
+    the whole batch, (c, phi, iterations) of the oracle's lanes in their order."""
     newton_kw = dict(newton_kw or {})
     D, q, cb, dx, phiM = make_lanes(N, nx, B, seed, **lane_kw)
     c0 = np.repeat(cb[:, :, None], nx, axis=2)
@@ -82,8 +84,9 @@ def run_both(N, nx, B, seed, dt=None, nsteps=1, stationary=True, newton_kw=None,
                estimate=bool(newton_kw.get('error_estimate', False)))
     if okw['dphi_max'] <= 0:
         okw['dphi_max'] = None
-    ref_c = np.zeros_like(c); ref_phi = np.zeros_like(phi); ref_it = np.zeros(B, int)
-    for b in range(B):
+    sel = list(range(B)) if lanes is None else list(lanes)
+    ref_c = np.zeros((len(sel),) + c.shape[1:]); ref_phi = np.zeros((len(sel),) + phi.shape[1:]); ref_it = np.zeros(len(sel), int)
+    for j, b in enumerate(sel):
         p = PH.PhysicalProblem(D=D, charges=q, beta=BETA, eps=EPS, dx=dx, nx=nx, c_bulk=cb[b], phiM=phiM[b], flux=fl[b],
                                stern_capacitance=newton_kw.get('stern_capacitance') if newton_kw.get('wall_bc') == 'stern' else None,
                                phi_pzc=newton_kw.get('phi_pzc', 0.0), mpb_radius=newton_kw.get('mpb_radius'), reactions=reactions,
@@ -91,12 +94,12 @@ def run_both(N, nx, B, seed, dt=None, nsteps=1, stationary=True, newton_kw=None,
         cc, ph = c0[b].copy(), np.zeros(nx)
         if stationary:
             cc, ph, it, _ = PH.newton_step(p, cc, ph, cc, np.inf, **okw)
-            ref_it[b] = it
+            ref_it[j] = it
         else:
             cc, ph, its_b = PH.integrate(p, cc, ph, dt, nsteps, bdf2=newton_kw.get('time_order', 1) == 2,
                                          predictor=bool(newton_kw.get('predictor', False)), **okw)
-            ref_it[b] = sum(its_b)
-        ref_c[b], ref_phi[b] = cc, ph
+            ref_it[j] = sum(its_b)
+        ref_c[j], ref_phi[j] = cc, ph
     return (c, phi, its, st), (ref_c, ref_phi, ref_it)
 
 
@@ -525,10 +528,11 @@ def test_config2_batch_physical_mode_full_size_properties():
         assert np.abs(c[b] - rc).max() <= 2e-9 * np.abs(rc).max() and np.abs(phi[b] - rphi).max() <= 2e-9 * 0.2
 
 
-def test_config4_per_gpu_share_through_the_sweep_kernel():
+def test_config4_per_gpu_share_through_the_lane_kernel():
     """BASELINE configs[3] (6 species x 1024 points, 262144 lanes over 8 GPUs): one GPU's 32768 lanes, size-modified with a Stern
-    wall, two implicit timesteps -- the batch takes the sweep kernel.  Every lane converges, sampled lanes equal the oracle, and
-    a lane does not depend on its position in the batch (teams pick lanes up in a different order)."""
+    wall, two implicit timesteps -- the batch takes the lane kernel (pnp_lane.hip, update fused into the back-substitution), 64 of its
+    lanes the lane-team kernel.  Every lane converges, sampled lanes equal the oracle, and a lane does not depend on its position in
+    the batch."""
     from catint_amd.synthetic import make_batch
     B, N, nx = 32768, 6, 1024
     prob, c0, pb, vz, fl = make_batch(B, N, nx, seed=6, phi_max=0.2, dt_factor=0.1)
@@ -540,6 +544,7 @@ def test_config4_per_gpu_share_through_the_sweep_kernel():
         with _capi.PnpSolver(N, nx, prob.dx, prob.dt, prob.beta, prob.eps, prob.D, prob.charges, method='Newton', batch_capacity=len(idx)) as s:
             s.set_newton(**kw)
             s.set_batch(c0[idx], pb[idx], vz[idx], fl[idx])
+            assert s.default_family() == ('lane+fused' if len(idx) == B else 'workgroup')
             s.step(steps)
             cs, vs, es = s.get_surface()
             return cs, vs, s.newton_iterations(), s.get_status(), (s.get_state() if len(idx) <= 64 else None)
