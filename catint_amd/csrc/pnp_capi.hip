@@ -17,24 +17,6 @@
 
 using namespace pnp;
 
-// kernel families of the physical mode, as newton_family picks them: the three lane kernels, then the workgroup-per-point kernels
-// (pnp_newton.hip: pair / team / sweep / row-per-thread, chosen by launch_newton)
-enum NewtonFamily { NF_LANE4 = 0, NF_LANE2, NF_LANE, NF_WORKGROUP };
-constexpr int NUM_LANE_FAMILIES = NF_WORKGROUP;
-
-// per lane family: operating points per group, the kernel choice that forces it, and its supported / sizing / launch functions
-static const struct LaneFamily {
-  int points;
-  int kernel;
-  bool (*supported)(int nb, int nx, int mode);
-  size_t (*rec_doubles)(int nb, int nx);
-  size_t (*state_doubles)(int nb, int nx);
-  hipError_t (*launch)(const NewtonArgs& a, hipStream_t stream);
-} kLaneFamilies[NUM_LANE_FAMILIES] = {
-    {8, NK_LANE4, newton_lane4_supported, newton_lane4_rec_doubles, newton_lane4_state_doubles, launch_newton_lane4},
-    {16, NK_LANE2, newton_lane2_supported, newton_lane2_rec_doubles, newton_lane2_state_doubles, launch_newton_lane2},
-    {32, NK_LANE, newton_lane_supported, newton_lane_rec_doubles, newton_lane_state_doubles, launch_newton_lane}};
-
 struct pnp_handle {
   pnp_config cfg;
   DevArgs a;
@@ -79,7 +61,8 @@ struct pnp_handle {
   std::vector<uint8_t> lane_hist;           // per lane: c_old2 (phi_old2) holds the level before its current state (cleared by an upload
                                             // and a change of time_order / predictor for every lane, by a stationary solve or patch for
                                             // the lanes it touched: their next step is backward Euler)
-  int nw_family = -1;                       // >= 0: the family every launch of one pnp_step call uses (sized by the caller's mask)
+  int nw_family = -1;                       // >= 0: the NewtonFamily every launch of one pnp_step call uses (sized by the caller's mask and,
+                                            // for the sweeps, by the full batch, which is constant within a call)
   ReactionSides* rs_dev = nullptr;          // the table flattened per reaction side (lane kernels)
   int rs_max_exponent = 0;
   int n_wk = 0;
@@ -869,7 +852,7 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
 static int newton_variant(const pnp_handle* h) {
   const bool rt = h->rt_dev && h->rt.n > 0;
   if (rt && h->rs_max_exponent > PNP_MAX_REACTANTS) return 3;
-  return (rt || h->velocity != 0.0) ? 2 : (h->mpb ? 1 : 0);
+  return newton_mode_lane(h->mpb, rt, h->velocity != 0.0);
 }
 
 // (a solve restricted to a few lanes by pnp_set_lane_mask is sized by those lanes: the workgroup-per-point kernels skip masked-out
@@ -879,27 +862,24 @@ static int64_t newton_effective_batch(const pnp_handle* h) {
   return host_mask ? (h->newton_mask_count > 0 ? h->newton_mask_count : 1) : h->B;
 }
 
-// the kernel family that runs this handle's batch under options o (the one place the choice is made: run_newton, newton_timesteps,
-// pnp_autotune_default, pnp_tune_placement).  The order matters: newton_lane2_preferred leaves the lane-quad window to
-// newton_lane4_preferred, and newton_lane_preferred the windows of both to them.
+// the kernel family that runs this handle's batch under options o (pnp_newton.hip: newton_family makes the choice; its callers:
+// run_newton, newton_timesteps, pnp_autotune_default, pnp_tune_placement)
 static NewtonFamily newton_family(const pnp_handle* h, const Options& o) {
-  const int nb = h->a.N + 1, nx = h->a.nx, variant = newton_variant(h);
-  const int64_t n_eff = newton_effective_batch(h);
-  if (newton_lane4_preferred(nb, nx, n_eff, variant, o)) return NF_LANE4;
-  if (newton_lane2_preferred(nb, nx, n_eff, variant, o)) return NF_LANE2;
-  if (newton_lane_preferred(nb, nx, n_eff, variant, o)) return NF_LANE;
-  return NF_WORKGROUP;
+  const bool rt = h->rt_dev && h->rt.n > 0;
+  const NewtonShape s = {h->a.N + 1, h->a.nx, h->B, newton_effective_batch(h), h->mpb, rt, h->velocity != 0.0, newton_variant(h) != 3,
+                         h->work != nullptr};
+  return newton_family(s, o);
 }
 
 static size_t lane_group_doubles(const pnp_handle* h, NewtonFamily f) {
-  const LaneFamily& F = kLaneFamilies[f];
+  const NewtonFamilyInfo& F = newton_family_info(f);
   return F.rec_doubles(h->a.N + 1, h->a.nx) + F.state_doubles(h->a.N + 1, h->a.nx);
 }
 
 // the workspace of lane family f for a launch: transposed state + records of as many groups as the batch capacity has, capped at
 // 48 GiB (the launcher walks a larger batch in chunks), allocated on first use; cut into the arrays of NewtonArgs
 static int lane_workspace(pnp_handle* h, NewtonFamily f, NewtonArgs& a) {
-  const LaneFamily& F = kLaneFamilies[f];
+  const NewtonFamilyInfo& F = newton_family_info(f);
   pnp_handle::LaneWorkspace& ws = h->lane_ws[f];
   const int N = h->a.N, nx = h->a.nx, P = F.points;
   const size_t per_group = lane_group_doubles(h, f) * sizeof(double);
@@ -996,7 +976,7 @@ static int newton_timesteps(pnp_handle* h, int nsteps) {
     return PNP_OK;
   };
   int rc = PNP_OK;
-  if (bdf2 && !pred && h->nw_family != NF_WORKGROUP) {
+  if (bdf2 && !pred && h->nw_family < NUM_LANE_FAMILIES) {
     // the lane kernels keep the history themselves: ONE launch for all nsteps (the first step of a trajectory is backward Euler
     // from u_0, which becomes the history -- as below), c_old2 is the history's home between launches
     h->nw_bdf2_inline = 1;
@@ -1133,12 +1113,13 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   a.c_old2 = a.bdf2 ? h->c_old2 : nullptr;
   a.opt = &h->opt;
   const NewtonFamily family = h->nw_family >= 0 ? (NewtonFamily)h->nw_family : newton_family(h, h->opt);
-  if (family != NF_WORKGROUP) {
+  const NewtonWorkspace ws = family < NUM_NEWTON_FAMILIES ? newton_family_info(family).ws : NW_EXCHANGE;
+  if (ws == NW_LANE) {
     const int rc = lane_workspace(h, family, a);
     if (rc != PNP_OK) return rc;
-  } else if (newton_sweep_preferred(N + 1, nx, h->B, a.rt ? 2 : (a.mpb ? 1 : 0), h->opt)) {
+  } else if (ws == NW_SWEEP) {
     // one team (N+1 lanes) per operating point, 64/(N+1) per wave; the workspace holds the records of the resident waves: at
-    // most four per SIMD, all of the batch capacity, and 32 GiB.  (a.sweep is the decision launch_newton follows: it is set here only.)
+    // most four per SIMD, all of the batch capacity, and 32 GiB
     const int64_t tpw = 64 / (N + 1);
     const size_t per_block = newton_sweep_doubles(N + 1, nx) * (size_t)tpw * sizeof(double);
     if (!h->sweep) {
@@ -1175,13 +1156,13 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   int blocks = h->nw_blocks;
   if (h->opt.newton_blocks >= 1 && h->opt.newton_blocks < blocks) blocks = h->opt.newton_blocks;      // tuning: size of the persistent grid
   if ((int64_t)blocks > h->B) blocks = (int)h->B;
-  if (family != NF_WORKGROUP) {
+  if (ws == NW_LANE) {
     const int rc = lane_order(h, a);
     if (rc != PNP_OK) return rc;
     if (a.B == 0) return PNP_OK;        // (a mask without a lane: nothing to solve)
-    HIP_TRY(h, kLaneFamilies[family].launch(a, h->stream));
+    HIP_TRY(h, newton_family_info(family).launch(a, h->stream));
   } else {
-    HIP_TRY(h, launch_newton(a, blocks, h->stream));
+    HIP_TRY(h, launch_newton(a, family, blocks, h->stream));
   }
   h->steps_done += nsteps;
   h->iters_valid = true;
@@ -1635,20 +1616,15 @@ int32_t pnp_autotune_default(const pnp_handle* h) {
   Options o = h->opt;
   o.newton_kernel = NK_AUTO;
   o.lane_fused = -1;
-  // (the lane kernel: "lane+fused", fused for timesteps at every batch, pnp_lane.hip: launch_lane_nb)
-  static const int32_t kChoice[] = {0 /* lane4 */, 1 /* lane2 */, 3 /* lane+fused */, 4 /* workgroup */};
-  return kChoice[newton_family(h, o)];
+  const NewtonFamily f = newton_family(h, o);
+  return f == NF_NONE ? -1 : newton_family_info(f).tune;
 }
 
-// can kernel choice k (NK_*) run this handle's batch at all?
-static bool newton_kernel_applicable(const pnp_handle* h, int k) {
-  const int nb = h->a.N + 1, nx = h->a.nx;
-  for (const LaneFamily& f : kLaneFamilies)
-    if (k == f.kernel) return f.supported(nb, nx, newton_variant(h));
-  if (k == NK_TEAM) return nb >= 3 && h->work != nullptr;
-  if (k == NK_SWEEP) return nb >= 3;
-  if (k == NK_BOTH) return nb >= 6 && nx >= 8;
-  return true;
+// the family that kernel choice k (NK_*) forces; NF_NONE: k is no family's own choice (NK_WORKGROUP)
+static NewtonFamily newton_forced_family(int k) {
+  for (int f = 0; f < NUM_NEWTON_FAMILIES; ++f)
+    if (k == newton_family_info(f).kernel) return (NewtonFamily)f;
+  return NF_NONE;
 }
 
 int pnp_autotune(pnp_handle* h, int32_t nsteps, double* ms_per_step, int32_t* chosen) {
@@ -1670,7 +1646,9 @@ int pnp_autotune(pnp_handle* h, int32_t nsteps, double* ms_per_step, int32_t* ch
   int rc = tr.warm_up();
   for (int i = 0; i < PNP_AUTOTUNE_CHOICES && rc == PNP_OK; ++i) {
     if (ms_per_step) ms_per_step[i] = -1.0;
-    if (!newton_kernel_applicable(h, kTuneChoices[i].kernel)) continue;
+    // (a forced family that cannot run this handle's batch at all is left out)
+    const NewtonFamily forced = newton_forced_family(kTuneChoices[i].kernel);
+    if (forced != NF_NONE && !newton_family_info(forced).runs(nb, nx, newton_variant(h), h->work != nullptr)) continue;
     h->opt = opt0;
     h->opt.newton_kernel = kTuneChoices[i].kernel;
     h->opt.lane_fused = kTuneChoices[i].fused;
@@ -1700,10 +1678,10 @@ int pnp_autotune(pnp_handle* h, int32_t nsteps, double* ms_per_step, int32_t* ch
   h->opt.newton_kernel = kTuneChoices[best_i].kernel;
   h->opt.lane_fused = kTuneChoices[best_i].fused;
   // the workspaces of the families that lost go back to the device
-  const int nk = h->opt.newton_kernel;
+  const NewtonFamily won = newton_forced_family(kTuneChoices[best_i].kernel);
   for (int f = 0; f < NUM_LANE_FAMILIES; ++f)
-    if (nk != kLaneFamilies[f].kernel) free_dev(h, &h->lane_ws[f].buf, (size_t)h->lane_ws[f].groups * lane_group_doubles(h, (NewtonFamily)f) * sizeof(double));
-  if (nk == NK_LANE || nk == NK_LANE2 || nk == NK_LANE4 || nk == NK_TEAM)
+    if (f != won) free_dev(h, &h->lane_ws[f].buf, (size_t)h->lane_ws[f].groups * lane_group_doubles(h, (NewtonFamily)f) * sizeof(double));
+  if (won != NF_NONE && (newton_family_info(won).ws == NW_LANE || newton_family_info(won).ws == NW_WORK))      // the lane and team choices
     free_dev(h, &h->sweep, (size_t)h->sweep_blocks * newton_sweep_doubles(nb, nx) * (size_t)(64 / nb) * sizeof(double));
   if (chosen) *chosen = best_i;
   return PNP_OK;
@@ -1724,7 +1702,7 @@ int pnp_tune_placement(pnp_handle* h, int32_t nsteps, int32_t trials, double* ms
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   for (int i = 0; i < trials && ms_per_step; ++i) ms_per_step[i] = -1.0;
   const NewtonFamily family = newton_family(h, h->opt);
-  if (family == NF_WORKGROUP) return PNP_OK;      // (no lane kernel for this batch: nothing to place)
+  if (family >= NUM_LANE_FAMILIES) return PNP_OK;      // (no lane kernel for this batch: nothing to place)
   pnp_handle::LaneWorkspace& ws = h->lane_ws[family];
   const size_t per_group = lane_group_doubles(h, family);
   Trials tr(h, "pnp_tune_placement");

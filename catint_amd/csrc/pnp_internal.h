@@ -3,6 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
+
 #include "../../include/catint_pnp.h"
 
 namespace pnp {
@@ -214,38 +217,93 @@ struct NewtonArgs {
                                          // lane_order) so that the lanes of a wave finish together.
   int32_t lane_lg, pad3_;                // operating points per group: 32 (lane kernel) or 16 (lane-pair kernel, pnp_lane2.hip)
   double lane_pivot_limit;               // pivot monitor of the lane kernels (pnp_lane_common.h): multipliers beyond this mark the lane
-  const Options* opt;                    // HOST pointer (the launchers' kernel choice); never dereferenced on the device
-  int32_t lane_stagger;
+  const Options* opt;                    // HOST pointer (the launchers' launch parameters); never dereferenced on the device
+  int32_t lane_stagger;                  // lane-quad kernel: wave g starts (g & 3) * lane_stagger sleep periods late (see pnp_lane4.hip)
   int32_t ext_old;                       // 1: c_old holds the previous-level combination of this (single) step, prepared by the caller
-                                         // (BDF2: (4 c_n - c_n-1)/3, with sig scaled by 3/2); the kernels do not overwrite it           // lane-quad kernel: wave g starts (g & 3) * lane_stagger sleep periods late (see pnp_lane4.hip)
+                                         // (BDF2: (4 c_n - c_n-1)/3, with sig scaled by 3/2); the kernels do not overwrite it
 };
-int newton_threads(int nb, int nx);
+
+// The MODE template argument of the kernels: 0 point ions, 1 steric ions, 2 + homogeneous reactions.  The two mappings differ in the
+// constant convection term: the workgroup-per-point kernels take it as a run-time flag inside MODE 0 / 1, the lane kernels compile it
+// into their MODE 2 only.
+inline int newton_mode_workgroup(bool mpb, bool reactions) { return reactions ? 2 : (mpb ? 1 : 0); }
+inline int newton_mode_lane(bool mpb, bool reactions, bool convect) { return (reactions || convect) ? 2 : (mpb ? 1 : 0); }
+// A run-time mode / switch as the compile-time argument of a generic lambda: f(std::integral_constant<int, MODE>), f(std::bool_constant<V>)
+template <typename F>
+inline void with_mode(int mode, F&& f) {
+  if (mode == 2) f(std::integral_constant<int, 2>{});
+  else if (mode == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
+}
+template <typename F>
+inline void with_flag(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+// ... and the block size NB = N + 1 among the instantiated LO .. HI (another one: hipErrorInvalidValue)
+template <int LO, int HI, typename F>
+inline hipError_t with_block(int nb, F&& f) {
+  if constexpr (LO > HI) return hipErrorInvalidValue;
+  else return nb == LO ? f(std::integral_constant<int, LO>{}) : with_block<LO + 1, HI>(nb, f);
+}
+
+// The eight kernel families, in the order newton_family tries them: three lane kernels (pnp_lane4.hip, pnp_lane2.hip, pnp_lane.hip:
+// operating points in the lanes of a wave), then the kernels of pnp_newton.hip (row-per-thread, pair, lane teams, sweep, two-sided sweep)
+enum NewtonFamily { NF_LANE4 = 0, NF_LANE2, NF_LANE, NF_GENERIC, NF_PAIR, NF_TEAM, NF_SWEEP, NF_SWEEP2, NUM_NEWTON_FAMILIES, NF_NONE = NUM_NEWTON_FAMILIES };
+constexpr int NUM_LANE_FAMILIES = NF_GENERIC;
+// the workspace a family works in: a lane workspace of its own (allocated on first use), the row-per-thread kernel's exchange buffers
+// (`work` where pnp_create made it, else dynamic LDS), `stash`, `work`, the sweep records (allocated on first use)
+enum NewtonWorkspace { NW_LANE, NW_EXCHANGE, NW_STASH, NW_WORK, NW_SWEEP };
+// What each family needs, stated once (pnp_newton.hip: newton_family_info) for newton_family, run_newton's workspace hand-over and pnp_autotune
+struct NewtonFamilyInfo {
+  int kernel;                  // the NEWTON_KERNEL choice that forces it (-1: none, only the library's own choice reaches it)
+  int tune;                    // the pnp_autotune slot that stands for it when it is the library's own choice (3 "lane+fused", 4 "workgroup")
+  NewtonWorkspace ws;
+  bool (*runs)(int nb, int nx, int lane_mode, bool work);      // can it run this shape at all (work: the handle owns a `work` buffer)
+  // lane families: operating points per group, the measured window of batches, sizes of one group's workspace, launcher
+  int points;
+  bool (*preferred)(int nb, int nx, int64_t B);
+  size_t (*rec_doubles)(int nb, int nx);
+  size_t (*state_doubles)(int nb, int nx);
+  hipError_t (*launch)(const NewtonArgs& a, hipStream_t stream);
+};
+const NewtonFamilyInfo& newton_family_info(int f);      // f: a NewtonFamily below NUM_NEWTON_FAMILIES
+// what the choice looks at.  Two batch sizes: the lane families are sized by the lanes a masked call solves (B_eff),
+// the sweep / two-sided sweep choice by the full batch B (the workgroup-per-point kernels walk all of it and skip masked points at once)
+struct NewtonShape {
+  int nb, nx;
+  int64_t B, B_eff;
+  bool mpb, reactions, convect;
+  bool sides_fit;              // the flattened reaction table holds the handle's reactions (else no lane kernel: lane mode 3)
+  bool work;                   // pnp_create gave the handle a `work` buffer
+};
+// the family that runs this shape under options o: the one place that reads Options::newton_kernel
+NewtonFamily newton_family(const NewtonShape& s, const Options& o);
+hipError_t launch_newton(const NewtonArgs& a, NewtonFamily family, int blocks, hipStream_t stream);
+
 size_t newton_exchange_doubles(int nb, int nx);
 size_t newton_team_doubles(int nb, int nx);      // row buffer of the lane-team kernel (N >= 5)
 size_t newton_sweep_doubles(int nb, int nx);     // records of one team of the sweep kernel (block Thomas, large batches)
-bool newton_sweep_preferred(int nb, int nx, int64_t B, int mode, const Options& opt);
-bool newton_sweep_two_sided(int nb, int nx, int64_t B, int mode, const Options& opt);    // ... with two teams per operating point (elimination from both ends)   // large blocks and enough lanes to fill the chip with teams (mode: 0 point ions, 1 steric, 2 + reactions)
 bool newton_exchange_in_lds(int nb, int nx, const Options& opt);
 int newton_pair_threads(int nb, int nx);   // threads of the pair kernel, 0 if the shape does not fit it
 int newton_pair_stride(int nb, int nx);    // its compile-time row stride (256 or 512)
-hipError_t launch_newton(const NewtonArgs& a, int blocks, hipStream_t stream);
 // lane kernel (pnp_lane.hip): one operating point per lane, block Thomas from both ends in registers; point / steric ions without
 // homogeneous reactions
 bool newton_lane_supported(int nb, int nx, int mode);
-bool newton_lane_preferred(int nb, int nx, int64_t B, int mode, const Options& opt);
+bool newton_lane_preferred(int nb, int nx, int64_t B);
 size_t newton_lane_rec_doubles(int nb, int nx);       // records of one group of 32 operating points
 size_t newton_lane_state_doubles(int nb, int nx);     // transposed state + previous time level of one group
 hipError_t launch_newton_lane(const NewtonArgs& a, hipStream_t stream);
 hipError_t launch_lane_transpose(const NewtonArgs& a, int64_t ngroups, bool in, hipStream_t stream);     // a.lane_lg points per group
 // lane-pair kernel (pnp_lane2.hip): four lanes per operating point (two directions x two halves of the block row), N >= 5
 bool newton_lane2_supported(int nb, int nx, int mode);
-bool newton_lane2_preferred(int nb, int nx, int64_t B, int mode, const Options& opt);
+bool newton_lane2_preferred(int nb, int nx, int64_t B);
 size_t newton_lane2_rec_doubles(int nb, int nx);      // per group of 16 operating points
 size_t newton_lane2_state_doubles(int nb, int nx);
 hipError_t launch_newton_lane2(const NewtonArgs& a, hipStream_t stream);
 // lane-quad kernel (pnp_lane4.hip): eight lanes per operating point (two directions x four column lanes of the block row), N >= 5
 bool newton_lane4_supported(int nb, int nx, int mode);
-bool newton_lane4_preferred(int nb, int nx, int64_t B, int mode, const Options& opt);
+bool newton_lane4_preferred(int nb, int nx, int64_t B);
 size_t newton_lane4_rec_doubles(int nb, int nx);      // per group of 8 operating points
 size_t newton_lane4_state_doubles(int nb, int nx);
 hipError_t launch_newton_lane4(const NewtonArgs& a, hipStream_t stream);

@@ -1113,9 +1113,7 @@ __global__ __launch_bounds__(64) void newton_lane_kernel(const NewtonArgs G) {
 // mode 2: homogeneous reactions and / or a constant convection velocity (MODE 2 instances: the steric code path with both terms)
 bool newton_lane_supported(int nb, int nx, int mode) { return nb >= 2 && nb <= 9 && nx >= 5 && mode <= 2; }
 
-bool newton_lane_preferred(int nb, int nx, int64_t B, int mode, const Options& opt) {
-  if (!newton_lane_supported(nb, nx, mode)) return false;
-  if (opt.newton_kernel != NK_AUTO) return opt.newton_kernel == NK_LANE;      // a kernel family is forced (tests, probes)
+bool newton_lane_preferred(int nb, int nx, int64_t B) {
   // Measured (tools/probe/lane_sweep.py -> profiles/r03_lane_sweep.jsonl: transient steps, steric ions, Stern wall; timesteps/s of
   // this kernel over the best of the others).  A lane advances its operating point at a fixed pace whatever the batch (N = 8,
   // nx = 512: 3.4 ms per Newton iteration), so its rate grows with the batch until every SIMD holds a wave (B = 32 768) and is
@@ -1162,42 +1160,24 @@ static hipError_t launch_lane_nb(const NewtonArgs& a0, hipStream_t stream) {
     // (separate / fused, ms per solve: 8 x 512 x 16 384 26.6 / 26.3, 32 768 40.0 / 39.6, 6 x 1024 x 16 384 35.7 / 32.9, 3 x 512 x 16 384
     // 11.1 / 10.6) -- so the fused form is the one that runs; option LANE_FUSED = 0 keeps the separate passes selectable.
     const bool fused = (a.opt && a.opt->lane_fused >= 0) ? a.opt->lane_fused != 0 : true;
-    const int mode = (a.rt || a.convect) ? 2 : (a.mpb ? 1 : 0);
+    const bool r32 = fused && a.opt && a.opt->lane_records_f32 > 0;      // (instances with f32 records: N >= 2, fused)
     const dim3 gk((unsigned)ng), bk(64);
-    if (fused) {
-      bool launched = false;
+    with_mode(newton_mode_lane(a.mpb, a.rt, a.convect), [&](auto M) {
+      constexpr int MODE = decltype(M)::value;
       if constexpr (NB >= 3) {
-        if (a.opt && a.opt->lane_records_f32 > 0) {
-          if (mode == 2) hipLaunchKernelGGL((newton_lane_kernel<NB, 2, true, true>), gk, bk, 0, stream, a);
-          else if (mode == 1) hipLaunchKernelGGL((newton_lane_kernel<NB, 1, true, true>), gk, bk, 0, stream, a);
-          else hipLaunchKernelGGL((newton_lane_kernel<NB, 0, true, true>), gk, bk, 0, stream, a);
-          launched = true;
+        if (r32) {
+          hipLaunchKernelGGL((newton_lane_kernel<NB, MODE, true, true>), gk, bk, 0, stream, a);
+          return;
         }
       }
-      if (launched) {
-      } else if (mode == 2) hipLaunchKernelGGL((newton_lane_kernel<NB, 2, true>), gk, bk, 0, stream, a);
-      else if (mode == 1) hipLaunchKernelGGL((newton_lane_kernel<NB, 1, true>), gk, bk, 0, stream, a);
-      else hipLaunchKernelGGL((newton_lane_kernel<NB, 0, true>), gk, bk, 0, stream, a);
-    } else {
-      if (mode == 2) hipLaunchKernelGGL((newton_lane_kernel<NB, 2, false>), gk, bk, 0, stream, a);
-      else if (mode == 1) hipLaunchKernelGGL((newton_lane_kernel<NB, 1, false>), gk, bk, 0, stream, a);
-      else hipLaunchKernelGGL((newton_lane_kernel<NB, 0, false>), gk, bk, 0, stream, a);
-    }
+      if (fused) hipLaunchKernelGGL((newton_lane_kernel<NB, MODE, true>), gk, bk, 0, stream, a);
+      else hipLaunchKernelGGL((newton_lane_kernel<NB, MODE, false>), gk, bk, 0, stream, a);
+    });
   });
 }
 
 hipError_t launch_newton_lane(const NewtonArgs& a, hipStream_t stream) {
-  switch (a.N + 1) {
-    case 2: return launch_lane_nb<2>(a, stream);
-    case 3: return launch_lane_nb<3>(a, stream);
-    case 4: return launch_lane_nb<4>(a, stream);
-    case 5: return launch_lane_nb<5>(a, stream);
-    case 6: return launch_lane_nb<6>(a, stream);
-    case 7: return launch_lane_nb<7>(a, stream);
-    case 8: return launch_lane_nb<8>(a, stream);
-    case 9: return launch_lane_nb<9>(a, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return with_block<2, 9>(a.N + 1, [&](auto NB) { return launch_lane_nb<decltype(NB)::value>(a, stream); });
 }
 
 }  // namespace pnp

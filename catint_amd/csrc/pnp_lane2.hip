@@ -771,36 +771,24 @@ __global__ __launch_bounds__(64) void newton_lane2_kernel(const NewtonArgs G) {
   }
 }
 
-#define LAUNCH_BDF(MODE_)                                                                                              \
-  do {                                                                                                                 \
-    if (a.bdf2) hipLaunchKernelGGL((newton_lane2_kernel<NB, MODE_, true>), dim3((unsigned)ng), dim3(64), 0, stream, a);  \
-    else hipLaunchKernelGGL((newton_lane2_kernel<NB, MODE_, false>), dim3((unsigned)ng), dim3(64), 0, stream, a);       \
-  } while (0)
-
 template <int NB>
 static hipError_t launch_lane2_nb(const NewtonArgs& a0, hipStream_t stream) {
   return launch_lane_chunks<OG>(a0, stream, [&](const NewtonArgs& a, int64_t ng) {
-    if (a.rt || a.convect) LAUNCH_BDF(2);
-    else if (a.mpb) LAUNCH_BDF(1);
-    else LAUNCH_BDF(0);
+    with_mode(newton_mode_lane(a.mpb, a.rt, a.convect), [&](auto M) {
+      with_flag(a.bdf2 != 0, [&](auto BDF) {
+        hipLaunchKernelGGL((newton_lane2_kernel<NB, decltype(M)::value, decltype(BDF)::value>), dim3((unsigned)ng), dim3(64), 0, stream, a);
+      });
+    });
   });
 }
 
 hipError_t launch_newton_lane2(const NewtonArgs& a, hipStream_t stream) {
-  switch (a.N + 1) {
-    case 6: return launch_lane2_nb<6>(a, stream);
-    case 7: return launch_lane2_nb<7>(a, stream);
-    case 8: return launch_lane2_nb<8>(a, stream);
-    case 9: return launch_lane2_nb<9>(a, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return with_block<6, 9>(a.N + 1, [&](auto NB) { return launch_lane2_nb<decltype(NB)::value>(a, stream); });
 }
 
 bool newton_lane2_supported(int nb, int nx, int mode) { return nb >= 6 && nb <= 9 && nx >= 5 && mode <= 2; }
 
-bool newton_lane2_preferred(int nb, int nx, int64_t B, int mode, const Options& opt) {
-  if (!newton_lane2_supported(nb, nx, mode)) return false;
-  if (opt.newton_kernel != NK_AUTO) return opt.newton_kernel == NK_LANE2;
+bool newton_lane2_preferred(int nb, int nx, int64_t B) {
   // Measured on one device in one call (tools/probe/lane2_probe.sh; N = 8, nx = 512, timesteps/s, lane pair / lane / lane teams):
   // B = 1024 1.16e5 / 1.00e5 / 1.40e5, 2048 2.40e5 / 1.96e5 / 1.43e5, 4096 4.51e5 / 3.85e5 / 1.44e5, 8192 7.31e5 / 7.07e5 / 1.51e5,
   // 16 384 0.99e6 / 1.03e6.  Twice the waves for the same batch, but the distribution overhead (selects, DPP moves, duplicated

@@ -957,38 +957,26 @@ __global__ __launch_bounds__(64) void newton_lane4_kernel(const NewtonArgs G) {
 #endif
 }
 
-#define LAUNCH_BDF(MODE_)                                                                                              \
-  do {                                                                                                                 \
-    if (a.bdf2) hipLaunchKernelGGL((newton_lane4_kernel<NB, MODE_, true>), dim3((unsigned)ng), dim3(64), 0, stream, a);  \
-    else hipLaunchKernelGGL((newton_lane4_kernel<NB, MODE_, false>), dim3((unsigned)ng), dim3(64), 0, stream, a);       \
-  } while (0)
-
 template <int NB>
 static hipError_t launch_lane4_nb(const NewtonArgs& a0, hipStream_t stream) {
   NewtonArgs as = a0;
   as.lane_stagger = (as.opt && as.opt->lane_stagger >= 0) ? as.opt->lane_stagger : 0;
   return launch_lane_chunks<QG>(as, stream, [&](const NewtonArgs& a, int64_t ng) {
-    if (a.rt || a.convect) LAUNCH_BDF(2);
-    else if (a.mpb) LAUNCH_BDF(1);
-    else LAUNCH_BDF(0);
+    with_mode(newton_mode_lane(a.mpb, a.rt, a.convect), [&](auto M) {
+      with_flag(a.bdf2 != 0, [&](auto BDF) {
+        hipLaunchKernelGGL((newton_lane4_kernel<NB, decltype(M)::value, decltype(BDF)::value>), dim3((unsigned)ng), dim3(64), 0, stream, a);
+      });
+    });
   });
 }
 
 hipError_t launch_newton_lane4(const NewtonArgs& a, hipStream_t stream) {
-  switch (a.N + 1) {
-    case 6: return launch_lane4_nb<6>(a, stream);
-    case 7: return launch_lane4_nb<7>(a, stream);
-    case 8: return launch_lane4_nb<8>(a, stream);
-    case 9: return launch_lane4_nb<9>(a, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return with_block<6, 9>(a.N + 1, [&](auto NB) { return launch_lane4_nb<decltype(NB)::value>(a, stream); });
 }
 
 bool newton_lane4_supported(int nb, int nx, int mode) { return nb >= 6 && nb <= 9 && nx >= 5 && mode <= 2; }
 
-bool newton_lane4_preferred(int nb, int nx, int64_t B, int mode, const Options& opt) {
-  if (!newton_lane4_supported(nb, nx, mode)) return false;
-  if (opt.newton_kernel != NK_AUTO) return opt.newton_kernel == NK_LANE4;
+bool newton_lane4_preferred(int nb, int nx, int64_t B) {
   // Measured on one device in one process (tools/probe/lane4_probe.py -> profiles/r04_lane4_probe.jsonl; N = 8 steric, nx = 512,
   // timesteps/s, lane quad / lane pair / lane / lane teams): B = 1024 1.66e5 / 1.19e5 / 1.00e5 / 1.38e5, 2048 3.24e5 / 2.32e5 / 1.97e5 /
   // 1.41e5, 4096 5.61e5 / 4.46e5 / 3.86e5 / 1.45e5, 8192 9.09e5 / 7.43e5 / 7.18e5, 12 288 7.78e5 / 9.96e5 / 9.55e5, 16 384 0.87e6 /

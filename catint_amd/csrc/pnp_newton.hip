@@ -2196,7 +2196,7 @@ __global__ __launch_bounds__(64, 2) void newton_sweep2_kernel(const NewtonArgs G
 // ------------------------------------------------------------------------------------------------
 static constexpr size_t kLdsBudget = 160 * 1024 - 512;
 
-int newton_threads(int nb, int nx) {
+static int newton_threads(int nb, int nx) {
   const int tmax = nb <= 4 ? 512 : 256;
   const int t = (nx + 63) / 64 * 64;
   return t < tmax ? t : tmax;
@@ -2237,16 +2237,11 @@ template <int NB, int TS>
 static hipError_t launch_pair(const NewtonArgs& a, int blocks, int tp, hipStream_t stream) {
   const size_t lds = (size_t)(2 * NB * NB + NB) * TS * sizeof(double);
   // variants: 0 point ions, 1 steric (MPB) drift, 2 steric drift + homogeneous reactions (point ions: zero volumes)
-  if (a.rt) {
-    (void)hipFuncSetAttribute((const void*)newton_pair_kernel<NB, TS, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((newton_pair_kernel<NB, TS, 2>), dim3(blocks), dim3(tp), lds, stream, a);
-  } else if (a.mpb) {
-    (void)hipFuncSetAttribute((const void*)newton_pair_kernel<NB, TS, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((newton_pair_kernel<NB, TS, 1>), dim3(blocks), dim3(tp), lds, stream, a);
-  } else {
-    (void)hipFuncSetAttribute((const void*)newton_pair_kernel<NB, TS, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((newton_pair_kernel<NB, TS, 0>), dim3(blocks), dim3(tp), lds, stream, a);
-  }
+  with_mode(newton_mode_workgroup(a.mpb, a.rt), [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    (void)hipFuncSetAttribute((const void*)newton_pair_kernel<NB, TS, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((newton_pair_kernel<NB, TS, MODE>), dim3(blocks), dim3(tp), lds, stream, a);
+  });
   return hipGetLastError();
 }
 
@@ -2273,9 +2268,9 @@ static hipError_t launch_team(const NewtonArgs& a, int blocks, hipStream_t strea
     (void)hipFuncSetAttribute((const void*)newton_team_kernel<NB, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute((const void*)newton_team_kernel<NB, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  if (a.rt) hipLaunchKernelGGL((newton_team_kernel<NB, 2>), dim3(blocks), dim3(T), lds, stream, a);
-  else if (a.mpb) hipLaunchKernelGGL((newton_team_kernel<NB, 1>), dim3(blocks), dim3(T), lds, stream, a);
-  else hipLaunchKernelGGL((newton_team_kernel<NB, 0>), dim3(blocks), dim3(T), lds, stream, a);
+  with_mode(newton_mode_workgroup(a.mpb, a.rt), [&](auto M) {
+    hipLaunchKernelGGL((newton_team_kernel<NB, decltype(M)::value>), dim3(blocks), dim3(T), lds, stream, a);
+  });
   return hipGetLastError();
 }
 
@@ -2285,9 +2280,9 @@ static hipError_t launch_sweep(const NewtonArgs& a, hipStream_t stream) {
   constexpr int TPW = SweepLayout<NB>::TPW;
   int64_t blocks = (a.B + TPW - 1) / TPW;
   if (blocks > a.sweep_blocks) blocks = a.sweep_blocks;
-  if (a.rt) hipLaunchKernelGGL((newton_sweep_kernel<NB, 2>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-  else if (a.mpb) hipLaunchKernelGGL((newton_sweep_kernel<NB, 1>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-  else hipLaunchKernelGGL((newton_sweep_kernel<NB, 0>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+  with_mode(newton_mode_workgroup(a.mpb, a.rt), [&](auto M) {
+    hipLaunchKernelGGL((newton_sweep_kernel<NB, decltype(M)::value>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+  });
   return hipGetLastError();
 }
 
@@ -2297,16 +2292,30 @@ static hipError_t launch_sweep2(const NewtonArgs& a, hipStream_t stream) {
   constexpr int PPW = SweepLayout<NB>::TPW / 2;
   int64_t blocks = (a.B + PPW - 1) / PPW;
   if (blocks > a.sweep_blocks) blocks = a.sweep_blocks;
-  if (a.rt) hipLaunchKernelGGL((newton_sweep2_kernel<NB, 2>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-  else if (a.mpb) hipLaunchKernelGGL((newton_sweep2_kernel<NB, 1>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
-  else hipLaunchKernelGGL((newton_sweep2_kernel<NB, 0>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+  with_mode(newton_mode_workgroup(a.mpb, a.rt), [&](auto M) {
+    hipLaunchKernelGGL((newton_sweep2_kernel<NB, decltype(M)::value>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+  });
   return hipGetLastError();
 }
 
-// Two teams per operating point instead of one: when the one-sided sweep would leave the SIMDs with fewer than ~3 waves.
-bool newton_sweep_two_sided(int nb, int nx, int64_t B, int mode, const Options& opt) {
-  if (nb < 6 || nx < 8) return false;
-  if (opt.newton_kernel != NK_AUTO && opt.newton_kernel != NK_WORKGROUP) return opt.newton_kernel == NK_BOTH;      // "both ends" (tests, probes)
+// row-per-thread kernel: small shapes the other two do not take, and (up to N = 6) the forced cross-check of the tests;
+// for N >= 7 it is not built (it only spilled there, and its instances dominated the compile time)
+template <int NB, int TMAX>
+static hipError_t launch_generic(const NewtonArgs& a, int blocks, hipStream_t stream) {
+  const int T = newton_threads(NB, a.nx);
+  const size_t lds = a.work ? 0 : newton_exchange_doubles(NB, a.nx) * sizeof(double);
+  with_mode(newton_mode_workgroup(a.mpb, a.rt), [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)newton_kernel<NB, TMAX, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((newton_kernel<NB, TMAX, MODE>), dim3(blocks), dim3(T), lds, stream, a);
+  });
+  return hipGetLastError();
+}
+
+// Two teams per operating point (elimination from both ends) instead of one: when the one-sided sweep would leave the SIMDs with
+// fewer than ~3 waves (mode: 0 point ions, 1 steric, 2 + reactions).
+static bool newton_sweep_two_sided(int nb, int64_t B, int mode) {
   // with homogeneous reactions (the 4096-lane CO2R sweep: stationary solves along a continuation, 3...30 iterations per lane) the
   // lane-team kernel stays ahead: 0.48 s against 0.52 s (one-sided sweep 0.83 s)
   if (mode >= 2) return false;
@@ -2320,10 +2329,7 @@ bool newton_sweep_two_sided(int nb, int nx, int64_t B, int mode, const Options& 
 }
 
 // Large blocks and a batch that fills the chip with teams on its own (measured): the sweep kernel.
-bool newton_sweep_preferred(int nb, int nx, int64_t B, int mode, const Options& opt) {
-  if (opt.newton_kernel != NK_AUTO && opt.newton_kernel != NK_WORKGROUP)
-    return (opt.newton_kernel == NK_SWEEP && nb >= 3) || (opt.newton_kernel == NK_BOTH && nb >= 6 && nx >= 8);
-  if (newton_sweep_two_sided(nb, nx, B, mode, opt)) return true;
+static bool newton_sweep_preferred(int nb, int64_t B) {
   // at least one wave of teams per SIMD (1024 SIMDs): below that the chip is not full and, with uniform control flow, a wave
   // waits for its slowest lane -- the CO2R example (7 species, 4096 lanes, iteration counts 3...30) took 0.84 s instead of 0.51 s
   const int64_t waves = (B + 64 / nb - 1) / (64 / nb);
@@ -2333,72 +2339,86 @@ bool newton_sweep_preferred(int nb, int nx, int64_t B, int mode, const Options& 
   return nb >= 6 && waves >= 1024;
 }
 
-template <int NB, int TMAX>
-static hipError_t launch_newton_nb(const NewtonArgs& a, int blocks, hipStream_t stream) {
-  static const Options kDefaults;
-  const Options& opt = a.opt ? *a.opt : kDefaults;
-  const bool generic = opt.newton_kernel == NK_GENERIC;     // forces the row-per-thread kernel (tests)
-  const int tp = generic ? 0 : newton_pair_threads(NB, a.nx);
-  if constexpr (NB >= 3) {
-    // (run_newton hands over the sweep workspace exactly when newton_sweep_preferred holds for this batch)
-    if (a.sweep && a.sweep_blocks > 0) {
-      if constexpr (NB >= 6) {
-        if (newton_sweep_two_sided(NB, a.nx, a.B, a.rt ? 2 : (a.mpb ? 1 : 0), opt)) return launch_sweep2<NB>(a, stream);
-      }
-      return launch_sweep<NB>(a, stream);
-    }
+// What each family needs: the choice that forces it, its autotune slot, its workspace, the shapes it can run; for the lane families
+// also the group size, the measured window and the sizing / launch functions.  (The lane teams and the sweeps need a block of at least
+// 3 x 3, the two-sided sweep 6 x 6 and eight rows; the row-per-thread kernel is built up to N = 6, the pair kernel for what
+// newton_pair_threads takes.)
+const NewtonFamilyInfo& newton_family_info(int f) {
+  static const NewtonFamilyInfo kFamilies[NUM_NEWTON_FAMILIES] = {
+      {NK_LANE4, 0, NW_LANE, [](int nb, int nx, int lm, bool) { return newton_lane4_supported(nb, nx, lm); }, 8, newton_lane4_preferred,
+       newton_lane4_rec_doubles, newton_lane4_state_doubles, launch_newton_lane4},
+      {NK_LANE2, 1, NW_LANE, [](int nb, int nx, int lm, bool) { return newton_lane2_supported(nb, nx, lm); }, 16, newton_lane2_preferred,
+       newton_lane2_rec_doubles, newton_lane2_state_doubles, launch_newton_lane2},
+      // (the lane kernel: "lane+fused", fused for timesteps at every batch, pnp_lane.hip: launch_lane_nb)
+      {NK_LANE, 3, NW_LANE, [](int nb, int nx, int lm, bool) { return newton_lane_supported(nb, nx, lm); }, 32, newton_lane_preferred,
+       newton_lane_rec_doubles, newton_lane_state_doubles, launch_newton_lane},
+      {NK_GENERIC, 4, NW_EXCHANGE, [](int nb, int, int, bool) { return nb <= 7; }},
+      {-1, 4, NW_STASH, [](int nb, int nx, int, bool) { return newton_pair_threads(nb, nx) > 0; }},
+      {NK_TEAM, 4, NW_WORK, [](int nb, int, int, bool work) { return nb >= 3 && work; }},
+      {NK_SWEEP, 4, NW_SWEEP, [](int nb, int, int, bool) { return nb >= 3; }},
+      {NK_BOTH, 4, NW_SWEEP, [](int nb, int nx, int, bool) { return nb >= 6 && nx >= 8; }}};
+  return kFamilies[f];
+}
+
+// The kernel family that runs a batch.  A forced choice (tests, probes, pnp_autotune) takes its family where that can run the shape;
+// every case it cannot falls through to what the library's own choice among the remaining families would be.
+NewtonFamily newton_family(const NewtonShape& s, const Options& o) {
+  const int nb = s.nb, nx = s.nx, k = o.newton_kernel;
+  const int lane_mode = s.sides_fit ? newton_mode_lane(s.mpb, s.reactions, s.convect) : 3;
+  auto runs = [&](NewtonFamily f) { return newton_family_info(f).runs(nb, nx, lane_mode, s.work); };
+  // the lane kernels, sized by the lanes the call solves.  The order matters: newton_lane2_preferred leaves the lane-quad window to
+  // newton_lane4_preferred, and newton_lane_preferred the windows of both to them.
+  for (int f = 0; f < NUM_LANE_FAMILIES; ++f) {
+    const NewtonFamilyInfo& F = newton_family_info(f);
+    if (runs((NewtonFamily)f) && (k == NK_AUTO ? F.preferred(nb, nx, s.B_eff) : k == F.kernel)) return (NewtonFamily)f;
   }
-  if constexpr (NB >= 3) {     // lane teams: every large block, and the N = 2..4 grids too long for the pair kernel
-    if (a.work && !generic && (NB >= 6 || tp == 0 || opt.newton_kernel == NK_TEAM)) return launch_team<NB>(a, blocks, stream);
+  // the workgroup-per-point kernels, sized by the full batch; NK_WORKGROUP is the library's own choice among them
+  const bool own = k == NK_AUTO || k == NK_WORKGROUP;
+  if (runs(NF_SWEEP2) && (own ? newton_sweep_two_sided(nb, s.B, newton_mode_workgroup(s.mpb, s.reactions)) : k == NK_BOTH)) return NF_SWEEP2;
+  if (runs(NF_SWEEP) && (own ? newton_sweep_preferred(nb, s.B) : k == NK_SWEEP)) return NF_SWEEP;
+  // lane teams: every large block, and the N = 2..4 grids too long for the pair kernel; `generic` forces the row-per-thread kernel (tests)
+  const bool pair = runs(NF_PAIR), generic = k == NK_GENERIC;
+  if (runs(NF_TEAM) && !generic && (nb >= 6 || !pair || k == NK_TEAM)) return NF_TEAM;
+  if (pair && !generic) return NF_PAIR;
+  if (runs(NF_GENERIC)) return NF_GENERIC;
+  // N >= 7 without the row-per-thread build: the lane teams (pnp_create gives every block of 5 x 5 and more its `work` buffer)
+  return runs(NF_TEAM) ? NF_TEAM : NF_NONE;
+}
+
+template <int NB>
+static hipError_t launch_newton_nb(const NewtonArgs& a, NewtonFamily family, int blocks, hipStream_t stream) {
+  if constexpr (NB >= 6) {
+    if (family == NF_SWEEP2) return launch_sweep2<NB>(a, stream);
+  }
+  if constexpr (NB >= 3) {
+    if (family == NF_SWEEP) return launch_sweep<NB>(a, stream);
+    if (family == NF_TEAM) return launch_team<NB>(a, blocks, stream);
   }
   if constexpr (NB <= 5) {
-    if (tp > 0) {
+    if (family == NF_PAIR) {
+      const int tp = newton_pair_threads(NB, a.nx);
       if (tp <= 64) return launch_pair<NB, 64>(a, blocks, tp, stream);
       if (tp <= 128) return launch_pair<NB, 128>(a, blocks, tp, stream);
       if (tp <= 256) return launch_pair<NB, 256>(a, blocks, tp, stream);
       if constexpr (NB <= 4) return launch_pair<NB, 512>(a, blocks, tp, stream);
     }
   }
-  // row-per-thread kernel: small shapes the other two do not take, and (up to N = 6) the forced cross-check of the tests;
-  // for N >= 7 it is not built (it only spilled there, and its instances dominated the compile time)
-  if constexpr (NB >= 8) {
-    if (a.work) return launch_team<NB>(a, blocks, stream);
-    return hipErrorInvalidValue;
-  } else {
-    const int T = newton_threads(NB, a.nx);
-    const size_t lds = a.work ? 0 : newton_exchange_doubles(NB, a.nx) * sizeof(double);
-    if (a.rt) {
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)newton_kernel<NB, TMAX, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((newton_kernel<NB, TMAX, 2>), dim3(blocks), dim3(T), lds, stream, a);
-    } else if (a.mpb) {
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)newton_kernel<NB, TMAX, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((newton_kernel<NB, TMAX, 1>), dim3(blocks), dim3(T), lds, stream, a);
-    } else {
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)newton_kernel<NB, TMAX, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((newton_kernel<NB, TMAX, 0>), dim3(blocks), dim3(T), lds, stream, a);
+  if constexpr (NB <= 7) {
+    if (family == NF_GENERIC) {
+      // (the row-per-thread kernel of N = 5, 6 also exists in a 512-register build -- launch bound 256, accumulator registers as
+      // spill space -- selected by CATINT_NEWTON_REGS=512: tests/test_gpu_newton.py checks that it walks the same bits)
+      if constexpr (NB >= 6) {
+        if (a.opt && a.opt->newton_regs == 512) return launch_generic<NB, 256>(a, blocks, stream);
+      }
+      return launch_generic<NB, 512>(a, blocks, stream);
     }
-    return hipGetLastError();
   }
+  return hipErrorInvalidValue;      // a family that is not built for this block size (newton_family returns none such)
 }
 
-hipError_t launch_newton(const NewtonArgs& a, int blocks, hipStream_t stream) {
-  const bool regs512 = a.opt && a.opt->newton_regs == 512;
-  switch (a.N + 1) {
-    case 2: return launch_newton_nb<2, 512>(a, blocks, stream);
-    case 3: return launch_newton_nb<3, 512>(a, blocks, stream);
-    case 4: return launch_newton_nb<4, 512>(a, blocks, stream);
-    case 5: return launch_newton_nb<5, 512>(a, blocks, stream);
-    // (the row-per-thread kernel of these two block sizes also exists in a 512-register build -- launch bound 256, accumulator
-    // registers as spill space -- selected by CATINT_NEWTON_REGS=512: tests/test_gpu_newton.py checks that it walks the same bits)
-    case 6: return regs512 ? launch_newton_nb<6, 256>(a, blocks, stream) : launch_newton_nb<6, 512>(a, blocks, stream);
-    case 7: return regs512 ? launch_newton_nb<7, 256>(a, blocks, stream) : launch_newton_nb<7, 512>(a, blocks, stream);
-    case 8: return launch_newton_nb<8, 512>(a, blocks, stream);
-    case 9: return launch_newton_nb<9, 512>(a, blocks, stream);
-    default: return hipErrorInvalidValue;
-  }
+// launches the family newton_family chose (run_newton handed over its workspace)
+hipError_t launch_newton(const NewtonArgs& a, NewtonFamily family, int blocks, hipStream_t stream) {
+  return with_block<2, 9>(a.N + 1, [&](auto NB) { return launch_newton_nb<decltype(NB)::value>(a, family, blocks, stream); });
 }
 
 }  // namespace pnp
