@@ -33,7 +33,7 @@ SYMBOLS = [
     'pnp_set_batch', 'pnp_set_flux', 'pnp_set_pb', 'pnp_step', 'pnp_integrate', 'pnp_mol_rhs', 'pnp_integrate_dopri5', 'pnp_integrate_dop853', 'pnp_integrate_rkc', 'pnp_get_state',
     'pnp_get_surface', 'pnp_get_status', 'pnp_synchronize', 'pnp_timer_start', 'pnp_timer_stop',
     'pnp_device_bytes', 'pnp_row_pitch', 'pnp_step_row_chunks', 'pnp_set_newton', 'pnp_solve_stationary', 'pnp_get_newton_iterations',
-    'pnp_set_potential', 'pnp_set_convection', 'pnp_set_option', 'pnp_get_lane_order', 'pnp_autotune', 'pnp_autotune_name', 'pnp_autotune_default', 'pnp_tune_placement', 'pnp_set_lanes', 'pnp_set_lane_mask', 'pnp_set_wall_kinetics', 'pnp_set_wall_rate_law', 'pnp_set_grid', 'pnp_solve_surface', 'pnp_scf_cycle',
+    'pnp_set_potential', 'pnp_set_convection', 'pnp_set_option', 'pnp_get_lane_order', 'pnp_autotune', 'pnp_autotune_name', 'pnp_autotune_default', 'pnp_tune_placement', 'pnp_set_lanes', 'pnp_set_lane_mask', 'pnp_set_wall_kinetics', 'pnp_set_wall_rate_law', 'pnp_set_grid', 'pnp_solve_surface', 'pnp_scf_cycle', 'pnp_get_device_view',
 ]
 
 
@@ -172,6 +172,8 @@ def load_library():
                  'pnp_integrate', 'pnp_mol_rhs', 'pnp_get_state', 'pnp_get_surface', 'pnp_get_status', 'pnp_synchronize',
                  'pnp_timer_start', 'pnp_timer_stop'):
         getattr(lib, name).restype = C.c_int
+    lib.pnp_get_device_view.argtypes = [vp, C.c_void_p]
+    lib.pnp_get_device_view.restype = C.c_int
     lib.pnp_device_bytes.argtypes = [vp]
     lib.pnp_device_bytes.restype = C.c_int64
     lib.pnp_row_pitch.argtypes = [vp]
@@ -218,12 +220,19 @@ class PnpSolver(object):
         self.dt_ode = float(dt)      # interval length of integrate_dopri5 (cfg.dt)
         self.method = method
         self._check(self._lib.pnp_set_species(self._h, _dptr(_f64(D, (self.N,))), _dptr(_f64(charges, (self.N,)))))
+        # what get_electrolyte hands to the observables library: the problem as this solver was given it
+        self._obs = {'D': np.array(D, float), 'charges': np.array(charges, float), 'beta': float(beta), 'x': np.arange(self.nx) * float(dx),
+                     'mpb_radius': None, 'velocity': 0.0, 'device': int(device)}
+        self._observer = None
 
     def _check(self, rc):
         if rc != 0:
             raise PnpError(rc, self._lib.pnp_last_error(self._h).decode())
 
     def close(self):
+        if getattr(self, '_observer', None) is not None:
+            self._observer.close()
+            self._observer = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -287,6 +296,7 @@ class PnpSolver(object):
                             float(stern_capacitance), float(phi_pzc), float(tol), float(dphi_max), int(time_order), int(bool(predictor)))
         r = None if mpb_radius is None else _f64(mpb_radius, (self.N,))
         self._check(self._lib.pnp_set_newton(self._h, C.byref(p), _dptr(r)))
+        self._obs['mpb_radius'] = None if r is None else r.copy()
 
     def set_option(self, key, value):
         """Debug / tuning switch of this handle (pnp_set_option): e.g. set_option('NEWTON_KERNEL', 'lane2').  The CATINT_* environment
@@ -326,10 +336,12 @@ class PnpSolver(object):
     def set_convection(self, velocity):
         """Constant convection velocity (m/s) of the physical mode: tp.system['flow rate'] (comsol_model.py:901-903)."""
         self._check(self._lib.pnp_set_convection(self._h, float(velocity)))
+        self._obs['velocity'] = float(velocity)
 
     def set_grid(self, x):
         """Non-uniform grid x[nx] of the physical mode (electrode at x[0]); dx of the constructor stays the scaling length."""
         self._check(self._lib.pnp_set_grid(self._h, _dptr(_f64(x, (self.nx,)))))
+        self._obs['x'] = np.array(x, float)
 
     def set_wall_kinetics(self, species, nu, k, alpha=None, saturation=None):
         """Surface reactions coupled implicitly: species [n] (index, -1 = zeroth order), nu [n][N] stoichiometry of the flux
@@ -473,8 +485,14 @@ class PnpSolver(object):
         return cout, idid, stats, t_end
 
     # -- read-back -------------------------------------------------------------------------
-    def get_state(self, potential=True):
+    def get_state(self, potential=True, derived=True):
+        """(c, v, grad_v, lapl_v); potential=False: c alone; derived=False: (c, v) -- in the physical mode two plain copies, without
+        the host loops that derive the gradient and the charge row."""
         c = np.zeros((self.B, self.N, self.nx))
+        if potential and not derived:
+            v = np.zeros((self.B, self.nx))
+            self._check(self._lib.pnp_get_state(self._h, _dptr(c), _dptr(v), None, None))
+            return c, v
         if potential:
             v = np.zeros((self.B, self.nx)); g = np.zeros((self.B, self.nx)); l = np.zeros((self.B, self.nx))
             self._check(self._lib.pnp_get_state(self._h, _dptr(c), _dptr(v), _dptr(g), _dptr(l)))
@@ -486,6 +504,30 @@ class PnpSolver(object):
         cs = np.zeros((self.B, self.N)); vs = np.zeros(self.B); es = np.zeros(self.B)
         self._check(self._lib.pnp_get_surface(self._h, _dptr(cs), _dptr(vs), _dptr(es)))
         return cs, vs, es
+
+    def device_view(self):
+        """Where the state lives on the device (pnp_get_device_view): a catint_amd._observe.PnpDeviceView, valid until the next
+        set_batch / close.  No copy, no synchronisation."""
+        from ._observe import PnpDeviceView
+        view = PnpDeviceView()
+        self._check(self._lib.pnp_get_device_view(self._h, C.byref(view)))
+        return view
+
+    def get_electrolyte(self, fields=None, scalars=True, species_H=-1, species_OH=-1, max_waves=0):
+        """Electrolyte observables of the physical mode derived on the device (include/catint_observe.h): a dict of the rows named in
+        `fields` (catint_amd._observe.FIELDS; None: all of them; without species_H and species_OH no 'pH') and, with scalars, 'scalars'
+        [B][NSCALARS] (columns: catint_amd._observe.SCALARS).  D, charges, ion radii, grid and velocity are the ones this solver was
+        given.  Only what is asked for crosses PCIe: a scalars-only call moves 80 bytes per operating point."""
+        from . import _observe
+        if self._observer is None:
+            self._observer = _observe.Observer(self._obs['device'])
+        names = list(_observe.FIELDS) if fields is None else list(fields)
+        if species_H < 0 and species_OH < 0 and fields is None:
+            names.remove('pH')
+        o = self._obs
+        return self._observer.electrolyte(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], mpb_radius=o['mpb_radius'],
+                                          velocity=o['velocity'], species_H=species_H, species_OH=species_OH, fields=names,
+                                          scalars=scalars, max_waves=max_waves)
 
     def get_status(self):
         st = np.zeros(self.B, np.int32)

@@ -12,6 +12,14 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wall', '-Wno-unused-function']
 
 
+# second library (include/catint_observe.h): observables derived from a device-resident state.  Its kernels stay out of SOURCES:
+# the solver library holds the solver's kernels and nothing else (tests/test_kernel_census.py)
+OBSERVE_DIR = os.path.join(CSRC, 'observe')
+OBSERVE_LIB = os.path.join(LIB_DIR, 'libcatint_observe.so')
+OBSERVE_SOURCES = ['catobs.hip']
+OBSERVE_HEADERS = [os.path.join(CSRC, 'pnp_internal.h'), os.path.join(CSRC, 'pnp_wave.h'), os.path.join(CSRC, 'pnp_math.h'),
+                   os.path.join(_HERE, '..', 'include', 'catint_pnp.h'), os.path.join(_HERE, '..', 'include', 'catint_observe.h')]
+
 PARTIAL = os.path.join(LIB_DIR, '.partial')      # left by tools/devbuild.sh: the library holds only one block size
 
 
@@ -60,3 +68,26 @@ def build_library(force=False, verbose=False):
     if os.path.exists(PARTIAL):
         os.remove(PARTIAL)
     return LIB
+
+
+def observe_needs_build():
+    if not os.path.exists(OBSERVE_LIB):
+        return True
+    t = os.path.getmtime(OBSERVE_LIB)
+    deps = [os.path.join(OBSERVE_DIR, s) for s in OBSERVE_SOURCES] + OBSERVE_HEADERS
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_observe_library(force=False, verbose=False):
+    """hipcc --offload-arch=gfx950 of catint_amd/csrc/observe into catint_amd/lib/libcatint_observe.so (one command: the library is one
+    translation unit)"""
+    if not force and not observe_needs_build():
+        return OBSERVE_LIB
+    os.makedirs(LIB_DIR, exist_ok=True)
+    cmd = [HIPCC] + FLAGS + [os.path.join(OBSERVE_DIR, s) for s in OBSERVE_SOURCES] + ['-o', OBSERVE_LIB]
+    if verbose:
+        print(' '.join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError('hipcc failed on the observe library:\n%s%s' % (r.stdout, r.stderr))
+    return OBSERVE_LIB

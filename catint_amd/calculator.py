@@ -50,7 +50,7 @@ def make_itout(nt, ntout):
 
 class Calculator(object):
     def __init__(self, transport=None, dt=None, tmax=None, ntout=1, calc=None, scale_pb_grid=None, tau_jacobi=1e-7,
-                 tau_scf=5e-5, mix_scf=0.5, mode=None, desc_method='external', device=0):
+                 tau_scf=5e-5, mix_scf=0.5, mode=None, desc_method='external', device=0, derive_on_device=False):
         if transport is None:
             raise CalculatorError('No transport object provided for calculator.')
         self.tp = transport
@@ -58,6 +58,9 @@ class Calculator(object):
         self.tau_scf = tau_scf
         self.mix_scf = mix_scf
         self.device = device
+        # physical mode: run() fills tp.alldata from quantities derived on the device (PnpSolver.get_electrolyte) instead of on the host
+        self.derive_on_device = bool(derive_on_device)
+        self.observables = None           # [B][NSCALARS] of the last device-derived run(), ready for parallel.gather_observables
         if calc is None:
             calc = self.tp.calc
         if calc is None:
@@ -568,11 +571,23 @@ class Calculator(object):
                 _t0 = _time.perf_counter()
                 status = self.solve_physical(s, c0, phiM, flux)
                 self.solve_seconds = _time.perf_counter() - _t0        # transport solves only (incl. their host<->device traffic)
-                cfin, v, g, l = s.get_state()
+                derived = None
+                if self.derive_on_device:
+                    cfin, v = s.get_state(derived=False)
+                    names = list(tp.species.keys())
+                    derived = s.get_electrolyte(species_H=names.index('H+') if 'H+' in names else -1,
+                                                species_OH=names.index('OH-') if 'OH-' in names else -1)
+                else:
+                    cfin, v, g, l = s.get_state()
                 self.newton_iterations = s.newton_iterations()
                 if getattr(self, 'surface_kinetics', None):
                     self.kinetic_flux = self.surface_kinetic_fluxes(cfin[:, :, 0], phiM, vsurf=v[:, 0])
             cout = cfin.reshape(1, B, tp.nspecies * tp.nx)
+            if derived is not None:
+                self.status = status
+                self.observables = derived['scalars']
+                self._alldata_fill(0, self._alldata_from_device(cfin, v, derived, flux, getattr(self, 'kinetic_flux', None)), status)
+                return cout
         else:
             cout, status, (v, g, l) = self.integrate_pnp_batch(c0, pb, vz, flux)
         self.status = status
@@ -658,6 +673,15 @@ class Calculator(object):
                                                          * h[None, :], axis=1)], axis=1)
         out.update(gamma=gamma, jwall=jwall, pH=pH, kappa=kappa, i_el=i_el, dphi_iR=dphi_iR, dphi_diff=dphi_diff)
         return out
+
+    def _alldata_from_device(self, cfin, v, derived, flux, kinetic_flux):
+        """The arrays of _alldata_arrays out of PnpSolver.get_electrolyte: same names, same shapes, nothing computed on the host but the
+        wall fluxes.  (The device's electrolyte current carries the convection term of the flux the solver conserves; _alldata_arrays
+        leaves it out -- at velocity 0 the two are the same.)"""
+        jwall = np.asarray(flux, float) + (np.asarray(kinetic_flux, float) if kinetic_flux is not None else 0.0)
+        return {'cfin': cfin, 'v': v, 'efield': derived['efield'], 'rho': derived['charge_density'], 'gamma': derived['gamma'],
+                'jwall': jwall, 'pH': derived.get('pH'), 'kappa': derived['conductivity'], 'i_el': derived['current_density'],
+                'dphi_iR': derived['dphi_iR'], 'dphi_diff': derived['dphi_diff']}
 
     def _alldata_fill(self, first, A, status):
         """tp.alldata[first ...] from the arrays of _alldata_arrays (the entries are rows of those arrays)."""

@@ -2272,6 +2272,23 @@ int pnp_get_status(pnp_handle* h, int32_t* status) {
   return PNP_OK;
 }
 
+int pnp_get_device_view(pnp_handle* h, pnp_device_view* out) {
+  if (!h || !out) return fail(h, PNP_EINVAL, "pnp_get_device_view: null argument");
+  if (!h->have_batch) return fail(h, PNP_ESTATE, "pnp_get_device_view: call pnp_set_batch first");
+  out->struct_size = (int32_t)sizeof(pnp_device_view);
+  out->method = h->cfg.method;
+  out->nspecies = h->a.N;
+  out->nx = h->a.nx;
+  out->row_pitch = h->a.ldx;
+  out->reserved = 0;
+  out->batch = h->B;
+  out->c_dev = h->c;
+  out->phi_dev = h->newton ? h->v : nullptr;
+  out->status_dev = h->status;
+  out->stream = (void*)h->stream;
+  return PNP_OK;
+}
+
 int pnp_synchronize(pnp_handle* h) {
   if (!h) return PNP_EINVAL;
   HIP_TRY(h, hipSetDevice(h->cfg.device));

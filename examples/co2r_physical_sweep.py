@@ -54,11 +54,13 @@ def main():
     ap.add_argument('--nx', type=int, default=384)
     ap.add_argument('--scf', action='store_true', help='also run the SCF outer loop (kinetics callback on the host) for comparison')
     ap.add_argument('--scf-device', action='store_true', help='also run the SCF outer loop on the device (pnp_scf_cycle)')
+    ap.add_argument('--device-observables', action='store_true',
+                    help='derive field, pH, conductivity, current density and potential drops on the device (Calculator(derive_on_device=True))')
     a = ap.parse_args()
     tp, phis = build(a.lanes, a.nx)
     rate = tafel_rate(tp)
     kin = [{'species': 'CO2', 'rate': rate, 'stoichiometry': {'CO2': -1.0, 'CO': 1.0, 'OH-': 2.0}}]
-    calc = Calculator(transport=tp, calc='comsol')
+    calc = Calculator(transport=tp, calc='comsol', derive_on_device=a.device_observables)
     tp.newton = {'tol': 1e-8, 'maxit': 80}
     calc.set_surface_kinetics(kin)
     t0 = time.time()
@@ -79,6 +81,10 @@ def main():
         print('%7.3f   %12.5f   %8.4f   %5.2f   %9.4f   %8.1f' % (phis[i], j[i], d['species']['CO2']['surface_concentration'], ph,
                                                                 d['system']['surface_potential'], d['species']['K+']['surface_concentration']))
     print('diffusion-limited CO2 current without buffer regeneration: %.3f mA/cm2' % jlim)
+    if a.device_observables:      # the table of scalars per operating point, as the device left it (catint_amd._observe.SCALARS)
+        from catint_amd._observe import SCALARS
+        print('device observables [%d x %d]: %s' % (calc.observables.shape + (', '.join(SCALARS),)))
+        print('  first / last operating point: %s / %s' % (np.array2string(calc.observables[0], precision=4), np.array2string(calc.observables[-1], precision=4)))
     if a.scf_device:
         tp3, _ = build(a.lanes, a.nx)
         tp3.newton = tp.newton

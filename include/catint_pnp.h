@@ -357,6 +357,21 @@ int pnp_get_state(pnp_handle* h, double* c, double* v, double* grad_v, double* l
 int pnp_get_surface(pnp_handle* h, double* csurf, double* vsurf, double* esurf);
 int pnp_get_status(pnp_handle* h, int32_t* status /* [B] */);
 
+/* Where the state lives on the device, for code that derives quantities from it there instead of copying it out (libcatint_observe,
+ * catint_observe.h).  No kernel, no copy, no synchronisation: the pointers of the handle's own buffers.  The view is valid until
+ * the next pnp_set_batch or pnp_destroy; the contents are ordered on `stream` (work enqueued there sees the state every earlier
+ * call on the handle left behind).  Readers only: the buffers stay the handle's.  PNP_ESTATE before pnp_set_batch. */
+typedef struct pnp_device_view {
+  int32_t struct_size, method, nspecies, nx, row_pitch, reserved;   /* struct_size = sizeof(pnp_device_view), set by the library;
+                                                                      * method = PNP_METHOD_*; row_pitch in doubles */
+  int64_t batch;
+  const double* c_dev;        /* [B][N][row_pitch] */
+  const double* phi_dev;      /* [B][row_pitch], physical mode; NULL otherwise */
+  const int32_t* status_dev;  /* [B] */
+  void* stream;               /* the handle's hipStream_t */
+} pnp_device_view;
+int pnp_get_device_view(pnp_handle* h, pnp_device_view* out);
+
 /* ---- measurement hooks (bench.py; HIP events on the handle's own stream) ---------------------- */
 int pnp_synchronize(pnp_handle* h);
 int pnp_timer_start(pnp_handle* h);
