@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pnp_internal.h"
@@ -55,14 +56,9 @@ struct pnp_handle {
   int32_t* bdf_acc = nullptr;               // ... and per-lane iteration counts / status summed over the launches of one pnp_step call
   double* phi_old2 = nullptr;               // predictor: the potential of the time level before the current one
   double* vol_dev = nullptr;                // ... and the ion volumes for its crowding guard
-  int nw_ext_old = 0;                       // set around a prepared step: c_old is given (BDF2 combination or c_n under the predictor)
-  double nw_sig_scale = 1.0;                // ... and 1/dt carries the factor 3/2 of BDF2
-  int nw_bdf2_inline = 0, nw_bdf_hist0 = 0; // set around a launch of several BDF2 steps by a lane kernel, which keeps the history itself
   std::vector<uint8_t> lane_hist;           // per lane: c_old2 (phi_old2) holds the level before its current state (cleared by an upload
                                             // and a change of time_order / predictor for every lane, by a stationary solve or patch for
                                             // the lanes it touched: their next step is backward Euler)
-  int nw_family = -1;                       // >= 0: the NewtonFamily every launch of one pnp_step call uses (sized by the caller's mask and,
-                                            // for the sweeps, by the full batch, which is constant within a call)
   ReactionSides* rs_dev = nullptr;          // the table flattened per reaction side (lane kernels)
   int rs_max_exponent = 0;
   int n_wk = 0;
@@ -76,8 +72,6 @@ struct pnp_handle {
   int64_t work_stride = 0;
   int32_t* iters = nullptr;
   int nw_blocks = 0;
-  // device SCF loop (pnp_scf_cycle): per-lane bookkeeping, allocated on first use; the two switches below are set around
-  // its transport solves
   double* sweep = nullptr;               // sweep kernel: records of the resident teams (allocated on first use)
   int sweep_blocks = 0;
   struct LaneWorkspace {                 // lane kernels, one per family (lane_workspace): batch-innermost state copies + records of
@@ -89,27 +83,25 @@ struct pnp_handle {
   std::vector<float> lane_key;           // |phiM - phi_bulk| per operating point (pnp_set_batch / pnp_set_pb): the order of a first call
   std::vector<int32_t> lane_iters_host, lane_perm_host;
   bool iters_valid = false;              // h->iters holds the iteration counts of a Newton call on this batch
-  bool lane_perm_keep = false;           // inside one pnp_step call of several launches (BDF2 / predictor): the launches after the first
-  int64_t lane_perm_B = 0;               // keep the first one's order (no read-back, no sort, no synchronisation per timestep)
+  int64_t lane_perm_B = 0;               // slots the order in lane_perm fills (0: the last launch used none)
+  // device SCF loop (pnp_scf_cycle): per-lane bookkeeping, allocated on first use
   double* scf_d = nullptr;               // (4N + 5) B doubles
   double* scf_snap = nullptr;            // (N + 1) ldx B doubles: per-lane state of the last converged transport solve
   int32_t* scf_i = nullptr;              // 3 B flags + 65 counters
-  const int32_t* newton_mask = nullptr;  // lanes to solve (null: all)
-  const int32_t* newton_mask_host = nullptr;  // ... its host copy, when the host has one (not the SCF loop's device flags): a masked
-  int64_t newton_mask_count = 0;         // solve is sized (kernel choice, lane groups) by the lanes it solves
-  int32_t* user_mask = nullptr;          // pnp_set_lane_mask's copy
+  bool user_mask_set = false;            // pnp_set_lane_mask: the caller's mask is in force (caller_mask) ...
+  int32_t* user_mask = nullptr;          // ... its device copy
   std::vector<int32_t> user_mask_host;
   int64_t user_mask_count = 0;
   int32_t* sub_mask = nullptr;           // device [2][capacity]: the active lanes of a call without / with a history, when both occur
   std::vector<int32_t> sub_mask_host;    // ... [2][B]
-  bool newton_explicit_kinetics = false; // the wall-kinetics table feeds the prescribed fluxes instead of the Jacobian
   int cur = 0;  // lapl[cur] = charge row of the current state; lapl[1-cur] = row used by the last step
   // pnp_step with several launches in one call: the batch is cut into row chunks whose launch sequences run on streams of their own
   // (rows are independent), so one chunk's launch boundary is covered by the other chunk's rows; created on first use
   static constexpr int MAX_STEP_STREAMS = 4;
   hipStream_t aux_stream[MAX_STEP_STREAMS - 1] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[MAX_STEP_STREAMS - 1] = {nullptr, nullptr, nullptr};
-  int64_t dev_bytes = 0;
+  std::vector<std::pair<void*, size_t>> allocs;      // what dev_alloc gave the handle: (pointer, bytes); pnp_destroy frees what is left
+  int64_t dev_bytes = 0;                             // ... and their sum
   std::string err;
 };
 
@@ -189,8 +181,30 @@ static int fail(pnp_handle* h, int code, const std::string& msg) {
 template <typename T>
 static hipError_t dev_alloc(pnp_handle* h, T** p, size_t count) {
   hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-  if (e == hipSuccess) h->dev_bytes += (int64_t)(count * sizeof(T));
+  if (e == hipSuccess) {
+    h->allocs.emplace_back((void*)*p, count * sizeof(T));
+    h->dev_bytes += (int64_t)(count * sizeof(T));
+  }
   return e;
+}
+
+// bytes of the dev_alloc allocation at p (0: none of the handle's)
+static size_t dev_size(const pnp_handle* h, const void* p) {
+  for (const auto& r : h->allocs)
+    if (r.first == p) return r.second;
+  return 0;
+}
+
+// gives one dev_alloc allocation back to the device
+template <typename T>
+static void free_dev(pnp_handle* h, T** p) {
+  const auto it = std::find_if(h->allocs.begin(), h->allocs.end(), [&](const std::pair<void*, size_t>& r) { return r.first == (void*)*p; });
+  if (it != h->allocs.end()) {
+    (void)hipFree(it->first);
+    h->dev_bytes -= (int64_t)it->second;
+    h->allocs.erase(it);
+  }
+  *p = nullptr;
 }
 
 extern "C" {
@@ -203,12 +217,7 @@ void pnp_destroy(pnp_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->cfg.device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->c, (void*)h->lapl[0], (void*)h->lapl[1], (void*)h->v, (void*)h->gradv, (void*)h->rates,
-                  (void*)h->pb, (void*)h->vzeta, (void*)h->flux, (void*)h->cbulk, (void*)h->csurf, (void*)h->status,
-                  (void*)h->spec, (void*)h->ytmp, (void*)h->ftmp, (void*)h->c_old, (void*)h->work, (void*)h->iters, (void*)h->stash, (void*)h->rt_dev, (void*)h->rs_dev, (void*)h->c_old2, (void*)h->phi_old2, (void*)h->vol_dev, (void*)h->bdf_acc, (void*)h->wk_k, (void*)h->gw, (void*)h->gv, (void*)h->mol_lapl, (void*)h->scf_d, (void*)h->scf_i, (void*)h->scf_snap, (void*)h->stage, (void*)h->sweep, (void*)h->lane_perm, (void*)h->user_mask, (void*)h->sub_mask, (void*)h->ode_buf, (void*)h->ode_int, (void*)h->rkc_d, (void*)h->rkc_i})
-    if (p) (void)hipFree(p);
-  for (const auto& ws : h->lane_ws)
-    if (ws.buf) (void)hipFree(ws.buf);
+  for (const auto& r : h->allocs) (void)hipFree(r.first);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -544,8 +553,7 @@ int pnp_set_batch(pnp_handle* h, int64_t B, const double* c0, const double* pb, 
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   const int N = h->a.N, nx = h->a.nx, ldx = h->a.ldx;
   h->B = B;
-  h->newton_mask = nullptr;      // (a lane mask belongs to the batch it was set for)
-  h->newton_mask_host = nullptr;
+  h->user_mask_set = false;      // (a lane mask belongs to the batch it was set for)
   h->a.B = B;
   // One contiguous upload into a staging buffer; unpack_state_kernel writes the pitched rows (zero pads: they travel through
   // the kernels untouched), the bulk Dirichlet values = last grid point of the initial state (calculator_old.py:540) and the
@@ -712,21 +720,55 @@ static int step_streams(const pnp_handle* h, int launches) {
   return S;
 }
 
+// ---- one Newton launch of the physical mode: everything run_newton needs beyond the handle's physics ----
+// the lanes a launch solves.  dev == nullptr: every lane; host == nullptr: device-only flags (the SCF loop's), else the host's copy of
+// dev with `count` lanes set: a masked solve is sized (kernel choice, lane groups) by the lanes it solves
+struct LaneMask {
+  const int32_t *dev = nullptr, *host = nullptr;
+  int64_t count = 0;
+};
+struct NewtonCall {
+  int nsteps = 1;                        // backward-Euler steps of the launch, or
+  bool stationary = false;               // ... one solve with 1/dt = 0 (ignores ext_old and bdf2_inline)
+  double tol = 0.0;                      // 0: the handle's pnp_newton_params
+  int maxit = 0;                         // ... likewise
+  LaneMask mask{};
+  bool ext_old = false;                  // prepared step: c_old is given (BDF2 combination, or c_n under the predictor) ...
+  double sig_scale = 1.0;                // ... and 1/dt carries the factor 3/2 of BDF2
+  bool bdf2_inline = false, bdf_hist0 = false;      // several BDF2 steps by a lane kernel, which keeps the history itself / finds one in c_old2
+  NewtonFamily family = NF_NONE;         // NF_NONE: run_newton chooses; else the family pinned for every launch of one API call
+  bool keep_lane_order = false;          // later launches of one pnp_step call reuse the first one's lane order
+  bool explicit_kinetics = false;        // SCF loop: the wall-kinetics table feeds the prescribed fluxes, not the Jacobian
+};
+
+// the mask of pnp_set_lane_mask
+static LaneMask caller_mask(const pnp_handle* h) {
+  if (!h->user_mask_set) return {};
+  return {h->user_mask, h->user_mask_host.data(), h->user_mask_count};
+}
+
+// lane_hist, one flag for every lane of the current batch
+static std::vector<uint8_t>& lane_history(pnp_handle* h) {
+  if ((int64_t)h->lane_hist.size() != h->B) h->lane_hist.assign((size_t)h->B, 0);
+  return h->lane_hist;
+}
+
 // Lane kernels: a wave iterates until the slowest of its operating points is done, and the points that are done keep streaming their
 // records (pnp_lane.hip) -- 1.15-1.28 x the algorithmic HBM bytes measured on random batches.  So the operating points are dealt to
 // the slots (group, lane) in the order of the Newton iterations they are expected to need, most first (the long waves start first,
 // the short ones fill the tail): by the iteration counts of the previous Newton call on this batch (read back here: one small copy
 // and a counting sort per call), before that by the wall-to-bulk potential difference.  The arithmetic of a point does not depend on
 // its slot: results are the same to the bit with and without the order (tests/test_gpu_lane.py).
-static int lane_order(pnp_handle* h, NewtonArgs& a) {
+static int lane_order(pnp_handle* h, NewtonArgs& a, const NewtonCall& call) {
   a.lane_perm = nullptr;
   const int64_t B = h->B;
-  if (!h->lane_perm_keep) h->lane_perm_B = 0;
+  const LaneMask& mask = call.mask;
+  if (!call.keep_lane_order) h->lane_perm_B = 0;
   // a solve restricted by pnp_set_lane_mask (the rerun ladder's confirming solve: a handful of recovered lanes): only the lanes it solves
   // are dealt to slots, and the launch covers ceil(n / points per group) groups instead of the whole batch
-  const bool masked = h->newton_mask && h->newton_mask_host && h->newton_mask_count < B;
+  const bool masked = mask.dev && mask.host && mask.count < B;
   if ((h->opt.lane_order == 0 || B < 64) && !masked) return PNP_OK;
-  if (h->lane_perm_keep && h->lane_perm && h->lane_perm_B > 0) {      // the order of this call's first launch
+  if (call.keep_lane_order && h->lane_perm && h->lane_perm_B > 0) {      // the first launch's order: no read-back, sort or synchronisation
     a.lane_perm = h->lane_perm;
     a.B = h->lane_perm_B;
     return PNP_OK;
@@ -762,7 +804,7 @@ static int lane_order(pnp_handle* h, NewtonArgs& a) {
   if (masked) {      // keep the order, drop the lanes that are not solved
     size_t n = 0;
     for (int64_t s_ = 0; s_ < B; ++s_)
-      if (h->newton_mask_host[(size_t)perm[(size_t)s_]] != 0) perm[n++] = perm[(size_t)s_];
+      if (mask.host[(size_t)perm[(size_t)s_]] != 0) perm[n++] = perm[(size_t)s_];
     for (size_t s_ = n; s_ < (size_t)B; ++s_) perm[s_] = perm[n > 0 ? n - 1 : 0];
     a.B = (int64_t)n;
   }
@@ -844,7 +886,7 @@ __global__ void bdf2_accumulate_kernel(int32_t* __restrict__ acc, int32_t* __res
   }
 }
 
-static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, int maxit);
+static int run_newton(pnp_handle* h, const NewtonCall& call);
 
 // kernel variant of the handle's physics: 0 point ions, 1 steric ions, 2 + homogeneous reactions and / or the constant convection term
 // (variant 3 is supported by none of the lane kernels: a guard for tables their flattened form could not hold -- none at present,
@@ -857,23 +899,17 @@ static int newton_variant(const pnp_handle* h) {
 
 // (a solve restricted to a few lanes by pnp_set_lane_mask is sized by those lanes: the workgroup-per-point kernels skip masked-out
 // points at once, the lane kernels would walk every group)
-static int64_t newton_effective_batch(const pnp_handle* h) {
-  const bool host_mask = h->newton_mask && h->newton_mask_host;
-  return host_mask ? (h->newton_mask_count > 0 ? h->newton_mask_count : 1) : h->B;
+static int64_t newton_effective_batch(const pnp_handle* h, const LaneMask& mask) {
+  return mask.dev && mask.host ? (mask.count > 0 ? mask.count : 1) : h->B;
 }
 
-// the kernel family that runs this handle's batch under options o (pnp_newton.hip: newton_family makes the choice; its callers:
-// run_newton, newton_timesteps, pnp_autotune_default, pnp_tune_placement)
-static NewtonFamily newton_family(const pnp_handle* h, const Options& o) {
+// the kernel family that runs the lanes of `mask` of this handle's batch under options o (pnp_newton.hip: newton_family makes the
+// choice; its callers: run_newton, newton_timesteps, pnp_autotune_default, pnp_tune_placement)
+static NewtonFamily newton_family(const pnp_handle* h, const Options& o, const LaneMask& mask) {
   const bool rt = h->rt_dev && h->rt.n > 0;
-  const NewtonShape s = {h->a.N + 1, h->a.nx, h->B, newton_effective_batch(h), h->mpb, rt, h->velocity != 0.0, newton_variant(h) != 3,
+  const NewtonShape s = {h->a.N + 1, h->a.nx, h->B, newton_effective_batch(h, mask), h->mpb, rt, h->velocity != 0.0, newton_variant(h) != 3,
                          h->work != nullptr};
   return newton_family(s, o);
-}
-
-static size_t lane_group_doubles(const pnp_handle* h, NewtonFamily f) {
-  const NewtonFamilyInfo& F = newton_family_info(f);
-  return F.rec_doubles(h->a.N + 1, h->a.nx) + F.state_doubles(h->a.N + 1, h->a.nx);
 }
 
 // the workspace of lane family f for a launch: transposed state + records of as many groups as the batch capacity has, capped at
@@ -882,7 +918,7 @@ static int lane_workspace(pnp_handle* h, NewtonFamily f, NewtonArgs& a) {
   const NewtonFamilyInfo& F = newton_family_info(f);
   pnp_handle::LaneWorkspace& ws = h->lane_ws[f];
   const int N = h->a.N, nx = h->a.nx, P = F.points;
-  const size_t per_group = lane_group_doubles(h, f) * sizeof(double);
+  const size_t per_group = (F.rec_doubles(N + 1, nx) + F.state_doubles(N + 1, nx)) * sizeof(double);
   if (!ws.buf) {
     int64_t groups = (h->cfg.batch_capacity + P - 1) / P;
     const int64_t fit = (int64_t)(((size_t)48 << 30) / per_group);
@@ -902,100 +938,78 @@ static int lane_workspace(pnp_handle* h, NewtonFamily f, NewtonArgs& a) {
   return PNP_OK;
 }
 
-// launches of one call restricted to a mask of the handle's own (the active lanes of one history class), set around run_newton
-struct MaskScope {
-  pnp_handle* h;
-  const int32_t *dev, *host;
-  int64_t count;
-  MaskScope(pnp_handle* h_, const int32_t* d, const int32_t* hm, int64_t n)
-      : h(h_), dev(h_->newton_mask), host(h_->newton_mask_host), count(h_->newton_mask_count) {
-    h->newton_mask = d;
-    h->newton_mask_host = hm;
-    h->newton_mask_count = n;
-  }
-  ~MaskScope() {
-    h->newton_mask = dev;
-    h->newton_mask_host = host;
-    h->newton_mask_count = count;
-  }
-};
-
-// nsteps timesteps of the physical mode: one launch (backward Euler), or one launch per step (BDF2 and / or the predictor).
-// The history is per lane (lane_hist): a lane's first step is backward Euler from u_0, which becomes its history, whatever the other
-// lanes do.  A call whose active lanes all have a history, or none has, makes the launches of one batch; one that mixes them starts with
-// a launch for each class under masks of its own (sub_mask) -- the device code never sees more than one class.
-static int newton_timesteps(pnp_handle* h, int nsteps) {
+// nsteps timesteps of the physical mode for the lanes of `mask`: one launch (backward Euler), or one launch per step (BDF2 and / or the
+// predictor).  The history is per lane (lane_hist): a lane's first step is backward Euler from u_0, which becomes its history, whatever
+// the other lanes do.  A call whose active lanes all have a history, or none has, makes the launches of one batch; one that mixes them
+// starts with a launch for each class under masks of its own (sub_mask) -- the device code never sees more than one class.
+static int newton_timesteps(pnp_handle* h, int nsteps, const LaneMask& mask) {
   const bool bdf2 = h->np.time_order == 2, pred = h->np.predictor == 1;
-  if ((!bdf2 && !pred) || nsteps < 1) return run_newton(h, nsteps, false, 0.0, 0);
+  NewtonCall call;      // what the launches of this call share; each launch is a copy with its own steps, lanes and preparation
+  call.nsteps = nsteps;
+  call.mask = mask;
+  if ((!bdf2 && !pred) || nsteps < 1) return run_newton(h, call);
   const int N = h->a.N, ldx = h->a.ldx, nx = h->a.nx;
   const size_t n = (size_t)h->B * N * ldx;
   const int64_t B = h->B;
   const size_t cap = (size_t)h->cfg.batch_capacity;
   if (!h->c_old2) HIP_TRY(h, dev_alloc(h, &h->c_old2, cap * N * ldx));
-  // the lanes of this call (the caller's mask) by history
-  const int32_t* um = h->newton_mask ? h->newton_mask_host : nullptr;
-  if ((int64_t)h->lane_hist.size() != B) h->lane_hist.assign((size_t)B, 0);
+  // the lanes of this call by history
+  const int32_t* um = mask.dev ? mask.host : nullptr;
+  std::vector<uint8_t>& hist = lane_history(h);
   int64_t n_act = 0, n_hist = 0;
   for (int64_t b = 0; b < B; ++b)
     if (!um || um[b]) {
       ++n_act;
-      n_hist += h->lane_hist[(size_t)b] ? 1 : 0;
+      n_hist += hist[(size_t)b] ? 1 : 0;
     }
   const bool mixed = n_hist > 0 && n_hist < n_act, all_hist = n_act > 0 && n_hist == n_act;
-  const int32_t *m_new = nullptr, *m_old = nullptr;      // device: the active lanes without / with a history (mixed calls)
+  LaneMask m_new, m_old;      // the active lanes without / with a history (mixed calls)
   if (mixed) {
     if (!h->sub_mask) HIP_TRY(h, dev_alloc(h, &h->sub_mask, cap * 2));
     h->sub_mask_host.assign((size_t)B * 2, 0);
     for (int64_t b = 0; b < B; ++b)
-      if (!um || um[b]) h->sub_mask_host[(size_t)(h->lane_hist[(size_t)b] ? B + b : b)] = 1;
+      if (!um || um[b]) h->sub_mask_host[(size_t)(hist[(size_t)b] ? B + b : b)] = 1;
     HIP_TRY(h, hipMemcpyAsync(h->sub_mask, h->sub_mask_host.data(), (size_t)B * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    m_new = h->sub_mask;
-    m_old = h->sub_mask + B;
+    m_new = {h->sub_mask, h->sub_mask_host.data(), n_act - n_hist};
+    m_old = {h->sub_mask + B, h->sub_mask_host.data() + B, n_hist};
   }
   auto mark = [&] {      // the active lanes have a history from here on
     for (int64_t b = 0; b < B; ++b)
-      if (!um || um[b]) h->lane_hist[(size_t)b] = 1;
+      if (!um || um[b]) hist[(size_t)b] = 1;
   };
   // every launch of the call runs the family the caller's mask sizes (a class of a mixed call is no batch of its own)
-  struct Pin {
-    pnp_handle* h;
-    ~Pin() {
-      h->nw_family = -1;
-      h->nw_bdf2_inline = 0;
-      h->nw_bdf_hist0 = 0;
-      h->nw_ext_old = 0;
-      h->nw_sig_scale = 1.0;
-    }
-  } pin{h};
-  h->nw_family = newton_family(h, h->opt);
+  call.family = newton_family(h, h->opt, mask);
   auto accumulate = [&](int last) -> int {
     hipLaunchKernelGGL(bdf2_accumulate_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, h->bdf_acc, h->iters, h->status, B,
-                       last, h->newton_mask);
+                       last, mask.dev);
     HIP_TRY(h, hipGetLastError());
     return PNP_OK;
   };
   int rc = PNP_OK;
-  if (bdf2 && !pred && h->nw_family < NUM_LANE_FAMILIES) {
+  if (bdf2 && !pred && call.family < NUM_LANE_FAMILIES) {
     // the lane kernels keep the history themselves: ONE launch for all nsteps (the first step of a trajectory is backward Euler
     // from u_0, which becomes the history -- as below), c_old2 is the history's home between launches
-    h->nw_bdf2_inline = 1;
+    call.bdf2_inline = true;
     if (!mixed) {
-      h->nw_bdf_hist0 = all_hist ? 1 : 0;
-      rc = run_newton(h, nsteps, false, 0.0, 0);
+      call.bdf_hist0 = all_hist;
+      rc = run_newton(h, call);
     } else {
       // one step for each class, then the rest of the call for all of them
       if (!h->bdf_acc) HIP_TRY(h, dev_alloc(h, &h->bdf_acc, cap * 2));
       HIP_TRY(h, hipMemsetAsync(h->bdf_acc, 0, (size_t)B * 2 * sizeof(int32_t), h->stream));
       for (int g = 0; g < 2 && rc == PNP_OK; ++g) {
-        MaskScope ms(h, g ? m_old : m_new, h->sub_mask_host.data() + (g ? B : 0), g ? n_hist : n_act - n_hist);
-        h->nw_bdf_hist0 = g;
-        rc = run_newton(h, 1, false, 0.0, 0);
+        NewtonCall one = call;
+        one.nsteps = 1;
+        one.mask = g ? m_old : m_new;
+        one.bdf_hist0 = g != 0;
+        rc = run_newton(h, one);
       }
       if (rc == PNP_OK) rc = accumulate(nsteps == 1 ? 1 : 0);
       if (rc == PNP_OK && nsteps > 1) {
-        h->nw_bdf_hist0 = 1;
-        rc = run_newton(h, nsteps - 1, false, 0.0, 0);
+        call.nsteps = nsteps - 1;
+        call.bdf_hist0 = true;
+        rc = run_newton(h, call);
         if (rc == PNP_OK) rc = accumulate(1);
       }
     }
@@ -1008,49 +1022,41 @@ static int newton_timesteps(pnp_handle* h, int nsteps) {
   if (pred && h->mpb) HIP_TRY(h, hipMemcpyAsync(h->vol_dev, h->volk, sizeof(double) * PNP_NEWTON_MAX_SPECIES, hipMemcpyHostToDevice, h->stream));
   if (!h->bdf_acc) HIP_TRY(h, dev_alloc(h, &h->bdf_acc, cap * 2));
   HIP_TRY(h, hipMemsetAsync(h->bdf_acc, 0, (size_t)B * 2 * sizeof(int32_t), h->stream));
-  struct KeepPerm {      // (the launches of this call after the first keep its lane order)
-    pnp_handle* h;
-    ~KeepPerm() { h->lane_perm_keep = false; }
-  } keep_guard{h};
-  // first step of a trajectory: backward Euler from u_0, which becomes the history (mask: the lanes that take it, null: all)
-  auto first_step = [&](const int32_t* mask) -> int {
-    if (!mask) {
+  call.nsteps = 1;
+  // first step of a trajectory: backward Euler from u_0, which becomes the history (m: the lanes that take it)
+  auto first_step = [&](const LaneMask& m) -> int {
+    if (!m.dev) {
       HIP_TRY(h, hipMemcpyAsync(h->c_old2, h->c, n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
       if (pred) HIP_TRY(h, hipMemcpyAsync(h->phi_old2, h->v, (size_t)B * ldx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     } else {
       hipLaunchKernelGGL(history_start_kernel, dim3(2048), dim3(256), 0, h->stream, (const double*)h->c, h->c_old2, (const double*)h->v,
-                         pred ? h->phi_old2 : nullptr, N, ldx, B, mask);
+                         pred ? h->phi_old2 : nullptr, N, ldx, B, m.dev);
       HIP_TRY(h, hipGetLastError());
     }
-    return run_newton(h, 1, false, 0.0, 0);
+    NewtonCall one = call;
+    one.mask = m;
+    return run_newton(h, one);
   };
   // a step with the history at hand: previous-level combination and start prepared, then one launch
-  auto next_step = [&](const int32_t* mask) -> int {
+  auto next_step = [&](const LaneMask& m) -> int {
     hipLaunchKernelGGL(step_prepare_kernel, dim3(2048), dim3(256), 0, h->stream, h->c, h->c_old2, h->c_old, h->v, h->phi_old2, N, ldx, nx, B,
-                       bdf2 ? 1 : 0, pred ? 1 : 0, (const double*)(pred && h->mpb ? h->vol_dev : nullptr), mask);
+                       bdf2 ? 1 : 0, pred ? 1 : 0, (const double*)(pred && h->mpb ? h->vol_dev : nullptr), m.dev);
     HIP_TRY(h, hipGetLastError());
-    h->nw_ext_old = 1;
-    h->nw_sig_scale = bdf2 ? 1.5 : 1.0;
-    const int r = run_newton(h, 1, false, 0.0, 0);
-    h->nw_ext_old = 0;
-    h->nw_sig_scale = 1.0;
-    return r;
+    NewtonCall one = call;
+    one.mask = m;
+    one.ext_old = true;
+    one.sig_scale = bdf2 ? 1.5 : 1.0;
+    return run_newton(h, one);
   };
   for (int s = 0; s < nsteps; ++s) {
-    h->lane_perm_keep = s > (mixed ? 1 : 0);
+    call.keep_lane_order = s > (mixed ? 1 : 0);      // (a mixed call's first launch for all its lanes is that of its second step)
     if (s == 0 && mixed) {
-      {
-        MaskScope ms(h, m_new, h->sub_mask_host.data(), n_act - n_hist);
-        rc = first_step(m_new);
-      }
-      if (rc == PNP_OK) {
-        MaskScope ms(h, m_old, h->sub_mask_host.data() + B, n_hist);
-        rc = next_step(m_old);
-      }
+      rc = first_step(m_new);
+      if (rc == PNP_OK) rc = next_step(m_old);
     } else if (s == 0 && !all_hist) {
-      rc = first_step(h->newton_mask);
+      rc = first_step(mask);
     } else {
-      rc = next_step(h->newton_mask);
+      rc = next_step(mask);
     }
     if (rc != PNP_OK) return rc;
     if (s == 0) mark();
@@ -1060,12 +1066,15 @@ static int newton_timesteps(pnp_handle* h, int nsteps) {
   return PNP_OK;
 }
 
-// physical mode: nsteps backward-Euler steps (stationary: one solve with 1/dt = 0) in one launch
-static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, int maxit) {
+// physical mode: call.nsteps backward-Euler steps (stationary: one solve with 1/dt = 0) in one launch.  NewtonArgs comes from the
+// handle's physics and buffers and from `call`, and from nothing else.
+static int run_newton(pnp_handle* h, const NewtonCall& call) {
+  const bool stationary = call.stationary;
+  const LaneMask& mask = call.mask;
   if (stationary) {      // (a stationary solve moves the lanes it solves off their trajectories; the SCF loop's lanes: pnp_scf_cycle)
-    if ((int64_t)h->lane_hist.size() != h->B) h->lane_hist.assign((size_t)h->B, 0);
+    std::vector<uint8_t>& hist = lane_history(h);
     for (int64_t b = 0; b < h->B; ++b)
-      if (!h->newton_mask || (h->newton_mask_host && h->newton_mask_host[b])) h->lane_hist[(size_t)b] = 0;
+      if (!mask.dev || (mask.host && mask.host[b])) hist[(size_t)b] = 0;
   }
   NewtonArgs a;
   memset(&a, 0, sizeof(a));
@@ -1074,8 +1083,8 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   a.N = N;
   a.nx = nx;
   a.ldx = h->a.ldx;
-  a.nsteps = nsteps;
-  a.maxit = maxit > 0 ? maxit : h->np.maxit;
+  a.nsteps = call.nsteps;
+  a.maxit = call.maxit > 0 ? call.maxit : h->np.maxit;
   a.wall_bc = h->np.wall_bc;
   a.mpb = h->mpb ? 1 : 0;
   a.estimate = h->np.error_estimate ? 1 : 0;
@@ -1086,14 +1095,14 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   a.work_stride = h->work_stride ? h->work_stride : (int64_t)newton_exchange_doubles(N + 1, nx);
   a.stash = h->stash;
   a.stash_stride = h->stash_stride;
-  a.tol = tol > 0 ? tol : h->np.tol;
+  a.tol = call.tol > 0 ? call.tol : h->np.tol;
   a.dphi_max = h->np.dphi_max;
   a.stern = dx * h->np.stern_capacitance / eps;
   a.phi_pzc = h->np.phi_pzc;
   double qmax = 1.0;
   for (int k = 0; k < N; ++k) {
     a.qb[k] = h->qk[k] * beta;
-    a.sig[k] = stationary ? 0.0 : h->nw_sig_scale * (dx * dx / (h->Dk[k] * dt));
+    a.sig[k] = stationary ? 0.0 : call.sig_scale * (dx * dx / (h->Dk[k] * dt));
     a.fl[k] = dx / h->Dk[k];
     a.peq[k] = dx * dx / eps * h->qk[k];
     a.vol[k] = h->volk[k];
@@ -1105,14 +1114,14 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   a.vt_inv = beta * qmax;
   a.rt = (h->rt_dev && h->rt.n > 0) ? h->rt_dev : nullptr;
   a.sides = a.rt ? h->rs_dev : nullptr;
-  a.n_wk = h->newton_explicit_kinetics ? 0 : h->n_wk;
-  a.lane_mask = h->newton_mask;
-  a.ext_old = (h->nw_ext_old && !stationary) ? 1 : 0;
-  a.bdf2 = (h->nw_bdf2_inline && !stationary) ? 1 : 0;
-  a.bdf_hist0 = a.bdf2 ? h->nw_bdf_hist0 : 0;
+  a.n_wk = call.explicit_kinetics ? 0 : h->n_wk;
+  a.lane_mask = mask.dev;
+  a.ext_old = (call.ext_old && !stationary) ? 1 : 0;
+  a.bdf2 = (call.bdf2_inline && !stationary) ? 1 : 0;
+  a.bdf_hist0 = (a.bdf2 && call.bdf_hist0) ? 1 : 0;
   a.c_old2 = a.bdf2 ? h->c_old2 : nullptr;
   a.opt = &h->opt;
-  const NewtonFamily family = h->nw_family >= 0 ? (NewtonFamily)h->nw_family : newton_family(h, h->opt);
+  const NewtonFamily family = call.family != NF_NONE ? call.family : newton_family(h, h->opt, mask);
   const NewtonWorkspace ws = family < NUM_NEWTON_FAMILIES ? newton_family_info(family).ws : NW_EXCHANGE;
   if (ws == NW_LANE) {
     const int rc = lane_workspace(h, family, a);
@@ -1157,14 +1166,14 @@ static int run_newton(pnp_handle* h, int nsteps, bool stationary, double tol, in
   if (h->opt.newton_blocks >= 1 && h->opt.newton_blocks < blocks) blocks = h->opt.newton_blocks;      // tuning: size of the persistent grid
   if ((int64_t)blocks > h->B) blocks = (int)h->B;
   if (ws == NW_LANE) {
-    const int rc = lane_order(h, a);
+    const int rc = lane_order(h, a, call);
     if (rc != PNP_OK) return rc;
     if (a.B == 0) return PNP_OK;        // (a mask without a lane: nothing to solve)
     HIP_TRY(h, newton_family_info(family).launch(a, h->stream));
   } else {
     HIP_TRY(h, launch_newton(a, family, blocks, h->stream));
   }
-  h->steps_done += nsteps;
+  h->steps_done += call.nsteps;
   h->iters_valid = true;
   return PNP_OK;
 }
@@ -1267,7 +1276,7 @@ int pnp_solve_stationary(pnp_handle* h, double tol, int32_t maxit, int32_t* stat
   if (!h->newton) return fail(h, PNP_EINVAL, "pnp_solve_stationary: the handle was not created with PNP_METHOD_NEWTON");
   if (!h->have_batch) return fail(h, PNP_ESTATE, "pnp_solve_stationary: call pnp_set_batch first");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  const int rc = run_newton(h, 1, true, tol, maxit);
+  const int rc = run_newton(h, {1, true, tol, maxit, caller_mask(h)});
   if (rc != PNP_OK) return rc;
   if (status) return pnp_get_status(h, status);
   return PNP_OK;
@@ -1284,7 +1293,7 @@ int pnp_solve_surface(pnp_handle* h, const double* flux, int32_t nsteps, double*
   const int N = h->a.N, ldx = h->a.ldx;
   // everything below is queued on the handle's stream; one synchronisation at the end
   if (flux) HIP_TRY(h, hipMemcpyAsync(h->flux, flux, (size_t)B * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  const int rc = nsteps == 0 ? run_newton(h, 1, true, 0.0, 0) : newton_timesteps(h, nsteps);
+  const int rc = nsteps == 0 ? run_newton(h, {1, true, 0.0, 0, caller_mask(h)}) : newton_timesteps(h, nsteps, caller_mask(h));
   if (rc != PNP_OK) return rc;
   std::vector<double> p01;
   if (csurf) {
@@ -1388,11 +1397,13 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
   int rc = PNP_OK;
   int32_t left = 1;
   // the loop's stationary solves restrict themselves to the lanes still active: those active now leave their trajectories
-  if ((int64_t)h->lane_hist.size() != B) h->lane_hist.assign((size_t)B, 0);
+  std::vector<uint8_t>& hist = lane_history(h);
   for (int64_t b = 0; b < B; ++b)
-    if (s->active[b]) h->lane_hist[(size_t)b] = 0;
-  const MaskScope caller_mask(h, a.active, nullptr, 0);      // (the caller's mask is back in force on return)
-  h->newton_explicit_kinetics = true;
+    if (s->active[b]) hist[(size_t)b] = 0;
+  NewtonCall solve;      // (its lanes are the loop's device flags, not the caller's mask, which stays in force for the calls after this one)
+  solve.stationary = true;
+  solve.mask = {a.active, nullptr, 0};
+  solve.explicit_kinetics = true;
   for (int istep = p->istep + 1; istep <= p->max_iter && rc == PNP_OK; ++istep) {
     a.istep = istep;
     a.slot = istep & 63;
@@ -1402,7 +1413,7 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
       rc = fail(h, PNP_EDEVICE, std::string("pnp_scf_cycle: ") + hipGetErrorString(e));
       break;
     }
-    rc = run_newton(h, 1, true, 0.0, 0);       // stationary, warm: the state of the previous iteration (restart=True, calculator.py:523)
+    rc = run_newton(h, solve);       // stationary, warm: the state of the previous iteration (restart=True, calculator.py:523)
     if (rc != PNP_OK) break;
     e = launch_scf_keep(a, st);
     if (e == hipSuccess) e = launch_scf_post(a, st);
@@ -1413,7 +1424,6 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
     }
     if (e != hipSuccess) rc = fail(h, PNP_EDEVICE, std::string("pnp_scf_cycle: ") + hipGetErrorString(e));
   }
-  h->newton_explicit_kinetics = false;
   if (rc != PNP_OK) return rc;
   int32_t last = 0;
   HIP_TRY(h, hipMemcpyAsync(s->surface_concentration, a.sc, bn, hipMemcpyDeviceToHost, st));
@@ -1464,8 +1474,8 @@ int pnp_set_lanes(pnp_handle* h, int64_t n, const int64_t* lanes, const double* 
     if (lanes[i] < 0 || lanes[i] >= h->B) return fail(h, PNP_EINVAL, "pnp_set_lanes: lane index out of range");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   // (the patched lanes have no previous time level of their own: their next BDF2 / predictor step starts over; the others keep theirs)
-  if ((int64_t)h->lane_hist.size() != h->B) h->lane_hist.assign((size_t)h->B, 0);
-  for (int64_t i = 0; i < n; ++i) h->lane_hist[(size_t)lanes[i]] = 0;
+  std::vector<uint8_t>& hist = lane_history(h);
+  for (int64_t i = 0; i < n; ++i) hist[(size_t)lanes[i]] = 0;
   const int N = h->a.N, nx = h->a.nx, ldx = h->a.ldx;
   const size_t w = (size_t)nx * sizeof(double), dp = (size_t)ldx * sizeof(double);
   // a handful of lanes: one strided copy per lane (N rows of the concentrations, one of the potential), all on the handle's stream
@@ -1484,8 +1494,7 @@ int pnp_set_lane_mask(pnp_handle* h, const int32_t* mask) {
   if (!h->have_batch) return fail(h, PNP_ESTATE, "pnp_set_lane_mask: call pnp_set_batch first");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   if (!mask) {
-    h->newton_mask = nullptr;
-    h->newton_mask_host = nullptr;
+    h->user_mask_set = false;
     return PNP_OK;
   }
   h->user_mask_host.assign(mask, mask + h->B);
@@ -1494,9 +1503,7 @@ int pnp_set_lane_mask(pnp_handle* h, const int32_t* mask) {
   if (!h->user_mask) HIP_TRY(h, dev_alloc(h, &h->user_mask, (size_t)h->cfg.batch_capacity));
   HIP_TRY(h, hipMemcpyAsync(h->user_mask, mask, (size_t)h->B * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  h->newton_mask = h->user_mask;
-  h->newton_mask_host = h->user_mask_host.data();
-  h->newton_mask_count = h->user_mask_count;
+  h->user_mask_set = true;
   return PNP_OK;
 }
 
@@ -1509,14 +1516,6 @@ static const struct {
                                         {"workgroup", NK_WORKGROUP, -1}, {"team", NK_TEAM, -1},   {"sweep", NK_SWEEP, -1}, {"both", NK_BOTH, -1}};
 
 const char* pnp_autotune_name(int32_t i) { return (i >= 0 && i < PNP_AUTOTUNE_CHOICES) ? kTuneChoices[i].name : nullptr; }
-
-static void free_dev(pnp_handle* h, double** p, size_t bytes) {
-  if (*p) {
-    (void)hipFree(*p);
-    h->dev_bytes -= (int64_t)bytes;
-  }
-  *p = nullptr;
-}
 
 // ---- trials of pnp_autotune and pnp_tune_placement: timesteps on the handle's own state, which is put back before every trial and at
 // the end with everything a step moves along (six device arrays and the host's bookkeeping); the copies live for one call and are not
@@ -1590,7 +1589,7 @@ struct Trials {
     int rc = PNP_OK;
     for (auto t0 = std::chrono::steady_clock::now(); rc == PNP_OK && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(200);) {
       rc = restore();
-      if (rc == PNP_OK) rc = newton_timesteps(h, 1);
+      if (rc == PNP_OK) rc = newton_timesteps(h, 1, caller_mask(h));
       if (rc == PNP_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, PNP_EDEVICE, std::string(who) + ": synchronisation failed");
     }
     return rc;
@@ -1602,7 +1601,7 @@ struct Trials {
     for (int pass = 0; pass < 2 && rc == PNP_OK; ++pass) {
       rc = restore();
       if (rc == PNP_OK && hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(h, PNP_EDEVICE, std::string(who) + ": hipEventRecord");
-      if (rc == PNP_OK) rc = newton_timesteps(h, pass == 0 ? 1 : nsteps);
+      if (rc == PNP_OK) rc = newton_timesteps(h, pass == 0 ? 1 : nsteps, caller_mask(h));
       if (rc == PNP_OK && (hipEventRecord(e1, h->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                            hipEventElapsedTime(ms, e0, e1) != hipSuccess))
         rc = fail(h, PNP_EDEVICE, std::string(who) + ": timing a trial failed");
@@ -1616,7 +1615,7 @@ int32_t pnp_autotune_default(const pnp_handle* h) {
   Options o = h->opt;
   o.newton_kernel = NK_AUTO;
   o.lane_fused = -1;
-  const NewtonFamily f = newton_family(h, o);
+  const NewtonFamily f = newton_family(h, o, caller_mask(h));
   return f == NF_NONE ? -1 : newton_family_info(f).tune;
 }
 
@@ -1680,9 +1679,9 @@ int pnp_autotune(pnp_handle* h, int32_t nsteps, double* ms_per_step, int32_t* ch
   // the workspaces of the families that lost go back to the device
   const NewtonFamily won = newton_forced_family(kTuneChoices[best_i].kernel);
   for (int f = 0; f < NUM_LANE_FAMILIES; ++f)
-    if (f != won) free_dev(h, &h->lane_ws[f].buf, (size_t)h->lane_ws[f].groups * lane_group_doubles(h, (NewtonFamily)f) * sizeof(double));
+    if (f != won) free_dev(h, &h->lane_ws[f].buf);
   if (won != NF_NONE && (newton_family_info(won).ws == NW_LANE || newton_family_info(won).ws == NW_WORK))      // the lane and team choices
-    free_dev(h, &h->sweep, (size_t)h->sweep_blocks * newton_sweep_doubles(nb, nx) * (size_t)(64 / nb) * sizeof(double));
+    free_dev(h, &h->sweep);
   if (chosen) *chosen = best_i;
   return PNP_OK;
 }
@@ -1701,10 +1700,9 @@ int pnp_tune_placement(pnp_handle* h, int32_t nsteps, int32_t trials, double* ms
   if (nsteps < 1 || nsteps > 64 || trials < 1 || trials > 16) return fail(h, PNP_EINVAL, "pnp_tune_placement: nsteps 1 ... 64, trials 1 ... 16");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   for (int i = 0; i < trials && ms_per_step; ++i) ms_per_step[i] = -1.0;
-  const NewtonFamily family = newton_family(h, h->opt);
+  const NewtonFamily family = newton_family(h, h->opt, caller_mask(h));
   if (family >= NUM_LANE_FAMILIES) return PNP_OK;      // (no lane kernel for this batch: nothing to place)
   pnp_handle::LaneWorkspace& ws = h->lane_ws[family];
-  const size_t per_group = lane_group_doubles(h, family);
   Trials tr(h, "pnp_tune_placement");
   if (tr.alloc() != hipSuccess) return fail(h, PNP_ENOMEM, "pnp_tune_placement: no memory for the state snapshot");
   if (tr.begin() != hipSuccess) return fail(h, PNP_EDEVICE, "pnp_tune_placement: set-up failed");
@@ -1717,7 +1715,7 @@ int pnp_tune_placement(pnp_handle* h, int32_t nsteps, int32_t trials, double* ms
       // the next placement: run_newton allocates on first use, while the earlier workspaces are still there -- if the device has room for
       // it twice over (other handles and other processes on the device allocate too), else what was measured so far decides
       size_t free_b = 0, total_b = 0;
-      const size_t W = (size_t)ws.groups * per_group * sizeof(double);
+      const size_t W = dev_size(h, ws.buf);
       if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * W + ((size_t)4 << 30)) break;
       ws.buf = nullptr;
     }
@@ -1742,7 +1740,7 @@ int pnp_tune_placement(pnp_handle* h, int32_t nsteps, int32_t trials, double* ms
   ws.buf = best_buf;
   const int restored = tr.restore(true);
   for (double* p : held)      // every workspace but the one the handle keeps
-    if (p != ws.buf) free_dev(h, &p, (size_t)ws.groups * per_group * sizeof(double));
+    if (p != ws.buf) free_dev(h, &p);
   return restored != PNP_OK ? restored : rc;
 }
 
@@ -1753,7 +1751,7 @@ int pnp_step(pnp_handle* h, int32_t nsteps, int32_t steps_per_launch) {
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   if (h->newton) {
     if (nsteps == 0) return PNP_OK;
-    return newton_timesteps(h, nsteps);
+    return newton_timesteps(h, nsteps, caller_mask(h));
   }
   int spl = steps_per_launch <= 0 ? 256 : steps_per_launch;   // kernel boundaries cost ~6 us each
   if (h->a.has_rates) spl = 1;
@@ -1920,8 +1918,7 @@ static int integrate_explicit_rk(pnp_handle* h, const pnp_ode_params* p, int32_t
   hipStream_t st = h->stream;
   if (h->ode_buf && h->ode_nbuf < nbuf) {      // a DOPRI5 workspace cannot hold DOP853's twelve buffers
     HIP_TRY(h, hipStreamSynchronize(st));
-    (void)hipFree(h->ode_buf);
-    h->ode_buf = nullptr;
+    free_dev(h, &h->ode_buf);
   }
   if (!h->ode_buf) {
     HIP_TRY(h, dev_alloc(h, &h->ode_buf, (size_t)nbuf * cnt + (size_t)cap * ODE_ND));

@@ -376,7 +376,9 @@ int pnp_get_device_view(pnp_handle* h, pnp_device_view* out);
 int pnp_synchronize(pnp_handle* h);
 int pnp_timer_start(pnp_handle* h);
 int pnp_timer_stop(pnp_handle* h, float* elapsed_ms); /* synchronises the stream */
-/* bytes of device memory held, and the device row pitch (in doubles) of one species row */
+/* bytes of device memory the handle holds now (what it gave back -- the workspaces of the families that lost pnp_autotune, the placements
+ * pnp_tune_placement dropped, a DOPRI5 workspace replaced by DOP853's -- is not counted), and the device row pitch (in doubles) of one
+ * species row */
 int64_t pnp_device_bytes(const pnp_handle* h);
 int32_t pnp_row_pitch(const pnp_handle* h);
 

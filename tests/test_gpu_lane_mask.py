@@ -297,6 +297,58 @@ def test_scf_cycle_keeps_the_callers_mask():
     assert (it1[on] > 0).all()
 
 
+def test_scf_cycle_leaves_the_wall_kinetics_in_the_jacobian():
+    """pnp_scf_cycle's transport solves take the wall kinetics as prescribed fluxes; that holds for the call alone.  The step after
+    it equals, to the bit, the step of a fresh handle given the same state, flux and kinetics: a switch that outlived the call would
+    drop the kinetics from the Jacobian and change the iterates."""
+    N, nx, B = 3, 64, 6
+    case = Case(N, nx, B, 47, {}, {})
+    k = np.linspace(1e-5, 5e-5, B)[:, None]
+
+    def step_once(s):
+        s.step(1)
+        return s.get_state()[:2] + (s.get_status(), s.newton_iterations())
+    with case.solver() as s:
+        s.set_wall_kinetics([2], [[0.0, 0.0, -1.0]], k)
+        assert (s.solve_stationary() == 0).all()
+        cs, vs, es = s.get_surface()
+        state = {'surface_concentration': cs.copy(), 'surface_concentration_old': cs.copy(), 'flux': np.zeros((B, N)),
+                 'current_density_old': np.zeros((B, N)), 'mix': np.full(B, 0.5), 'accuracy': np.full(B, np.inf),
+                 'surface_pH': np.full(B, 7.0), 'surface_potential': vs, 'surface_efield': es,
+                 'step_to_check': np.full(B, 1), 'active': np.ones(B, np.int32), 'failed': np.zeros(B, np.int32)}
+        s.scf_cycle(state, istep=1, max_iter=4, tau_scf=1e-12, faraday=F)
+        c0, phi0 = (a.copy() for a in s.get_state()[:2])
+        flux = state['flux'].copy()
+        after = step_once(s)
+    assert np.abs(flux).max() > 0.0 and (after[3] > 0).all()
+    with case.solver() as s:
+        s.set_batch(c0, case.pb, np.zeros(B), flux)
+        s.set_potential(phi0)
+        s.set_wall_kinetics([2], [[0.0, 0.0, -1.0]], k)
+        fresh = step_once(s)
+    for a, b in zip(after, fresh):
+        assert np.array_equal(a, b)
+
+
+def test_a_rejected_call_leaves_nothing_behind():
+    """A call the library rejects before any launch -- pnp_solve_surface with nsteps = -1, under a mask set for it -- in the middle of a
+    BDF2 trajectory of the lane-pair kernel: once the mask is lifted, the steps after it end where step(2); step(2) ends, to the bit."""
+    N, nx, B, options = FAMILIES['lane2']
+    case = Case(N, nx, B, 5 + N, options, newton_kw('bdf2', N))
+    with case.solver() as s:
+        s.step(2)
+        s.set_lane_mask(masks(B, 'third-off'))
+        with pytest.raises(_capi.PnpError) as rejected:
+            s.solve_surface(nsteps=-1)
+        assert rejected.value.code == -1                # PNP_EINVAL
+        s.set_lane_mask(None)
+        s.step(2)
+        got = s.get_state()[:2] + (s.get_status(), s.newton_iterations())
+    rc, rphi, rafter = case.run([(2, None), (2, None)])
+    for a, b in zip(got, (rc, rphi) + rafter[-1]):
+        assert np.array_equal(a, b)
+
+
 @pytest.mark.parametrize("mask_during_tune", [True, False])
 def test_autotune_under_a_mask_leaves_history_counters_and_mask_alone(mask_during_tune, monkeypatch):
     """BDF2 with a mask on the first call: the masked-in lanes have a history, the others none.  pnp_autotune (every family's trials,
