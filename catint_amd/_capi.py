@@ -199,6 +199,25 @@ def _f64(a, shape=None):
     return a
 
 
+def flatten_reactions(reactions):
+    """[(lhs indices, rhs indices, kf, kr)] -> (n, n_lhs, lhs, n_rhs, rhs, kf, kr), the arrays of pnp_set_reactions (and of
+    catbal_params).  A side longer than PNP_MAX_REACTANTS keeps its length in n_lhs / n_rhs and its first entries in lhs / rhs:
+    the callee rejects it."""
+    n = len(reactions)
+    n_lhs = np.zeros(max(n, 1), np.int32)
+    n_rhs = np.zeros(max(n, 1), np.int32)
+    lhs = np.zeros((max(n, 1), PNP_MAX_REACTANTS), np.int32)
+    rhs = np.zeros((max(n, 1), PNP_MAX_REACTANTS), np.int32)
+    kf = np.zeros(max(n, 1))
+    kr = np.zeros(max(n, 1))
+    for r, (l, rr, f, b) in enumerate(reactions):
+        n_lhs[r], n_rhs[r] = len(l), len(rr)
+        lhs[r, :min(len(l), PNP_MAX_REACTANTS)] = list(l)[:PNP_MAX_REACTANTS]
+        rhs[r, :min(len(rr), PNP_MAX_REACTANTS)] = list(rr)[:PNP_MAX_REACTANTS]
+        kf[r], kr[r] = f, b
+    return n, n_lhs, lhs, n_rhs, rhs, kf, kr
+
+
 class PnpSolver(object):
     """Thin object wrapper over one ``pnp_handle`` (one GPU)."""
 
@@ -222,8 +241,12 @@ class PnpSolver(object):
         self._check(self._lib.pnp_set_species(self._h, _dptr(_f64(D, (self.N,))), _dptr(_f64(charges, (self.N,)))))
         # what get_electrolyte hands to the observables library: the problem as this solver was given it
         self._obs = {'D': np.array(D, float), 'charges': np.array(charges, float), 'beta': float(beta), 'x': np.arange(self.nx) * float(dx),
-                     'mpb_radius': None, 'velocity': 0.0, 'device': int(device)}
+                     'mpb_radius': None, 'velocity': 0.0, 'device': int(device),
+                     # ... and what get_balance hands to the balance library on top of that (recording only)
+                     'reactions': [], 'wall': None, 'flux': None, 'phiM': None, 'flux_stale': False, 'wall_stale': False,
+                     'explicit_kinetics': False}
         self._observer = None
+        self._balancer = None
 
     def _check(self, rc):
         if rc != 0:
@@ -233,6 +256,9 @@ class PnpSolver(object):
         if getattr(self, '_observer', None) is not None:
             self._observer.close()
             self._observer = None
+        if getattr(self, '_balancer', None) is not None:
+            self._balancer.close()
+            self._balancer = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -252,22 +278,13 @@ class PnpSolver(object):
     # -- parameters ------------------------------------------------------------------------
     def set_reactions(self, reactions):
         """reactions: list of (lhs_indices, rhs_indices, kf, kr) in the reference's dict order."""
-        n = len(reactions)
-        n_lhs = np.zeros(max(n, 1), np.int32)
-        n_rhs = np.zeros(max(n, 1), np.int32)
-        lhs = np.zeros((max(n, 1), PNP_MAX_REACTANTS), np.int32)
-        rhs = np.zeros((max(n, 1), PNP_MAX_REACTANTS), np.int32)
-        kf = np.zeros(max(n, 1))
-        kr = np.zeros(max(n, 1))
         for r, (l, rr, f, b) in enumerate(reactions):
             if len(l) > PNP_MAX_REACTANTS or len(rr) > PNP_MAX_REACTANTS:
                 raise PnpError(-1, 'too many reactants in reaction %d' % r)
-            n_lhs[r], n_rhs[r] = len(l), len(rr)
-            lhs[r, :len(l)] = l
-            rhs[r, :len(rr)] = rr
-            kf[r], kr[r] = f, b
+        n, n_lhs, lhs, n_rhs, rhs, kf, kr = flatten_reactions(reactions)
         self._check(self._lib.pnp_set_reactions(self._h, n, _iptr(n_lhs), _iptr(lhs), _iptr(n_rhs), _iptr(rhs),
                                                 _dptr(kf), _dptr(kr)))
+        self._obs['reactions'] = [(list(l), list(rr), float(f), float(b)) for (l, rr, f, b) in reactions]
 
     def set_batch(self, c0, pb, vzeta, flux):
         c0 = np.ascontiguousarray(c0, dtype=np.float64)
@@ -277,13 +294,20 @@ class PnpSolver(object):
         self._check(self._lib.pnp_set_batch(self._h, B, _dptr(c0), _dptr(pb), _dptr(_f64(vzeta, (B,))),
                                             _dptr(_f64(flux, (B, self.N)))))
         self.B = B
+        self._obs.update(flux=np.array(_f64(flux, (B, self.N))), phiM=pb[:, 0].copy(), flux_stale=False, explicit_kinetics=False)
+        # pnp_set_batch keeps the handle's wall table, but its rate constants are per lane of the batch they were set for: with another
+        # batch size the recorded ones no longer say what the solver applies (get_balance refuses until set_wall_kinetics is called)
+        if self._obs['wall'] is not None and len(self._obs['wall']['k']) != B:
+            self._obs['wall_stale'] = True
 
     def set_flux(self, flux):
         self._check(self._lib.pnp_set_flux(self._h, _dptr(_f64(flux, (self.B, self.N)))))
+        self._obs.update(flux=np.array(_f64(flux, (self.B, self.N))), flux_stale=False)
 
     def set_pb(self, pb, vzeta):
         pb = np.nan_to_num(_f64(pb, (self.B, 4)), nan=0.0)
         self._check(self._lib.pnp_set_pb(self._h, _dptr(pb), _dptr(_f64(vzeta, (self.B,)))))
+        self._obs['phiM'] = pb[:, 0].copy()
 
     # -- physical mode ---------------------------------------------------------------------
     def set_newton(self, wall_bc='dirichlet', stern_capacitance=0.0, phi_pzc=0.0, tol=1e-10, maxit=50, dphi_max=0.05,
@@ -351,6 +375,7 @@ class PnpSolver(object):
         n = len(species)
         if n == 0:
             self._check(self._lib.pnp_set_wall_kinetics(self._h, 0, None, None, None))
+            self._obs.update(wall=None, wall_stale=False)
             return
         sp = np.ascontiguousarray(species, dtype=np.int32)
         self._check(self._lib.pnp_set_wall_kinetics(self._h, n, _iptr(sp), _dptr(_f64(nu, (n, self.N))),
@@ -359,10 +384,15 @@ class PnpSolver(object):
             al = _f64(np.zeros(n) if alpha is None else alpha, (n,))
             ks = _f64(np.zeros(n) if saturation is None else saturation, (n,))
             self._check(self._lib.pnp_set_wall_rate_law(self._h, n, _dptr(al), _dptr(ks)))
+        self._obs['wall'] = {'species': sp.copy(), 'nu': np.array(_f64(nu, (n, self.N))), 'k': np.array(_f64(k, (self.B, n))),
+                             'alpha': None if alpha is None and saturation is None else al.copy(),
+                             'saturation': None if alpha is None and saturation is None else ks.copy()}
+        self._obs['wall_stale'] = False
 
     def solve_stationary(self, tol=0.0, maxit=0):
         st = np.zeros(self.B, np.int32)
         self._check(self._lib.pnp_solve_stationary(self._h, float(tol), int(maxit), _iptr(st)))
+        self._obs['explicit_kinetics'] = False
         return st
 
     def solve_surface(self, flux=None, nsteps=0):
@@ -371,6 +401,9 @@ class PnpSolver(object):
         cs = np.zeros((self.B, self.N)); vs = np.zeros(self.B); es = np.zeros(self.B); st = np.zeros(self.B, np.int32)
         f = None if flux is None else _f64(flux, (self.B, self.N))
         self._check(self._lib.pnp_solve_surface(self._h, _dptr(f), int(nsteps), _dptr(cs), _dptr(vs), _dptr(es), _iptr(st)))
+        self._obs['explicit_kinetics'] = False
+        if f is not None:
+            self._obs.update(flux=np.array(f), flux_stale=False)
         return cs, vs, es, st
 
     def scf_cycle(self, state, istep, max_iter, tau_scf, faraday, nel=None, nprod=None, species_H=-1, species_OH=-1,
@@ -396,6 +429,10 @@ class PnpSolver(object):
         nprod = None if nprod is None else _f64(nprod, (N,))
         it = C.c_int32(0)
         self._check(self._lib.pnp_scf_cycle(self._h, C.byref(p), _dptr(nel), _dptr(nprod), C.byref(st), C.byref(it)))
+        # the loop updated the wall fluxes on the device: the recorded table is no longer theirs.  And its solves took the wall reactions
+        # through those fluxes (explicitly, from the mixed surface state), not through the wall table: the state it leaves conserves
+        # state['flux'] alone
+        self._obs.update(flux_stale=True, explicit_kinetics=True)
         return int(it.value)
 
     def newton_iterations(self):
@@ -426,6 +463,7 @@ class PnpSolver(object):
     # -- hot path --------------------------------------------------------------------------
     def step(self, nsteps=1, steps_per_launch=0):
         self._check(self._lib.pnp_step(self._h, int(nsteps), int(steps_per_launch)))
+        self._obs['explicit_kinetics'] = False
 
     def integrate(self, nt, itout):
         """Reference loop + outputs: returns (cout[n_out, B, N*nx], status[B])."""
@@ -528,6 +566,36 @@ class PnpSolver(object):
         return self._observer.electrolyte(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], mpb_radius=o['mpb_radius'],
                                           velocity=o['velocity'], species_H=species_H, species_OH=species_OH, fields=names,
                                           scalars=scalars, max_waves=max_waves)
+
+    def get_balance(self, fields=None, scalars=True, flux=None, phiM=None, max_waves=0):
+        """The per-species picture of the physical mode derived on the device (include/catint_balance.h): a dict of the rows named in
+        `fields` (catint_amd._balance.FIELDS: 'flux' [B][N][nx-1], 'reaction_rate' [B][R][nx], 'source' [B][N][nx], 'wall_rate' [B][n_wall],
+        'wall_flux' [B][N], 'imbalance' [B][N][nx]; None: all of them) and, with scalars, 'scalars' [B][N][NSCALARS] (columns:
+        catint_amd._balance.SCALARS).  D, charges, ion radii, grid, velocity, reactions and wall table are the ones this solver was
+        given; flux [B][N] and phiM [B] default to what set_batch / set_flux / set_pb / solve_surface(flux=...) were given last.
+        After scf_cycle the wall fluxes live on the device and the recorded ones are stale: pass `flux` = state['flux'] of the loop
+        (ValueError otherwise).  The loop's solves took the wall reactions through that flux, not through the wall table, so until the
+        next solve_stationary / solve_surface / step the balance is formed without the table: 'wall_flux' is the flux passed,
+        'wall_rate' is empty.  After a set_batch with another batch size the recorded rate constants of the wall table are not the
+        ones the handle applies: ValueError until set_wall_kinetics is called again."""
+        from . import _balance
+        o = self._obs
+        wall = None if o['explicit_kinetics'] else o['wall']
+        if wall is not None and o['wall_stale']:
+            raise ValueError('get_balance: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall table '
+                             'whose rate constants were not recorded for this batch: call set_wall_kinetics again')
+        if flux is None:
+            if o['flux_stale']:
+                raise ValueError('get_balance: scf_cycle updated the wall fluxes on the device; pass flux= (state["flux"] of the loop)')
+            flux = o['flux']
+        phiM = o['phiM'] if phiM is None else phiM
+        if flux is None or phiM is None:
+            raise ValueError('get_balance: no batch was set')
+        if self._balancer is None:
+            self._balancer = _balance.Balancer(o['device'])
+        return self._balancer.species(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], flux, phiM, mpb_radius=o['mpb_radius'],
+                                      velocity=o['velocity'], reactions=o['reactions'], wall=wall, fields=fields, scalars=scalars,
+                                      max_waves=max_waves)
 
     def get_status(self):
         st = np.zeros(self.B, np.int32)

@@ -20,6 +20,15 @@ OBSERVE_SOURCES = ['catobs.hip']
 OBSERVE_HEADERS = [os.path.join(CSRC, 'pnp_internal.h'), os.path.join(CSRC, 'pnp_wave.h'), os.path.join(CSRC, 'pnp_math.h'),
                    os.path.join(_HERE, '..', 'include', 'catint_pnp.h'), os.path.join(_HERE, '..', 'include', 'catint_observe.h')]
 
+# third library (include/catint_balance.h): species fluxes, reaction rates and the discrete mass balance of a device-resident state.  The
+# kernel and symbol sets of the other two libraries are pinned by their tests, so it is a library of its own
+BALANCE_DIR = os.path.join(CSRC, 'balance')
+BALANCE_LIB = os.path.join(LIB_DIR, 'libcatint_balance.so')
+BALANCE_SOURCES = ['catbal.hip']
+# (pnp_wave.h includes pnp_internal.h)
+BALANCE_HEADERS = [os.path.join(CSRC, 'pnp_internal.h'), os.path.join(CSRC, 'pnp_wave.h'), os.path.join(CSRC, 'pnp_math.h'),
+                   os.path.join(_HERE, '..', 'include', 'catint_pnp.h'), os.path.join(_HERE, '..', 'include', 'catint_balance.h')]
+
 PARTIAL = os.path.join(LIB_DIR, '.partial')      # left by tools/devbuild.sh: the library holds only one block size
 
 
@@ -91,3 +100,26 @@ def build_observe_library(force=False, verbose=False):
     if r.returncode != 0:
         raise RuntimeError('hipcc failed on the observe library:\n%s%s' % (r.stdout, r.stderr))
     return OBSERVE_LIB
+
+
+def balance_needs_build():
+    if not os.path.exists(BALANCE_LIB):
+        return True
+    t = os.path.getmtime(BALANCE_LIB)
+    deps = [os.path.join(BALANCE_DIR, s) for s in BALANCE_SOURCES] + BALANCE_HEADERS
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_balance_library(force=False, verbose=False):
+    """hipcc --offload-arch=gfx950 of catint_amd/csrc/balance into catint_amd/lib/libcatint_balance.so (one command: the library is one
+    translation unit)"""
+    if not force and not balance_needs_build():
+        return BALANCE_LIB
+    os.makedirs(LIB_DIR, exist_ok=True)
+    cmd = [HIPCC] + FLAGS + [os.path.join(BALANCE_DIR, s) for s in BALANCE_SOURCES] + ['-o', BALANCE_LIB]
+    if verbose:
+        print(' '.join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError('hipcc failed on the balance library:\n%s%s' % (r.stdout, r.stderr))
+    return BALANCE_LIB

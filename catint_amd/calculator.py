@@ -50,7 +50,7 @@ def make_itout(nt, ntout):
 
 class Calculator(object):
     def __init__(self, transport=None, dt=None, tmax=None, ntout=1, calc=None, scale_pb_grid=None, tau_jacobi=1e-7,
-                 tau_scf=5e-5, mix_scf=0.5, mode=None, desc_method='external', device=0, derive_on_device=False):
+                 tau_scf=5e-5, mix_scf=0.5, mode=None, desc_method='external', device=0, derive_on_device=False, balance_on_device=False):
         if transport is None:
             raise CalculatorError('No transport object provided for calculator.')
         self.tp = transport
@@ -61,6 +61,10 @@ class Calculator(object):
         # physical mode: run() fills tp.alldata from quantities derived on the device (PnpSolver.get_electrolyte) instead of on the host
         self.derive_on_device = bool(derive_on_device)
         self.observables = None           # [B][NSCALARS] of the last device-derived run(), ready for parallel.gather_observables
+        # physical mode, opt-in: run() also derives species fluxes, reaction rates, wall fluxes and the mass balance on the device
+        # (PnpSolver.get_balance, include/catint_balance.h) and adds them to tp.alldata
+        self.balance_on_device = bool(balance_on_device)
+        self.balance = None               # the dict of get_balance of the last such run()
         if calc is None:
             calc = self.tp.calc
         if calc is None:
@@ -83,6 +87,8 @@ class Calculator(object):
             raise CalculatorError("calculator '%s' is not part of the MI355X transport path "
                                   "(supported: %s)" % (self.calc, ', '.join(GPU_CALCS + MOL_CALCS + PHYSICAL_CALCS)))
         self.physical = self.calc in PHYSICAL_CALCS
+        if self.balance_on_device and not self.physical:
+            raise CalculatorError('balance_on_device is part of the physical mode (calc="comsol")')
         # roughness factor: every wall flux the COMSOL model prescribes is j_i = RF*flux_factor*flux_i (comsol_model.py:1000, :1134)
         self.RF = float(self.tp.system.get('RF', 1.0)) if self.physical else 1.0
         # the reference hands system['flow rate'] (a number or a COMSOL expression) to the convection velocity tds.cdm1 "u"
@@ -582,18 +588,50 @@ class Calculator(object):
                 self.newton_iterations = s.newton_iterations()
                 if getattr(self, 'surface_kinetics', None):
                     self.kinetic_flux = self.surface_kinetic_fluxes(cfin[:, :, 0], phiM, vsurf=v[:, 0])
+                if self.balance_on_device:
+                    self.balance = s.get_balance()
             cout = cfin.reshape(1, B, tp.nspecies * tp.nx)
             if derived is not None:
                 self.status = status
                 self.observables = derived['scalars']
                 self._alldata_fill(0, self._alldata_from_device(cfin, v, derived, flux, getattr(self, 'kinetic_flux', None)), status)
+                self._alldata_balance()
                 return cout
         else:
             cout, status, (v, g, l) = self.integrate_pnp_batch(c0, pb, vz, flux)
         self.status = status
         kf = getattr(self, 'kinetic_flux', None) if self.physical else None
         self.fill_alldata_batch(cout[-1].reshape(B, tp.nspecies, tp.nx), v, g, l, flux, status, kf)
+        if self.physical:
+            self._alldata_balance()
         return cout
+
+    def _alldata_balance(self):
+        """balance_on_device: the per-species picture of self.balance into tp.alldata -- per species 'flux' [nx-1], 'reaction_source' [nx],
+        'mass_balance_defect'; per point 'reaction_rates' [R][nx]; and the electrode fluxes / current densities from the wall flux the
+        device formed (prescribed plus every wall reaction) instead of the host's surface_kinetic_fluxes."""
+        if not self.balance_on_device or self.balance is None:
+            return
+        from . import _balance
+        tp, bal = self.tp, self.balance
+        names = list(tp.species.keys())
+        ers = getattr(tp, 'electrode_reactions', None) or {}
+        defect = bal['scalars'][:, :, _balance.SCALARS.index('defect')]
+        # (the solver was handed RF * flux and RF * k: tp.alldata carries the fluxes per geometric area without the roughness factor,
+        # as the host path does)
+        jwall = bal['wall_flux'] / self.RF if self.RF not in (0.0, 1.0) else bal['wall_flux']
+        for b in range(len(jwall)):
+            d = tp.alldata[b]
+            for k, sp in enumerate(names):
+                ds = d['species'][sp]
+                ds['flux'] = bal['flux'][b, k]
+                ds['reaction_source'] = bal['source'][b, k]
+                ds['mass_balance_defect'] = float(defect[b, k])
+                ds['electrode_flux'] = float(jwall[b, k])
+                if sp in ers and 'nel' in ers[sp]:
+                    nprod = len([a for a in ers[sp]['reaction'][1] if a == sp])
+                    ds['electrode_current_density'] = float(jwall[b, k]) * ers[sp]['nel'] * unit_F / nprod / 10.
+            d['system']['reaction_rates'] = bal['reaction_rate'][b]
 
     # ------------------------------------------------------------------------------------------
     def fill_alldata(self, i, cfin, v, g, l, flux, status, kinetic_flux=None):

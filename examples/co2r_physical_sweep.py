@@ -56,11 +56,14 @@ def main():
     ap.add_argument('--scf-device', action='store_true', help='also run the SCF outer loop on the device (pnp_scf_cycle)')
     ap.add_argument('--device-observables', action='store_true',
                     help='derive field, pH, conductivity, current density and potential drops on the device (Calculator(derive_on_device=True))')
+    ap.add_argument('--balance', action='store_true',
+                    help='derive species fluxes, reaction rates, wall fluxes and the mass balance on the device (Calculator(balance_on_device=True)): '
+                         'prints the partial current density of every wall reaction at three voltages and the worst relative imbalance')
     a = ap.parse_args()
     tp, phis = build(a.lanes, a.nx)
     rate = tafel_rate(tp)
     kin = [{'species': 'CO2', 'rate': rate, 'stoichiometry': {'CO2': -1.0, 'CO': 1.0, 'OH-': 2.0}}]
-    calc = Calculator(transport=tp, calc='comsol', derive_on_device=a.device_observables)
+    calc = Calculator(transport=tp, calc='comsol', derive_on_device=a.device_observables, balance_on_device=a.balance)
     tp.newton = {'tol': 1e-8, 'maxit': 80}
     calc.set_surface_kinetics(kin)
     t0 = time.time()
@@ -85,6 +88,19 @@ def main():
         from catint_amd._observe import SCALARS
         print('device observables [%d x %d]: %s' % (calc.observables.shape + (', '.join(SCALARS),)))
         print('  first / last operating point: %s / %s' % (np.array2string(calc.observables[0], precision=4), np.array2string(calc.observables[-1], precision=4)))
+    if a.balance:                 # catint_amd._balance: rows and scalars as the device left them
+        from catint_amd._balance import SCALARS as BAL
+        bal = calc.balance
+        nel = {'CO': 2.0}         # electrons per product molecule of a wall reaction (the table above: CO2 + H2O + 2 e- -> CO + 2 OH-)
+        print('partial current densities from the wall-reaction rates the device formed [mA/cm2]:')
+        for r, rx in enumerate(kin):
+            product = [sp for sp, nu in rx['stoichiometry'].items() if nu > 0 and sp in nel][0]
+            for i in (0, a.lanes // 2, a.lanes - 1):
+                print('  wall reaction %d (-> %s)   phiM = %7.3f V   j = %12.5f' % (r, product, phis[i], bal['wall_rate'][i, r] / calc.RF * nel[product] * unit_F / 10.0))
+        rel = bal['scalars'][:, :, BAL.index('max_imbalance_rel')]
+        b, k = np.unravel_index(np.nanargmax(rel), rel.shape)
+        print('worst MAX_IMBALANCE_REL of the sweep: %.3e (%s at phiM = %.3f V); largest |mass balance defect|: %.3e mol/(m2 s)'
+              % (rel[b, k], names[k], phis[b], np.abs(bal['scalars'][:, :, BAL.index('defect')]).max()))
     if a.scf_device:
         tp3, _ = build(a.lanes, a.nx)
         tp3.newton = tp.newton
