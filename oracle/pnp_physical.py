@@ -40,6 +40,8 @@ from scipy.linalg import solve_banded
 N_AVOGADRO = 6.022140857e23      # catint/units.py (unit_NA)
 FREE_MIN = 1e-12                 # floor of the free volume fraction 1-phi0 the damped update can reach
 SERIES_U = 0.05                  # |u| below which B(u) and B'(u) use their Taylor series
+# what newton_step counts into its `branches` dictionary: the four data-dependent branches of the damped update and the exit taken
+BRANCH_KEYS = ('damped', 'floor', 'free_volume', 'free_min', 'tol', 'estimate', 'rounding_floor', 'maxit')
 
 
 class PhysicalProblem(object):
@@ -302,7 +304,7 @@ def at_rounding_floor(upd, upd_prev, tol):
 
 
 def newton_step(p, c, phi, c_old, dt, tol=1e-10, maxit=50, dphi_max=0.05, solver=solve_block_tridiagonal,
-                verbose=False, estimate=False, jacobian_once=False):
+                verbose=False, estimate=False, jacobian_once=False, branches=None):
     """Solve one backward-Euler step (or, with dt=inf, the stationary problem) by damped Newton.
     Damping (identical on the device): the whole update is scaled so that |d phi| <= dphi_max, a concentration
     never drops below 10 % of its previous iterate, and neither does the free volume fraction 1-phi0 (MPB).
@@ -311,12 +313,23 @@ def newton_step(p, c, phi, c_old, dt, tol=1e-10, maxit=50, dphi_max=0.05, solver
     jacobian_once=True: the Jacobian of the first iterate serves every iteration of the step (the chord iteration COMSOL is told
     to run, comsol_model.py:526,530 jtech "once") -- a measuring option of the oracle only (tools/probe/jacobian_once_oracle.py: how many
     iterations the chord needs on the bench workloads); the library factorises every iteration.
+    branches: a dictionary that receives (added to what it holds) the number of iterations in which each data-dependent branch fired --
+    'damped' (the dphi_max scaling), 'floor' (a concentration held at a tenth of its iterate), 'free_volume' (the free-volume backtrack),
+    'free_min' (the backtrack with 0.1 free < FREE_MIN) -- and the exit taken: 'tol', 'estimate', 'rounding_floor' or 'maxit'.  Counting
+    changes no arithmetic (tests/test_physical_oracle.py).
     Returns (c, phi, iterations, history of update norms); iterations = maxit+1 if not converged."""
     c = c.copy(); phi = phi.copy()
     N = p.N
     vt = 1.0 / (p.beta * max(np.abs(p.q).max(), 1.0))            # thermal voltage of the highest valence
     hist = []
     upd_prev = np.inf
+    if branches is not None:
+        for key in BRANCH_KEYS:
+            branches.setdefault(key, 0)
+
+    def count(key):
+        if branches is not None:
+            branches[key] += 1
     for it in range(1, maxit + 1):
         if jacobian_once and it > 1:
             F = residual(p, c, phi, c_old, dt)
@@ -332,8 +345,11 @@ def newton_step(p, c, phi, c_old, dt, tol=1e-10, maxit=50, dphi_max=0.05, solver
             m = np.abs(du[N]).max()
             if m > dphi_max:
                 lam = dphi_max / m
+                count('damped')
         c_prev = c
         cn = c + lam * du[:N]
+        if branches is not None and np.any(cn < 0.1 * c):
+            count('floor')
         cn = np.where(cn < 0.1 * c, 0.1 * c, cn)
         if p.mpb:                                              # same rule for the free volume fraction 1-phi0
             phi0_old = (p.vol[:, None] * c).sum(axis=0)
@@ -342,6 +358,9 @@ def newton_step(p, c, phi, c_old, dt, tol=1e-10, maxit=50, dphi_max=0.05, solver
             target = np.maximum(0.1 * free, FREE_MIN)
             over = (1.0 - phi0_new) < target
             if np.any(over):
+                count('free_volume')
+                if np.any(over & (0.1 * free < FREE_MIN)):
+                    count('free_min')
                 theta = np.where(over, (free - target) / np.where(over, phi0_new - phi0_old, 1.0), 1.0)
                 cn = c + theta[None, :] * (cn - c)
         c = cn
@@ -354,41 +373,56 @@ def newton_step(p, c, phi, c_old, dt, tol=1e-10, maxit=50, dphi_max=0.05, solver
             # estimate=True: also accept when two consecutive undamped iterations contract and the quadratic estimate
             # upd^2/upd_prev of the error of the state just computed is below tol
             if upd < tol or (estimate and np.isfinite(upd_prev) and upd < 0.1 * upd_prev and upd * (upd / upd_prev) < tol):
+                count('tol' if upd < tol else 'estimate')
                 return c, phi, it, hist
             if at_rounding_floor(upd, upd_prev, tol):
+                count('rounding_floor')
                 return c, phi, it, hist
             upd_prev = upd
         else:
             upd_prev = np.inf
+    count('maxit')
     return c, phi, maxit + 1, hist
 
 
-def integrate(p, c0, phi0, dt, nsteps, bdf2=False, predictor=False, **kw):
+def integrate(p, c0, phi0, dt, nsteps, bdf2=False, predictor=False, branches=None, **kw):
     """nsteps implicit timesteps.  Backward Euler, or (bdf2=True) the second-order backward differentiation formula the reference's
     transient study asks COMSOL for (comsol_model.py:518-531: BDF, maxorder 2): (3 c_n+1 - 4 c_n + c_n-1) / (2 dt) -- a backward-Euler
     step of length dt / 1.5 against the combination c* = (4 c_n - c_n-1) / 3; the first step is backward Euler.
     predictor=True: from the second step on Newton starts from the linear extrapolation 2 u_n - u_n-1 (concentrations not below a tenth
     of their value; a point whose extrapolated ions would fill more than 90 % of the volume keeps u_n) -- step_prepare_kernel in
-    catint_amd/csrc/pnp_capi.hip."""
+    catint_amd/csrc/pnp_capi.hip.
+    branches: as for newton_step, summed over the steps; also, per step, 'pred_floor' and 'pred_keep': the number of points at which the
+    predictor held a concentration at a tenth and at which it kept u_n (0 on a step without a predictor)."""
     c, phi = c0.copy(), phi0.copy()
+    if branches is not None:
+        branches['pred_floor'], branches['pred_keep'] = [], []
+        kw = dict(kw, branches=branches)
     c_prev = phi_prev = None
     its = []
     for _ in range(nsteps):
         if (bdf2 or predictor) and c_prev is not None:
             c_old = (4.0 * c - c_prev) / 3.0 if bdf2 else c
             cs, ps = c, phi
+            floored = kept = 0
             if predictor:
                 g = 2.0 * c - c_prev
+                floored = int(np.any(g < 0.1 * c, axis=0).sum())
                 g = np.where(g < 0.1 * c, 0.1 * c, g)
                 fill = (p.vol[:, None] * g).sum(axis=0) if p.mpb else np.zeros(c.shape[1])
                 ext = fill < 0.9
+                kept = int((~ext).sum())
                 cs = np.where(ext[None, :], g, c)
                 ps = np.where(ext, 2.0 * phi - phi_prev, phi)
             c_prev, phi_prev = c, phi
             c, phi, it, _ = newton_step(p, cs, ps, c_old, dt / 1.5 if bdf2 else dt, **kw)
         else:
+            floored = kept = 0
             c_prev, phi_prev = c, phi
             c, phi, it, _ = newton_step(p, c, phi, c, dt, **kw)
+        if branches is not None:
+            branches['pred_floor'].append(floored)
+            branches['pred_keep'].append(kept)
         its.append(it)
     return c, phi, its
 

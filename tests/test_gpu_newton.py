@@ -46,10 +46,48 @@ def make_lanes(N, nx, B, seed, phi_lo=-0.15, phi_hi=0.15, points_per_debye=6.0, 
     return D, q, cb, dx, phiM
 
 
+def run_oracle(N, nx, B, seed, dt=None, nsteps=1, stationary=True, newton_kw=None, flux=None, reactions=None, wall_kinetics=None, x=None,
+               velocity=0.0, lanes=None, solver=None, branches=None, **lane_kw):
+    """The oracle's side of run_both (no device): (c, phi, iterations) of the lanes in their order.  solver: the oracle's linear solver
+    (None: its default); branches: a list that receives one dictionary of branch counters per lane (oracle/pnp_physical.py)."""
+    newton_kw = dict(newton_kw or {})
+    D, q, cb, dx, phiM = make_lanes(N, nx, B, seed, **lane_kw)
+    c0 = np.repeat(cb[:, :, None], nx, axis=2)
+    fl = np.zeros((B, N)) if flux is None else flux
+    if x is not None:
+        x = x * dx            # given in units of dx
+    okw = dict(tol=newton_kw.get('tol', 1e-10), maxit=newton_kw.get('maxit', 50), dphi_max=newton_kw.get('dphi_max', 0.05),
+               estimate=bool(newton_kw.get('error_estimate', False)))
+    if okw['dphi_max'] <= 0:
+        okw['dphi_max'] = None
+    if solver is not None:
+        okw['solver'] = solver
+    sel = list(range(B)) if lanes is None else list(lanes)
+    ref_c = np.zeros((len(sel), N, nx)); ref_phi = np.zeros((len(sel), nx)); ref_it = np.zeros(len(sel), int)
+    for j, b in enumerate(sel):
+        p = PH.PhysicalProblem(D=D, charges=q, beta=BETA, eps=EPS, dx=dx, nx=nx, c_bulk=cb[b], phiM=phiM[b], flux=fl[b],
+                               stern_capacitance=newton_kw.get('stern_capacitance') if newton_kw.get('wall_bc') == 'stern' else None,
+                               phi_pzc=newton_kw.get('phi_pzc', 0.0), mpb_radius=newton_kw.get('mpb_radius'), reactions=reactions,
+                               wall_kinetics=[dict(w, k=w['k'][b]) for w in (wall_kinetics or [])], x=x, velocity=velocity)
+        cc, ph = c0[b].copy(), np.zeros(nx)
+        if branches is not None:
+            branches.append({})
+            okw['branches'] = branches[-1]
+        if stationary:
+            cc, ph, it, _ = PH.newton_step(p, cc, ph, cc, np.inf, **okw)
+            ref_it[j] = it
+        else:
+            cc, ph, its_b = PH.integrate(p, cc, ph, dt, nsteps, bdf2=newton_kw.get('time_order', 1) == 2,
+                                         predictor=bool(newton_kw.get('predictor', False)), **okw)
+            ref_it[j] = sum(its_b)
+        ref_c[j], ref_phi[j] = cc, ph
+    return ref_c, ref_phi, ref_it
+
+
 def run_both(N, nx, B, seed, dt=None, nsteps=1, stationary=True, newton_kw=None, flux=None, reactions=None, wall_kinetics=None, x=None,
-             velocity=0.0, lanes=None, **lane_kw):
+             velocity=0.0, lanes=None, branches=None, **lane_kw):
     """The batch on the GPU and (lanes: a list of operating points; None: all of them) on the oracle: (c, phi, iterations, status) of
-    the whole batch, (c, phi, iterations) of the oracle's lanes in their order."""
+    the whole batch, (c, phi, iterations) of the oracle's lanes in their order (branches: see run_oracle)."""
     newton_kw = dict(newton_kw or {})
     D, q, cb, dx, phiM = make_lanes(N, nx, B, seed, **lane_kw)
     c0 = np.repeat(cb[:, :, None], nx, axis=2)
@@ -59,8 +97,7 @@ def run_both(N, nx, B, seed, dt=None, nsteps=1, stationary=True, newton_kw=None,
     s = _capi.PnpSolver(N, nx, dx, dt if dt else 1.0, BETA, EPS, D, q, method='Newton', pb_mode=_capi.PB_DD, batch_capacity=B)
     s.set_newton(**newton_kw)
     if x is not None:
-        x = x * dx            # given in units of dx
-        s.set_grid(x)
+        s.set_grid(x * dx)    # given in units of dx
     if reactions:
         s.set_reactions([(r['lhs'], r['rhs'], r['kf'], r['kr']) for r in reactions])
     if velocity:
@@ -80,27 +117,10 @@ def run_both(N, nx, B, seed, dt=None, nsteps=1, stationary=True, newton_kw=None,
     c, phi, _, _ = s.get_state()
     its = s.newton_iterations()
     s.close()
-    okw = dict(tol=newton_kw.get('tol', 1e-10), maxit=newton_kw.get('maxit', 50), dphi_max=newton_kw.get('dphi_max', 0.05),
-               estimate=bool(newton_kw.get('error_estimate', False)))
-    if okw['dphi_max'] <= 0:
-        okw['dphi_max'] = None
-    sel = list(range(B)) if lanes is None else list(lanes)
-    ref_c = np.zeros((len(sel),) + c.shape[1:]); ref_phi = np.zeros((len(sel),) + phi.shape[1:]); ref_it = np.zeros(len(sel), int)
-    for j, b in enumerate(sel):
-        p = PH.PhysicalProblem(D=D, charges=q, beta=BETA, eps=EPS, dx=dx, nx=nx, c_bulk=cb[b], phiM=phiM[b], flux=fl[b],
-                               stern_capacitance=newton_kw.get('stern_capacitance') if newton_kw.get('wall_bc') == 'stern' else None,
-                               phi_pzc=newton_kw.get('phi_pzc', 0.0), mpb_radius=newton_kw.get('mpb_radius'), reactions=reactions,
-                               wall_kinetics=[dict(w, k=w['k'][b]) for w in (wall_kinetics or [])], x=x, velocity=velocity)
-        cc, ph = c0[b].copy(), np.zeros(nx)
-        if stationary:
-            cc, ph, it, _ = PH.newton_step(p, cc, ph, cc, np.inf, **okw)
-            ref_it[j] = it
-        else:
-            cc, ph, its_b = PH.integrate(p, cc, ph, dt, nsteps, bdf2=newton_kw.get('time_order', 1) == 2,
-                                         predictor=bool(newton_kw.get('predictor', False)), **okw)
-            ref_it[j] = sum(its_b)
-        ref_c[j], ref_phi[j] = cc, ph
-    return (c, phi, its, st), (ref_c, ref_phi, ref_it)
+    ref = run_oracle(N, nx, B, seed, dt=dt, nsteps=nsteps, stationary=stationary, newton_kw=newton_kw, flux=flux, reactions=reactions,
+                     wall_kinetics=wall_kinetics, x=x, velocity=velocity, lanes=lanes, branches=branches,
+                     **lane_kw)
+    return (c, phi, its, st), ref
 
 
 def run_gpu_only(N, nx, B, seed):

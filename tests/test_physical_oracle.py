@@ -478,3 +478,35 @@ def test_convection_velocity_analytic_profile_and_flux_closure():
     cm = c.copy(); cm[k, i] -= h
     dF = (PH.residual(p, cp, phi, c, np.inf) - PH.residual(p, cm, phi, c, np.inf)) / (2 * h)
     assert np.allclose(dF[:, i], Mb[i, :, k], rtol=1e-6, atol=1e-9) and np.allclose(dF[:, i + 1], Lb[i + 1, :, k], rtol=1e-6, atol=1e-9)
+
+
+def test_branch_counters_change_no_arithmetic():
+    """newton_step / integrate with a `branches` dictionary: states and iteration counts equal, bit for bit, to the run without one -- on
+    a stationary solve and on predictor + BDF2 steps, both driven far enough (crowded steric ions, strong Stern capacitance) for every
+    clip of the damped update to fire, which the counters must show."""
+    from tests.test_gpu_newton import BETA, EPS, make_lanes
+    N, nx = 3, 25
+    D, q, cb, dx, phiM = make_lanes(N, nx, 16, 7, phi_lo=-0.8, phi_hi=0.8, cref=200.0)
+    dt = 100 * 0.3 * (6 * dx) * (nx * dx) / D.max()
+    total = {}
+    for b in range(16):
+        p = PH.PhysicalProblem(D=D, charges=q, beta=BETA, eps=EPS, dx=dx, nx=nx, c_bulk=cb[b], phiM=phiM[b], stern_capacitance=1.0,
+                               mpb_radius=[5.0e-10] * N)
+        c0 = np.repeat(cb[b][:, None], nx, axis=1)
+        plain = PH.newton_step(p, c0, np.zeros(nx), c0, np.inf)
+        br = {}
+        counted = PH.newton_step(p, c0, np.zeros(nx), c0, np.inf, branches=br)
+        assert np.array_equal(plain[0], counted[0]) and np.array_equal(plain[1], counted[1]) and plain[2] == counted[2]
+        assert plain[3] == counted[3]
+        assert set(PH.BRANCH_KEYS) == set(br) and sum(br[k] for k in ('tol', 'estimate', 'rounding_floor', 'maxit')) == 1
+        assert max(br['damped'], br['floor'], br['free_volume']) <= plain[2] and br['free_min'] <= br['free_volume']
+        plain = PH.integrate(p, c0, np.zeros(nx), dt, 3, bdf2=True, predictor=True)
+        bt = {}
+        counted = PH.integrate(p, c0, np.zeros(nx), dt, 3, bdf2=True, predictor=True, branches=bt)
+        assert np.array_equal(plain[0], counted[0]) and np.array_equal(plain[1], counted[1]) and plain[2] == counted[2]
+        assert sum(bt[k] for k in ('tol', 'estimate', 'rounding_floor', 'maxit')) == 3            # one exit per step
+        assert len(bt['pred_floor']) == len(bt['pred_keep']) == 3 and bt['pred_floor'][0] == bt['pred_keep'][0] == 0
+        for k in PH.BRANCH_KEYS:
+            total[k] = total.get(k, 0) + br[k] + bt[k]
+        total['pred_floor'] = total.get('pred_floor', 0) + sum(bt['pred_floor'])
+    assert total['damped'] > 0 and total['floor'] > 0 and total['free_volume'] > 0 and total['pred_floor'] > 0, total
