@@ -6,16 +6,16 @@ import os
 
 import numpy as np
 
+from . import _devlib
 from ._capi import flatten_reactions as reaction_table      # the arrays of pnp_set_reactions: catbal_params takes the same form
-from ._observe import PnpDeviceView  # noqa: F401  (the view is the solver library's struct; one mirror serves both libraries)
+from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CATINT_BALANCE_LIB') or os.path.join(_HERE, 'lib', 'libcatint_balance.so')
 
 # every symbol include/catint_balance.h declares (tests/test_balance_abi.py)
-SYMBOLS = ['catbal_create', 'catbal_destroy', 'catbal_last_error', 'catbal_last_kernel', 'catbal_last_kernel_ms', 'catbal_species']
+SYMBOLS = _devlib.symbols('catbal_', 'species')
 
-EINVAL, ENOMEM, EDEVICE = -1, -2, -3
 MAX_SPECIES, MAX_NX = 8, 4098
 MAX_REACTIONS, MAX_REACTANTS, MAX_WALL_REACTIONS = 16, 4, 8          # PNP_MAX_* of catint_pnp.h
 SCALARS = ('wall_flux', 'bulk_flux', 'source_integral', 'defect', 'max_imbalance_rel', 'inventory')
@@ -50,29 +50,9 @@ _lib = None
 
 def load_library():
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise BalanceError(EDEVICE, 'HIP extension %s is missing: run `python -c "import __graft_entry__ as g; g.build()"`' % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    lib.catbal_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
-    lib.catbal_create.restype = C.c_int
-    lib.catbal_destroy.argtypes = [C.c_void_p]
-    lib.catbal_destroy.restype = None
-    lib.catbal_last_error.argtypes = [C.c_void_p]
-    lib.catbal_last_error.restype = C.c_char_p
-    lib.catbal_last_kernel.argtypes = [C.c_void_p]
-    lib.catbal_last_kernel.restype = C.c_char_p
-    lib.catbal_last_kernel_ms.argtypes = [C.c_void_p]
-    lib.catbal_last_kernel_ms.restype = C.c_float
-    lib.catbal_species.argtypes = [C.c_void_p, C.POINTER(PnpDeviceView), C.POINTER(CatbalParams), C.POINTER(CatbalOutputs)]
-    lib.catbal_species.restype = C.c_int
-    _lib = lib
-    return lib
-
-
-def _dptr(a):
-    return a.ctypes.data_as(_PD) if a is not None else None
+    if _lib is None:
+        _lib = _devlib.load(LIB_PATH, 'catbal_', 'species', CatbalParams, CatbalOutputs, BalanceError)
+    return _lib
 
 
 def _iptr(a):
@@ -83,42 +63,9 @@ def _f64(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
 
 
-class Balancer(object):
+class Balancer(_devlib.Handle):
     """One ``catbal_ctx``.  No device call is made before the first ``species`` that passes validation."""
-
-    def __init__(self, device=0):
-        self._lib = load_library()
-        self._h = C.c_void_p()
-        rc = self._lib.catbal_create(int(device), C.byref(self._h))
-        if rc != 0:
-            self._h = C.c_void_p()
-            raise BalanceError(rc, self._lib.catbal_last_error(None).decode())
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            self._lib.catbal_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def last_kernel(self):
-        return self._lib.catbal_last_kernel(self._h).decode()
-
-    @property
-    def last_kernel_ms(self):
-        """Device time of the last call's kernel alone, without the copies (HIP events), in ms"""
-        return float(self._lib.catbal_last_kernel_ms(self._h))
+    _prefix, _error, _load = 'catbal_', BalanceError, staticmethod(load_library)
 
     def species(self, view, D, charges, x, beta, flux, phiM, mpb_radius=None, velocity=0.0, reactions=(), wall=None, fields=None,
                 scalars=True, max_waves=0, struct_size=None):
@@ -153,7 +100,5 @@ class Balancer(object):
         if scalars:
             out['scalars'] = np.empty((B, N, NSCALARS))
         o = CatbalOutputs(**{n: _dptr(a) for n, a in out.items()})
-        rc = self._lib.catbal_species(self._h, C.byref(view), C.byref(p), C.byref(o))
-        if rc != 0:
-            raise BalanceError(rc, self._lib.catbal_last_error(self._h).decode())
+        self._call('species', view, p, o)
         return out

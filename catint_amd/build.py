@@ -12,22 +12,24 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wall', '-Wno-unused-function']
 
 
+_INCLUDE = os.path.join(_HERE, '..', 'include')
+# what every library that derives quantities from a device-resident state includes (csrc/pnp_post.h); tests/test_build_deps.py follows
+# the #include lines of all three libraries and compares with the lists here
+_POST_HEADERS = [os.path.join(CSRC, h) for h in ('pnp_post.h', 'pnp_wave.h', 'pnp_math.h', 'pnp_internal.h')] + [os.path.join(_INCLUDE, 'catint_pnp.h')]
+
 # second library (include/catint_observe.h): observables derived from a device-resident state.  Its kernels stay out of SOURCES:
 # the solver library holds the solver's kernels and nothing else (tests/test_kernel_census.py)
 OBSERVE_DIR = os.path.join(CSRC, 'observe')
 OBSERVE_LIB = os.path.join(LIB_DIR, 'libcatint_observe.so')
 OBSERVE_SOURCES = ['catobs.hip']
-OBSERVE_HEADERS = [os.path.join(CSRC, 'pnp_internal.h'), os.path.join(CSRC, 'pnp_wave.h'), os.path.join(CSRC, 'pnp_math.h'),
-                   os.path.join(_HERE, '..', 'include', 'catint_pnp.h'), os.path.join(_HERE, '..', 'include', 'catint_observe.h')]
+OBSERVE_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_observe.h')]
 
 # third library (include/catint_balance.h): species fluxes, reaction rates and the discrete mass balance of a device-resident state.  The
 # kernel and symbol sets of the other two libraries are pinned by their tests, so it is a library of its own
 BALANCE_DIR = os.path.join(CSRC, 'balance')
 BALANCE_LIB = os.path.join(LIB_DIR, 'libcatint_balance.so')
 BALANCE_SOURCES = ['catbal.hip']
-# (pnp_wave.h includes pnp_internal.h)
-BALANCE_HEADERS = [os.path.join(CSRC, 'pnp_internal.h'), os.path.join(CSRC, 'pnp_wave.h'), os.path.join(CSRC, 'pnp_math.h'),
-                   os.path.join(_HERE, '..', 'include', 'catint_pnp.h'), os.path.join(_HERE, '..', 'include', 'catint_balance.h')]
+BALANCE_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_balance.h')]
 
 PARTIAL = os.path.join(LIB_DIR, '.partial')      # left by tools/devbuild.sh: the library holds only one block size
 
@@ -79,47 +81,40 @@ def build_library(force=False, verbose=False):
     return LIB
 
 
-def observe_needs_build():
-    if not os.path.exists(OBSERVE_LIB):
+def _unit_needs_build(src_dir, sources, headers, lib):
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(OBSERVE_LIB)
-    deps = [os.path.join(OBSERVE_DIR, s) for s in OBSERVE_SOURCES] + OBSERVE_HEADERS
-    return any(os.path.getmtime(d) > t for d in deps)
+    t = os.path.getmtime(lib)
+    return any(os.path.getmtime(d) > t for d in [os.path.join(src_dir, s) for s in sources] + headers)
+
+
+def _build_unit(src_dir, sources, headers, lib, force, verbose):
+    """One hipcc --offload-arch=gfx950 command from the sources under src_dir to lib (the library is one translation unit)"""
+    if not force and not _unit_needs_build(src_dir, sources, headers, lib):
+        return lib
+    os.makedirs(LIB_DIR, exist_ok=True)
+    cmd = [HIPCC] + FLAGS + [os.path.join(src_dir, s) for s in sources] + ['-o', lib]
+    if verbose:
+        print(' '.join(cmd))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError('hipcc failed on %s:\n%s%s' % (os.path.basename(lib), r.stdout, r.stderr))
+    return lib
+
+
+def observe_needs_build():
+    return _unit_needs_build(OBSERVE_DIR, OBSERVE_SOURCES, OBSERVE_HEADERS, OBSERVE_LIB)
 
 
 def build_observe_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 of catint_amd/csrc/observe into catint_amd/lib/libcatint_observe.so (one command: the library is one
-    translation unit)"""
-    if not force and not observe_needs_build():
-        return OBSERVE_LIB
-    os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [HIPCC] + FLAGS + [os.path.join(OBSERVE_DIR, s) for s in OBSERVE_SOURCES] + ['-o', OBSERVE_LIB]
-    if verbose:
-        print(' '.join(cmd))
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError('hipcc failed on the observe library:\n%s%s' % (r.stdout, r.stderr))
-    return OBSERVE_LIB
+    """catint_amd/csrc/observe into catint_amd/lib/libcatint_observe.so"""
+    return _build_unit(OBSERVE_DIR, OBSERVE_SOURCES, OBSERVE_HEADERS, OBSERVE_LIB, force, verbose)
 
 
 def balance_needs_build():
-    if not os.path.exists(BALANCE_LIB):
-        return True
-    t = os.path.getmtime(BALANCE_LIB)
-    deps = [os.path.join(BALANCE_DIR, s) for s in BALANCE_SOURCES] + BALANCE_HEADERS
-    return any(os.path.getmtime(d) > t for d in deps)
+    return _unit_needs_build(BALANCE_DIR, BALANCE_SOURCES, BALANCE_HEADERS, BALANCE_LIB)
 
 
 def build_balance_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 of catint_amd/csrc/balance into catint_amd/lib/libcatint_balance.so (one command: the library is one
-    translation unit)"""
-    if not force and not balance_needs_build():
-        return BALANCE_LIB
-    os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [HIPCC] + FLAGS + [os.path.join(BALANCE_DIR, s) for s in BALANCE_SOURCES] + ['-o', BALANCE_LIB]
-    if verbose:
-        print(' '.join(cmd))
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError('hipcc failed on the balance library:\n%s%s' % (r.stdout, r.stderr))
-    return BALANCE_LIB
+    """catint_amd/csrc/balance into catint_amd/lib/libcatint_balance.so"""
+    return _build_unit(BALANCE_DIR, BALANCE_SOURCES, BALANCE_HEADERS, BALANCE_LIB, force, verbose)

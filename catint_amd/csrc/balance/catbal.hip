@@ -2,12 +2,9 @@
 // mode derived on the device from the state a pnp_handle holds there.  It shares no code with the Newton kernels (pnp_newton.hip,
 // pnp_lane*.hip): the formulas are restated here from the header's definitions.  gfx950 / MI355X only.
 //
-// Layout: that of catobs::electrolyte_kernel (observe/catobs.hip).  Persistent workgroups walk operating points b, b + grid, ...;
-// thread t of the WY waves of a point owns the P consecutive grid points t P + 1 .. t P + P and holds windows of P + 2 values starting
-// at point t P.  Here every thread evaluates all P + 1 edges of its window (the balance of its last own point needs the edge to its
-// right), and stores the P edges left of its points; when the nx - 2 interior points fill the waves exactly (`tight`) the last thread
-// also stores the bulk point and the last edge.  Rows move through range-checked 16-byte buffer loads and stores whose resource ends
-// at the row's nx-th value.
+// Layout and memory access: csrc/pnp_post.h, shared with observe/catobs.hip.  Persistent workgroups walk operating points b, b + grid,
+// ...  Here every thread evaluates all P + 1 edges of its window (the balance of its last own point needs the edge to its right), and
+// stores the P edges left of its points; when the grid is `tight` the last thread also stores the bulk point and the last edge.
 // Passes per operating point: (0, steric ions only) phi0 -> w, gamma over the window; (A) one reaction at a time: the participants'
 // windows are multiplied and the rate row is written -- to the output row when it was asked for, else to a workspace row of this
 // workgroup -- with the sum of the absolute forward and backward terms next to it when the scalars are wanted; (B) one species at a
@@ -15,25 +12,18 @@
 // per-thread partial sums that wave scans (pnp_wave.h) and, with several waves, a few doubles of LDS turn into the scalars.
 // A thread reads back from the rate rows only the positions it stored itself (its own points; the wall for thread 0; the bulk point
 // for the last thread when tight), so pass B needs no barrier behind pass A.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <string>
+#include <new>
 #include <vector>
 
 #include "../../../include/catint_balance.h"
-#include "../pnp_math.h"
-#include "../pnp_wave.h"
+#include "../pnp_post.h"
 
 namespace catbal {
 
-using pnp::d2;
-using pnp::u4;
-typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+using namespace pnp::post;
 
-constexpr double N_AVOGADRO = 6.022140857e23;   // catint/units.py (unit_NA), as in oracle/pnp_physical.py
 constexpr int MAXS = CATBAL_MAX_SPECIES, MAXR = PNP_MAX_REACTIONS, MAXT = PNP_MAX_REACTANTS, MAXW = PNP_MAX_WALL_REACTIONS;
 
 // the reaction and wall tables of one call, flattened on the host (every index validated there)
@@ -62,67 +52,6 @@ struct KArgs {
   double* ws;            // [blocks][2][nreact][nx]: rate rows (unless `rate` takes them) and the rows of |forward| + |backward|
   double D[MAXS], qb[MAXS], pe[MAXS], vol[MAXS];   // D_k, q_k beta, velocity / D_k, N_A a_k^3
 };
-
-// window of P + 2 doubles starting at element t P of a row
-template <int P>
-__device__ __forceinline__ void load_win(__amdgpu_buffer_rsrc_t r, double (&w)[P + 2], int t) {
-  if constexpr (P == 1) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) w[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, t * 8 + q * 8, 0, 0));
-  } else {
-    pnp::load_window<P>(r, w, t);
-  }
-}
-
-// v[OFF .. OFF + P) to consecutive doubles at byte offset `at`
-template <int P, int OFF, int LEN>
-__device__ __forceinline__ void store_blocked(__amdgpu_buffer_rsrc_t r, const double (&v)[LEN], int at) {
-  if constexpr (P == 1) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v[OFF]), r, at, 0, 0);
-  } else {
-#pragma unroll
-    for (int q = 0; q < P / 2; ++q) {
-      d2 t;
-      t.x = v[OFF + 2 * q];
-      t.y = v[OFF + 2 * q + 1];
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, t), r, at + q * 16, 0, 0);
-    }
-  }
-}
-
-// element `pos` (thread-dependent) of a register array: compares, not an indexed access (which would go to scratch)
-template <int LEN>
-__device__ __forceinline__ double pick(const double (&a)[LEN], int pos) {
-  double v = 0.0;
-#pragma unroll
-  for (int j = 0; j < LEN; ++j) v = (j == pos) ? a[j] : v;
-  return v;
-}
-
-// Row of point values, v[jw] = value at window position jw: own positions 1 .. P by vector stores, the wall by thread 0, the bulk
-// point by the last thread when it has no owner.
-template <int P, int T>
-__device__ __forceinline__ void store_point_row(double* row, const double (&v)[P + 2], int nx, int t, bool tight) {
-  store_blocked<P, 1, P + 2>(pnp::row_rsrc(row, nx), v, (t * P + 1) * 8);
-  if (t == 0) row[0] = v[0];
-  if (tight && t == T - 1) row[nx - 1] = v[P + 1];
-}
-
-// Row of edge values, v[j] = value on edge t P + j
-template <int P, int T>
-__device__ __forceinline__ void store_edge_row(double* row, const double (&v)[P + 1], int nx, int t, bool tight) {
-  store_blocked<P, 0, P + 1>(pnp::row_rsrc(row, nx - 1), v, t * P * 8);
-  if (tight && t == T - 1) row[nx - 2] = v[P];
-}
-
-// B(u) = u / (exp(u) - 1), evaluated as the solver does (oracle/pnp_physical.py: bernoulli, SERIES_U)
-__device__ __forceinline__ double bernoulli(double u) {
-  if (fabs(u) < 0.05) {
-    const double u2 = u * u;
-    return 1.0 - 0.5 * u + u2 * (1.0 / 12.0 + u2 * (-1.0 / 720.0 + u2 * (1.0 / 30240.0)));
-  }
-  return u * pnp::nrcp(pnp::expm1_sc(u));
-}
 
 // the larger of two values that are >= 0 or NaN; a NaN wins
 __device__ __forceinline__ double max_nan(double a, double b) { return (b > a || b != b) ? b : a; }
@@ -372,153 +301,76 @@ __global__ __launch_bounds__(64 * WY) void species_kernel(const KArgs A) {
   }
 }
 
-// (P, WY) of a grid: nx - 2 <= 64 P in one wave up to 1026 points, then 16 points per lane in 2 / 4 waves
-static void choose_shape(int nx, int* P, int* WY) {
-  const int m = nx - 2;
-  *WY = 1;
-  if (m > 2048) *P = 16, *WY = 4;
-  else if (m > 1024) *P = 16, *WY = 2;
-  else
-    for (int p : {1, 2, 4, 8, 16})
-      if (m <= 64 * p) {
-        *P = p;
-        break;
-      }
-}
-
-template <int P, int WY, bool STERIC>
-static void launch_one(const KArgs& a, int blocks, hipStream_t st) {
-  hipLaunchKernelGGL((species_kernel<P, WY, STERIC>), dim3(blocks), dim3(64 * WY), 0, st, a);
-}
-template <bool STERIC>
-static void launch_shape(int P, int WY, const KArgs& a, int blocks, hipStream_t st) {
-  if (WY == 4) launch_one<16, 4, STERIC>(a, blocks, st);
-  else if (WY == 2) launch_one<16, 2, STERIC>(a, blocks, st);
-  else if (P == 1) launch_one<1, 1, STERIC>(a, blocks, st);
-  else if (P == 2) launch_one<2, 1, STERIC>(a, blocks, st);
-  else if (P == 4) launch_one<4, 1, STERIC>(a, blocks, st);
-  else if (P == 8) launch_one<8, 1, STERIC>(a, blocks, st);
-  else launch_one<16, 1, STERIC>(a, blocks, st);
-}
-
 }  // namespace catbal
 
-struct catbal_ctx {
-  int device = 0;
-  double* buf = nullptr;     // device: the call's inputs, the requested output rows, the workspace
-  size_t buf_doubles = 0;
-  std::vector<double> stage; // host: the inputs of the call in flight, one copy
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernel of the last call (catbal_last_kernel_ms)
-  float kernel_ms = -1.0f;
-  std::string err, last_kernel;
+static_assert(CATBAL_OK == pnp::post::OK && CATBAL_EINVAL == pnp::post::ERR_INVAL && CATBAL_ENOMEM == pnp::post::ERR_NOMEM &&
+                  CATBAL_EDEVICE == pnp::post::ERR_DEVICE && CATBAL_MAX_NX == pnp::post::MAX_NX && CATBAL_MAX_SPECIES == pnp::post::MAX_SPECIES,
+              "catint_balance.h and pnp_post.h disagree");
+
+struct catbal_ctx : pnp::post::Ctx {
+  std::vector<double> stage;   // host: the inputs of the call in flight, one copy
 };
-
-static thread_local std::string g_catbal_create_error;
-
-static int catbal_fail(catbal_ctx* ctx, int code, const std::string& msg) {
-  if (ctx) ctx->err = msg;
-  else g_catbal_create_error = msg;
-  return code;
-}
 
 extern "C" {
 
-int catbal_create(int32_t device, catbal_ctx** out) {
-  if (!out) return catbal_fail(nullptr, CATBAL_EINVAL, "catbal_create: null argument");
-  if (device < 0) return catbal_fail(nullptr, CATBAL_EINVAL, "catbal_create: negative device ordinal");
-  catbal_ctx* ctx = new (std::nothrow) catbal_ctx;
-  if (!ctx) return catbal_fail(nullptr, CATBAL_ENOMEM, "catbal_create: out of host memory");
-  ctx->device = device;
-  *out = ctx;
-  return CATBAL_OK;
-}
-
-void catbal_destroy(catbal_ctx* ctx) {
-  if (!ctx) return;
-  if ((ctx->buf || ctx->ev0) && hipSetDevice(ctx->device) == hipSuccess) {
-    if (ctx->buf) (void)hipFree(ctx->buf);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-  }
-  delete ctx;
-}
-
-const char* catbal_last_error(const catbal_ctx* ctx) { return ctx ? ctx->err.c_str() : g_catbal_create_error.c_str(); }
-const char* catbal_last_kernel(const catbal_ctx* ctx) { return ctx ? ctx->last_kernel.c_str() : ""; }
-float catbal_last_kernel_ms(const catbal_ctx* ctx) { return ctx ? ctx->kernel_ms : -1.0f; }
+int catbal_create(int32_t device, catbal_ctx** out) { return pnp::post::create("catbal_create", device, out); }
+void catbal_destroy(catbal_ctx* ctx) { pnp::post::destroy(ctx); }
+const char* catbal_last_error(const catbal_ctx* ctx) { return pnp::post::last_error(ctx); }
+const char* catbal_last_kernel(const catbal_ctx* ctx) { return pnp::post::last_kernel(ctx); }
+float catbal_last_kernel_ms(const catbal_ctx* ctx) { return pnp::post::last_kernel_ms(ctx); }
 
 int catbal_species(catbal_ctx* ctx, const pnp_device_view* view, const catbal_params* p, const catbal_outputs* out) {
   using namespace catbal;
-  if (!ctx) return CATBAL_EINVAL;
-  if (!view || !p || !out) return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: null argument");
-  if (view->struct_size != (int32_t)sizeof(pnp_device_view))
-    return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: pnp_device_view.struct_size does not match this library");
-  if (p->struct_size != (int32_t)sizeof(catbal_params))
-    return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: catbal_params.struct_size does not match this library");
-  if (!view->phi_dev || !view->c_dev)
-    return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: the view has no potential row (only the physical mode keeps the potential in its state)");
+  static const char entry[] = "catbal_species";
+  if (const int rc = check_view(ctx, entry, "catbal_params", view, p, out)) return rc;
   const int N = view->nspecies, nx = view->nx;
   const int64_t B = view->batch;
   char msg[256];
-  if (nx < 3 || nx > CATBAL_MAX_NX) {
-    snprintf(msg, sizeof msg, "catbal_species: nx = %d outside [3, %d]", nx, CATBAL_MAX_NX);
-    return catbal_fail(ctx, CATBAL_EINVAL, msg);
-  }
-  if (N < 1 || N > CATBAL_MAX_SPECIES) {
-    snprintf(msg, sizeof msg, "catbal_species: %d species outside [1, %d]", N, CATBAL_MAX_SPECIES);
-    return catbal_fail(ctx, CATBAL_EINVAL, msg);
-  }
-  if (B < 1 || view->row_pitch < nx) return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: empty batch or a row pitch below nx");
-  if (!p->D || !p->charges || !p->x) return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: D, charges and x are required");
-  for (int i = 1; i < nx; ++i)
-    if (!(p->x[i] > p->x[i - 1])) {
-      snprintf(msg, sizeof msg, "catbal_species: x is not strictly increasing at index %d", i);
-      return catbal_fail(ctx, CATBAL_EINVAL, msg);
-    }
-  if (p->max_waves < 0) return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: negative max_waves");
+  if (p->max_waves < 0) return fail(ctx, CATBAL_EINVAL, "catbal_species: negative max_waves");
   // what the kernel divides by or exponentiates: a zero, negative or non-finite value would fill rows with inf / NaN without an error
+  // (catobs_electrolyte has no such checks)
   if (!(p->beta > 0.0) || !std::isfinite(p->beta) || !std::isfinite(p->velocity))
-    return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: beta must be positive and finite, velocity finite");
+    return fail(ctx, CATBAL_EINVAL, "catbal_species: beta must be positive and finite, velocity finite");
   for (int k = 0; k < N; ++k) {
     const double r = p->mpb_radius ? p->mpb_radius[k] : 0.0;
     if (!(p->D[k] > 0.0) || !std::isfinite(p->D[k]) || !std::isfinite(p->charges[k]) || !(r >= 0.0) || !std::isfinite(r)) {
       snprintf(msg, sizeof msg, "catbal_species: species %d needs D > 0, a finite charge and a radius >= 0 (all finite)", k);
-      return catbal_fail(ctx, CATBAL_EINVAL, msg);
+      return fail(ctx, CATBAL_EINVAL, msg);
     }
   }
   const int R = p->nreactions, W = p->n_wall;
   if (R < 0 || R > PNP_MAX_REACTIONS) {
     snprintf(msg, sizeof msg, "catbal_species: nreactions = %d outside [0, %d]", R, PNP_MAX_REACTIONS);
-    return catbal_fail(ctx, CATBAL_EINVAL, msg);
+    return fail(ctx, CATBAL_EINVAL, msg);
   }
   if (W < 0 || W > PNP_MAX_WALL_REACTIONS) {
     snprintf(msg, sizeof msg, "catbal_species: n_wall = %d outside [0, %d]", W, PNP_MAX_WALL_REACTIONS);
-    return catbal_fail(ctx, CATBAL_EINVAL, msg);
+    return fail(ctx, CATBAL_EINVAL, msg);
   }
   if (R > 0 && (!p->n_lhs || !p->lhs || !p->n_rhs || !p->rhs || !p->kf || !p->kr))
-    return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: nreactions > 0 needs n_lhs, lhs, n_rhs, rhs, kf and kr");
+    return fail(ctx, CATBAL_EINVAL, "catbal_species: nreactions > 0 needs n_lhs, lhs, n_rhs, rhs, kf and kr");
   for (int r = 0; r < R; ++r) {
     if (p->n_lhs[r] < 0 || p->n_lhs[r] > PNP_MAX_REACTANTS || p->n_rhs[r] < 0 || p->n_rhs[r] > PNP_MAX_REACTANTS) {
       snprintf(msg, sizeof msg, "catbal_species: reaction %d has n_lhs / n_rhs outside [0, %d]", r, PNP_MAX_REACTANTS);
-      return catbal_fail(ctx, CATBAL_EINVAL, msg);
+      return fail(ctx, CATBAL_EINVAL, msg);
     }
     for (int side = 0; side < 2; ++side)
       for (int j = 0; j < (side ? p->n_rhs[r] : p->n_lhs[r]); ++j) {
         const int s = (side ? p->rhs : p->lhs)[r * PNP_MAX_REACTANTS + j];
         if (s < 0 || s >= N) {
           snprintf(msg, sizeof msg, "catbal_species: reaction %d names species index %d outside [0, %d)", r, s, N);
-          return catbal_fail(ctx, CATBAL_EINVAL, msg);
+          return fail(ctx, CATBAL_EINVAL, msg);
         }
       }
   }
-  if (W > 0 && !p->k) return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: n_wall > 0 needs the rate constants k");
-  if (W > 0 && (!p->species || !p->nu)) return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: n_wall > 0 needs species and nu");
+  if (W > 0 && !p->k) return fail(ctx, CATBAL_EINVAL, "catbal_species: n_wall > 0 needs the rate constants k");
+  if (W > 0 && (!p->species || !p->nu)) return fail(ctx, CATBAL_EINVAL, "catbal_species: n_wall > 0 needs species and nu");
   for (int r = 0; r < W; ++r)
     if (p->species[r] < -1 || p->species[r] >= N) {
       snprintf(msg, sizeof msg, "catbal_species: wall reaction %d names species index %d outside [-1, %d)", r, p->species[r], N);
-      return catbal_fail(ctx, CATBAL_EINVAL, msg);
+      return fail(ctx, CATBAL_EINVAL, msg);
     }
-  if (!p->flux || !p->phiM) return catbal_fail(ctx, CATBAL_EINVAL, "catbal_species: flux and phiM are required");
+  if (!p->flux || !p->phiM) return fail(ctx, CATBAL_EINVAL, "catbal_species: flux and phiM are required");
 
   KArgs a;
   memset(&a, 0, sizeof a);
@@ -530,7 +382,7 @@ int catbal_species(catbal_ctx* ctx, const pnp_device_view* view, const catbal_pa
     a.qb[k] = p->charges[k] * p->beta;
     a.pe[k] = p->velocity / p->D[k];
     const double r = p->mpb_radius ? p->mpb_radius[k] : 0.0;
-    a.vol[k] = N_AVOGADRO * r * r * r;
+    a.vol[k] = pnp::N_AVOGADRO * r * r * r;
     steric = steric || a.vol[k] != 0.0;
   }
   int P = 1, WY = 1;
@@ -538,17 +390,12 @@ int catbal_species(catbal_ctx* ctx, const pnp_device_view* view, const catbal_pa
   a.tight = (nx - 2 == 64 * P * WY) ? 1 : 0;
 
   // the rows that were asked for (an empty row counts as not asked for)
-  struct Row { double* host; double** dev; size_t n; };
   const size_t np = (size_t)B * N * nx, ne = (size_t)B * N * (nx - 1);
-  Row rows[] = {{out->flux, &a.flux, ne}, {out->reaction_rate, &a.rate, (size_t)B * R * nx}, {out->source, &a.source, np},
-                {out->wall_rate, &a.wall_rate, (size_t)B * W}, {out->wall_flux, &a.wall_flux, (size_t)B * N}, {out->imbalance, &a.imb, np},
-                {out->scalars, &a.scal, (size_t)B * N * CATBAL_NSCALARS}};
-  const auto even = [](size_t n) { return (n + 1) & ~(size_t)1; };
-  bool any = false;
-  size_t need_out = 0;
-  for (const Row& r : rows)
-    if (r.host && r.n) need_out += even(r.n), any = true;
-  if (!any) return CATBAL_OK;
+  const Row rows[] = {{out->flux, &a.flux, ne}, {out->reaction_rate, &a.rate, (size_t)B * R * nx}, {out->source, &a.source, np},
+                      {out->wall_rate, &a.wall_rate, (size_t)B * W}, {out->wall_flux, &a.wall_flux, (size_t)B * N}, {out->imbalance, &a.imb, np},
+                      {out->scalars, &a.scal, (size_t)B * N * CATBAL_NSCALARS}};
+  const size_t need_out = rows_doubles(rows);
+  if (!need_out) return CATBAL_OK;
 
   // persistent grid: 8 waves per CU on 256 CUs unless the caller sizes it; every workgroup walks b, b + grid, ...  A workgroup's rate
   // rows take 2 R nx doubles: the grid shrinks before that workspace passes 128 MiB
@@ -565,7 +412,7 @@ int catbal_species(catbal_ctx* ctx, const pnp_device_view* view, const catbal_pa
   try {
     ctx->stage.assign(n_in, 0.0);
   } catch (const std::bad_alloc&) {
-    return catbal_fail(ctx, CATBAL_ENOMEM, "catbal_species: out of host memory");
+    return fail(ctx, CATBAL_ENOMEM, "catbal_species: out of host memory");
   }
   double* sg = ctx->stage.data();
   memcpy(sg + o_x, p->x, (size_t)nx * 8);
@@ -596,52 +443,19 @@ int catbal_species(catbal_ctx* ctx, const pnp_device_view* view, const catbal_pa
     for (int k = 0; k < N; ++k) tb->nu[r][k] = p->nu[r * N + k];
   }
 
-#define CATBAL_HIP(call)                                                                                            \
-  do {                                                                                                              \
-    hipError_t e_ = (call);                                                                                         \
-    if (e_ != hipSuccess)                                                                                           \
-      return catbal_fail(ctx, e_ == hipErrorOutOfMemory ? CATBAL_ENOMEM : CATBAL_EDEVICE,                           \
-                         std::string("catbal_species: " #call ": ") + hipGetErrorString(e_));                       \
-  } while (0)
-  CATBAL_HIP(hipSetDevice(ctx->device));
+  PNP_POST_HIP(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)view->stream;
-  const size_t need = n_in + need_out + even((size_t)blocks * ws_block);
-  if (need > ctx->buf_doubles) {
-    if (ctx->buf) CATBAL_HIP(hipFree(ctx->buf));
-    ctx->buf = nullptr;
-    ctx->buf_doubles = 0;
-    CATBAL_HIP(hipMalloc((void**)&ctx->buf, need * sizeof(double)));
-    ctx->buf_doubles = need;
-  }
+  if (const int rc = reserve(ctx, entry, n_in + need_out + even((size_t)blocks * ws_block))) return rc;
   a.x = ctx->buf + o_x;
   a.jpre = ctx->buf + o_j;
   a.phiM = ctx->buf + o_p;
   a.kwall = ctx->buf + o_k;
   a.tab = reinterpret_cast<const Table*>(ctx->buf + o_t);
-  double* cur = ctx->buf + n_in;
-  for (const Row& r : rows)
-    if (r.host && r.n) {
-      *r.dev = cur;
-      cur += even(r.n);
-    }
-  a.ws = cur;
-  CATBAL_HIP(hipMemcpyAsync(ctx->buf, sg, n_in * sizeof(double), hipMemcpyHostToDevice, st));
-  if (!ctx->ev0) CATBAL_HIP(hipEventCreate(&ctx->ev0));
-  if (!ctx->ev1) CATBAL_HIP(hipEventCreate(&ctx->ev1));
-  ctx->kernel_ms = -1.0f;
-  CATBAL_HIP(hipEventRecord(ctx->ev0, st));
-  if (steric) launch_shape<true>(P, WY, a, (int)blocks, st);
-  else launch_shape<false>(P, WY, a, (int)blocks, st);
-  CATBAL_HIP(hipGetLastError());
-  CATBAL_HIP(hipEventRecord(ctx->ev1, st));
-  for (const Row& r : rows)
-    if (r.host && r.n) CATBAL_HIP(hipMemcpyAsync(r.host, *r.dev, r.n * sizeof(double), hipMemcpyDeviceToHost, st));
-  CATBAL_HIP(hipStreamSynchronize(st));
-  CATBAL_HIP(hipEventElapsedTime(&ctx->kernel_ms, ctx->ev0, ctx->ev1));
-#undef CATBAL_HIP
-  snprintf(msg, sizeof msg, "catbal::species_kernel<%d, %d, %s>", P, WY, steric ? "true" : "false");
-  ctx->last_kernel = msg;
-  return CATBAL_OK;
+  a.ws = place_rows(rows, ctx->buf + n_in);
+  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, sg, n_in * sizeof(double), hipMemcpyHostToDevice, st));
+  return run(ctx, entry, st, rows, "catbal::species_kernel", P, WY, steric, [&](auto p_, auto wy_, auto steric_) {
+    hipLaunchKernelGGL((species_kernel<p_(), wy_(), steric_()>), dim3((int)blocks), dim3(64 * wy_()), 0, st, a);
+  });
 }
 
 }  // extern "C"

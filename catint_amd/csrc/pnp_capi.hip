@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "pnp_internal.h"
+#include "pnp_math.h"
 #include "pnp_step_table.h"
 
 using namespace pnp;
@@ -1193,7 +1194,7 @@ int pnp_set_newton(pnp_handle* h, const pnp_newton_params* p, const double* mpb_
   for (int k = 0; k < h->a.N; ++k) {
     const double a = mpb_radius ? mpb_radius[k] : 0.0;
     if (!(a >= 0)) return fail(h, PNP_EINVAL, "pnp_set_newton: negative MPB radius");
-    h->volk[k] = 6.022140857e23 * a * a * a;       // unit_NA, catint/units.py
+    h->volk[k] = N_AVOGADRO * a * a * a;
     if (h->volk[k] != 0.0) h->mpb = true;
   }
   return PNP_OK;

@@ -7,6 +7,8 @@
 
 namespace pnp {
 
+constexpr double N_AVOGADRO = 6.022140857e23;   // catint/units.py (unit_NA), as in oracle/pnp_physical.py
+
 __device__ __forceinline__ double nrcp(double x) {   // v_rcp_f64 + two Newton steps (1.1e-16 relative)
   double r = __builtin_amdgcn_rcp(x);
   double e = __builtin_fma(-x, r, 1.0);
