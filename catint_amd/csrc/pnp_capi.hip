@@ -146,6 +146,7 @@ static bool option_assign(Options& o, const char* key_in, const char* value) {
   else if (key == "PNP_ALTERNATE_ROWS") o.pnp_alternate_rows = value[0] ? (iv != 0 ? 1 : 0) : -1;
   else if (key == "PNP_ST_WAVES_PER_CU") o.pnp_st_waves_per_cu = iv;
   else if (key == "PNP_NO_POST_UPLOAD_DISPATCH") o.pnp_no_post_upload_dispatch = iv != 0 || !value[0] ? 1 : 0;
+  else if (key == "PNP_STEP_GENERIC") o.pnp_step_generic = iv != 0 ? 1 : 0;
   else return false;
   return true;
 }
@@ -153,7 +154,7 @@ static bool option_assign(Options& o, const char* key_in, const char* value) {
 static const char* const kOptionKeys[] = {"NEWTON_KERNEL", "NEWTON_EXCHANGE", "NEWTON_TEAM_THREADS", "NEWTON_REGS", "NEWTON_BLOCKS",
                                           "NEWTON_LANE_GROUPS", "NEWTON_SWEEP_BLOCKS", "LANE_PIVOT_LIMIT", "LANE_ORDER", "LANE_STAGGER", "LANE_FUSED", "LANE_RECORDS", "PNP_KERNEL",
                                           "PNP_WAVES_PER_GRID", "PNP_SPECIES_PER_WAVE", "PNP_STEP_STREAMS", "PNP_ALTERNATE_ROWS",
-                                          "PNP_ST_WAVES_PER_CU", "PNP_NO_POST_UPLOAD_DISPATCH"};
+                                          "PNP_ST_WAVES_PER_CU", "PNP_NO_POST_UPLOAD_DISPATCH", "PNP_STEP_GENERIC"};
 
 // the defaults of a new handle: the environment, read once per pnp_create (the only place the library looks at it)
 static Options options_from_environment() {
@@ -355,6 +356,7 @@ int pnp_create(const pnp_config* cfg, pnp_handle** out) {
   a.nsteps = 1;
   a.has_rates = 0;
   a.st_waves_per_cu = h->opt.pnp_st_waves_per_cu;
+  a.step_generic = h->opt.pnp_step_generic;
   a.B = 0;
   a.dx = cfg->dx;
   a.dx2 = cfg->dx * cfg->dx;
@@ -389,6 +391,7 @@ int pnp_set_option(pnp_handle* h, const char* key, const char* value) {
     return fail(h, PNP_ESTATE, "pnp_set_option: NEWTON_SWEEP_BLOCKS after the sweep workspace was allocated");
   h->opt = o;
   h->a.st_waves_per_cu = o.pnp_st_waves_per_cu;
+  h->a.step_generic = o.pnp_step_generic;
   return PNP_OK;
 }
 

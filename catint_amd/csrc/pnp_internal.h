@@ -35,6 +35,7 @@ struct Options {
   int pnp_alternate_rows = -1;       // PNP_ALTERNATE_ROWS = 0 | 1; -1: by the size of the state
   int pnp_st_waves_per_cu = 0;       // PNP_ST_WAVES_PER_CU: resident waves of the streaming kernel
   int pnp_no_post_upload_dispatch = 0;   // PNP_NO_POST_UPLOAD_DISPATCH = 1 (probes)
+  int pnp_step_generic = 0;          // PNP_STEP_GENERIC != 0: step_kernel runs its general body where the fast one applies (tests)
 };
 
 // Per-species constants, computed once on the host with the reference's expression order
@@ -75,6 +76,7 @@ struct DevArgs {
   int32_t st_waves_per_cu;   // streaming kernel: resident waves per CU (Options::pnp_st_waves_per_cu; 0: what fits)
   int32_t reverse;   // streaming kernel: walk the operating points from the last to the first (see pnp_step: alternate launches of one
                      // timestep start on the rows the previous launch wrote last, which the caches still hold)
+  int32_t step_generic;   // step_kernel: keep to the general body (Options::pnp_step_generic)
   int64_t B;
   double dx, dt, beta, eps;
   double dx2, inv2dx, nxm1;   // dx*dx, 1/(2 dx), (double)(nx-1): wave-uniform fp64 values would otherwise live in (spilled) vector registers

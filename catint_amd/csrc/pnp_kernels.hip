@@ -30,8 +30,9 @@ namespace pnp {
 // Poisson for one wave.  LV holds lapl_v by grid index (padded LDS row).  Writes grad_v by grid
 // index into GV (all nx entries incl. the extrapolated ends) and, if VV != nullptr, v into VV.
 // Returns v[1] (needed by the Robin wall condition, calculator_old.py:528-532).
+// DD: the caller has already established A.pb_mode == PNP_PB_DD (step_kernel's fast body), so the other branches are not compiled in.
 // ------------------------------------------------------------------------------------------------
-template <int P, bool WANT_V, int SHIFT>
+template <int P, bool WANT_V, int SHIFT, bool DD = false>
 __device__ __forceinline__ double poisson_wave(const DevArgs& A, double* LV, double* GV, double* VV, double* X,
                                                double vw, double vb, double gw, double gb, int lane) {
   const int nx = A.nx, m = A.m;
@@ -40,7 +41,7 @@ __device__ __forceinline__ double poisson_wave(const DevArgs& A, double* LV, dou
   double vown[P], gown[P];
   double v1;   // v at grid point 1
   if constexpr (!WANT_V && P >= 2) {
-    if (A.pb_mode == PNP_PB_DD) {
+    if (DD || A.pb_mode == PNP_PB_DD) {
       // The timestep kernels' Dirichlet-Dirichlet fast path: step_kernel_rr / step_kernel_st's register arithmetic statement for
       // statement (DPP prefix scans instead of six LDS round trips), so that every kernel family walks the same bits:
       //   w_i = v_{i+1}-v_i = w_0 + H_i,  H_i = sum_{j=1..i} h_j,  h = lapl*dx^2,  G_{nx-1} = sum_r (m - r) h_r,
@@ -231,9 +232,25 @@ constexpr int step_min_waves() {
   return P <= 2 ? 4 : (P == 4 ? (G == 1 ? 4 : 2) : (P == 8 ? (G == 1 ? 3 : 1) : 1));
 }
 
-template <int P, int W, int G>
-__global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(const DevArgs A) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
+// A wave-uniform value pinned to scalar registers, whichever kind of load produced it.
+__device__ __forceinline__ double uniform_f64(double v) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
+// The body of step_kernel: every instance compiles it with FAST = false, the instances of step_has_fast_body() with FAST = true as well.
+//   FAST = false: the general body.  Method, Poisson branch, migration, rate terms and the number of staging rounds are run-time
+//     flags, and every launch constant is read where it is used.
+//   FAST = true: the resident Crank-Nicolson body, for launches with
+//       method == CN && use_mig && pb_mode == PNP_PB_DD && P >= 2 && !has_rates && N <= W*G
+//     (step_kernel tests this once per launch).  The same statements with those flags as compile-time constants, so the expression
+//     trees -- and with them the rounding -- are the general body's.  What it adds: the launch constants (Poisson boundary values,
+//     vzeta, wall flux, bulk value and the species constants of the wave's rows, qe of the staged rows) are read once, before the
+//     time loop, into scalar registers; the rows are staged before the loop, so a fused step issues no vector-memory load; and the
+//     barrier behind the epilogue is dropped (see there).
+template <int P, int W, int G, bool FAST>
+__device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
   constexpr int RB = rowbuf_doubles<P>();
   constexpr int NR = W * G;              // species rows staged per round
   constexpr int V1SLOT = RB - 2;         // v[1] broadcast slot inside GV
@@ -253,9 +270,10 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
   double* lin = A.lapl_a + b * (int64_t)ldx;
   double* lout = A.lapl_b + b * (int64_t)ldx;
   double* crow0 = A.c + b * (int64_t)N * ldx;
-  const bool single_round = (N <= NR);   // every species row stays staged in LDS between fused steps
-  const bool cn = (A.method == PNP_METHOD_CRANK_NICOLSON);
-  double chk = 0.0;                      // NaN/Inf detector: sum of (x - x)
+  const bool single_round = FAST || (N <= NR);   // every species row stays staged in LDS between fused steps
+  const bool cn = FAST || (A.method == PNP_METHOD_CRANK_NICOLSON);
+  const bool use_mig = FAST || A.use_mig;
+  double chk = 0.0;                     // NaN/Inf detector: sum of (x - x)
   double mn = 0.0;                       // most negative concentration seen
   // Every LDS slot is finite from here on: rows of padded unknowns (r >= m) read past the row ends.
   for (int i = tid; i < (2 + NR) * RB; i += 64 * W) lds[i] = 0.0;
@@ -268,30 +286,63 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
   const bool lead_all = W > 1 && wave == 0 && A.B <= 2048;
   if (lead_all) __builtin_amdgcn_s_setprio(3);
 
+  // all global reads of a step's first round go out together
+  auto stage_first_round = [&]() {
+    RowRegs<P> rl, rr[G];
+    if (wave == 0 && use_mig) load_row_issue<P>(row_rsrc(lin, ldx), rl, lane);
+    if (wave * G < N) {
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        load_row_issue<P>(row_rsrc(crow0 + (int64_t)min(wave * G + g, N - 1) * ldx, ldx), rr[g], lane);
+    }
+    if (wave == 0 && use_mig) load_row_commit<P>(rl, LV, lane);
+    if (wave * G < N) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) load_row_commit<P>(rr[g], ROW0 + g * RB, lane);
+    }
+    lds_sync();
+  };
+
+  // Fast body: what a launch cannot change is read here, once.  Wave-uniform, kept in scalar registers.  k_*[g] belong to species
+  // min(wave*G + g, N-1) -- the wave's rows of the single round, a short last group clamped as in the loop below -- and k_qe[w2] to
+  // staged row w2 of the epilogue.  (The general body never touches them.)
+  double k_vw = 0.0, k_vb = 0.0, k_vz = 0.0;
+  double k_f2dx[G], k_cL[G], k_mu[G], k_twoD[G], k_hsr[G], k_e4r[G], k_eer[G], k_omsr[G], k_qe[NR];
+  if constexpr (FAST) {
+    k_vw = uniform_f64(A.pb[b * 4 + 0]);
+    k_vb = uniform_f64(A.pb[b * 4 + 1]);
+    k_vz = uniform_f64(A.vzeta[b]);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int k = min(wave * G + g, N - 1);
+      const SpecConst& S = A.spec[k];
+      k_f2dx[g] = uniform_f64(2 * A.flux[b * N + k] * dx);
+      k_cL[g] = uniform_f64(A.cbulk[b * N + k]);
+      k_mu[g] = uniform_f64(S.mu);
+      k_twoD[g] = uniform_f64(S.twoD);
+      k_hsr[g] = uniform_f64(S.hsr);
+      k_e4r[g] = uniform_f64(S.e4r);
+      k_eer[g] = uniform_f64(S.eer);
+      k_omsr[g] = uniform_f64(S.omsr);
+    }
+#pragma unroll
+    for (int w2 = 0; w2 < NR; ++w2) k_qe[w2] = uniform_f64(A.spec[min(w2, N - 1)].qe);
+    stage_first_round();   // the rows stay in LDS for the whole launch: no step of the loop below loads from global memory
+  }
+
   for (int step = 0; step < A.nsteps; ++step) {
     const bool resident = single_round && step > 0;   // rows (and LV) already in LDS from the last step
     const bool last_step = step + 1 == A.nsteps;
-    // ---- 0. all global reads of the first round go out together ------------------------------------
-    if (!resident) {
-      RowRegs<P> rl, rr[G];
-      if (wave == 0 && A.use_mig) load_row_issue<P>(row_rsrc(lin, ldx), rl, lane);
-      if (wave * G < N) {
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-          load_row_issue<P>(row_rsrc(crow0 + (int64_t)min(wave * G + g, N - 1) * ldx, ldx), rr[g], lane);
-      }
-      if (wave == 0 && A.use_mig) load_row_commit<P>(rl, LV, lane);
-      if (wave * G < N) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) load_row_commit<P>(rr[g], ROW0 + g * RB, lane);
-      }
-      lds_sync();
+    // ---- 0. first-round rows ------------------------------------------------------------------------
+    if constexpr (!FAST) {
+      if (!resident) stage_first_round();
     }
     __builtin_amdgcn_sched_barrier(0);   // keep the staging registers' live range inside the block above
     // ---- 1. lagged potential (wave 0) ------------------------------------------------------------
-    if (A.use_mig) {
+    if (use_mig) {
       if (wave == 0) {
-        const double vw = A.pb[b * 4 + 0], vb = A.pb[b * 4 + 1], gw = A.pb[b * 4 + 2], gb = A.pb[b * 4 + 3];
+        const double vw = FAST ? k_vw : A.pb[b * 4 + 0], vb = FAST ? k_vb : A.pb[b * 4 + 1];
+        const double gw = FAST ? 0.0 : A.pb[b * 4 + 2], gb = FAST ? 0.0 : A.pb[b * 4 + 3];   // (no Dirichlet/Dirichlet use)
         // grad_v[i] is kept in slot i+1 (slot 0 duplicates grad_v[0]) so that every stencil window
         // below is an affine, clamp-free LDS address
         // (the scans use the head of GV as their exchange strip: grad_v of the previous step is dead by now)
@@ -301,7 +352,7 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
         int lane_o = lane;
         asm volatile("" : "+v"(lane_o));
         if (W > 1 && !lead_all) __builtin_amdgcn_s_setprio(3);
-        const double v1w = poisson_wave<P, false, 1>(A, LV, GV, nullptr, GV, vw, vb, gw, gb, lane_o);
+        const double v1w = poisson_wave<P, false, 1, FAST>(A, LV, GV, nullptr, GV, vw, vb, gw, gb, lane_o);
         if (W > 1 && !lead_all) __builtin_amdgcn_s_setprio(0);
         if (lane == 0) {
           GV[V1SLOT] = v1w;
@@ -312,21 +363,21 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
       }
     }
     wg_sync<W>();
-    const double v1 = A.use_mig ? GV[V1SLOT] : 0.0;
-    const double vz = A.vzeta[b];
+    const double v1 = use_mig ? GV[V1SLOT] : 0.0;
+    const double vz = FAST ? k_vz : A.vzeta[b];
 
     d2 accp[IT2];   // next step's charge row at this thread's coalesced positions
 #pragma unroll
     for (int it = 0; it < IT2; ++it) accp[it] = (d2)(0.0);
 
     // ---- 2. species, W*G at a time ------------------------------------------------------------------
-    for (int k0 = 0; k0 < N; k0 += NR) {
+    for (int k0 = 0; k0 < N; k0 = FAST ? N : k0 + NR) {   // (fast body: N <= NR, one round)
       const int kw = k0 + wave * G;          // first species of this wave in this round
       if (kw < N) {
         int kg[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) kg[g] = min(kw + g, N - 1);   // a short last group recomputes species N-1
-        if (k0 > 0) {   // later rounds: the first round's rows were loaded above
+        if (!FAST && k0 > 0) {   // later rounds: the first round's rows were loaded above
           RowRegs<P> rr[G];
 #pragma unroll
           for (int g = 0; g < G; ++g) load_row_issue<P>(row_rsrc(crow0 + (int64_t)kg[g] * ldx, ldx), rr[g], lane);
@@ -340,15 +391,27 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
         for (int g = 0; g < G; ++g) {
           const double* ROW = ROW0 + g * RB;
           const SpecConst& S = A.spec[kg[g]];
-          const double flux = A.flux[b * N + kg[g]];
-          const double cL = A.cbulk[b * N + kg[g]];            // C[k,-1] = C0[(k+1)*nx-1], :540 / :1008
+          const double flux = FAST ? 0.0 : A.flux[b * N + kg[g]];   // (fast body: inside k_f2dx)
+          const double cL = FAST ? k_cL[g] : A.cbulk[b * N + kg[g]];            // C[k,-1] = C0[(k+1)*nx-1], :540 / :1008
           const double c1 = ROW[pidx<P>(1)];
           const double c0old = ROW[pidx<P>(0)];
           const double cLold = ROW[pidx<P>(nx - 1)];
-          const double aa = S.mu * (v1 - vz);
+          double aa;
+          if constexpr (FAST) {
+            // a product of its own, as in the general body's Crank-Nicolson path: that one forms it ahead of the branch on the
+            // method, where it cannot be contracted into the sums below; here there is no such branch and it would be fused
+            // (other last bits)
+#pragma clang fp contract(off)
+            aa = k_mu[g] * (v1 - vz);
+          } else {
+            aa = S.mu * (v1 - vz);
+          }
           if (cn) {   // Robin wall condition :528-532
-            const double rden = fast_rcp2(-S.twoD + aa);
-            c0new[g] = (-S.twoD - aa) * rden * c1 - 2 * flux * dx * rden;
+            // (the general body reads S.twoD inside either branch: read ahead of the branch, the two alternatives are evaluated
+            // together and contracted differently)
+            const double twoD = FAST ? k_twoD[g] : S.twoD;
+            const double rden = fast_rcp2(-twoD + aa);
+            c0new[g] = (-twoD - aa) * rden * c1 - (FAST ? k_f2dx[g] : 2 * flux * dx) * rden;
           } else {    // :1003-1006
             c0new[g] = ((S.twoD + aa) * c1 + flux * 2. * dx) * fast_rcp2(S.twoD - aa);
           }
@@ -384,7 +447,8 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
               const SpecConst& S = A.spec[kg[g]];
               // every row is divided by the constant diagonal 1+s up front: the scaled constants come
               // from the species table, so the unit-diagonal rows cost no extra multiplies
-              const double hsr = S.hsr, e4r = S.e4r, eer = S.eer, omsr = S.omsr;
+              const double hsr = FAST ? k_hsr[g] : S.hsr, e4r = FAST ? k_e4r[g] : S.e4r;
+              const double eer = FAST ? k_eer[g] : S.eer, omsr = FAST ? k_omsr[g] : S.omsr;
               double cc[P + 2], g4[P + 2];
 #pragma unroll
               for (int t = 0; t < P + 2; ++t) cc[t] = ROW[pidx<P>(r0 + t)];
@@ -431,7 +495,9 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
                 Wt -= 0.5;
                 Et -= 0.5;
               }
-              double val = Et * cc[j] + Mf * cc[j + 1] + Wt * cc[j + 2];
+              // The contraction is written out: left to the compiler, which of the three products stays a product of its own
+              // follows the operand order its passes happen to leave, and that changes with the code around this statement.
+              double val = __builtin_fma(Wt, cc[j + 2], __builtin_fma(Mf, cc[j + 1], Et * cc[j]));
               if (A.has_rates) val += A.rates[(b * N + kg[g]) * (int64_t)ldx + min(r0 + j + 1, nx - 1)] * dt;
               x[g][j] = val;
             }
@@ -459,10 +525,9 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
       wg_sync<W>();
       // ---- 3. cooperative epilogue: store the round's rows, fold them into the next charge row ----
       const int nk = min(NR, N - k0);
-      for (int w2 = 0; w2 < nk; ++w2) {
+      auto store_and_fold = [&](int w2, double qe) {
         const double* R2 = ROWS + w2 * RB;
         double* grow = crow0 + (int64_t)(k0 + w2) * ldx;
-        const double qe = A.spec[k0 + w2].qe;
         const __amdgpu_buffer_rsrc_t rs = row_rsrc(grow, ldx);
 #pragma unroll
         for (int it = 0; it < IT2; ++it) {
@@ -483,8 +548,20 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
             mn = fmin(mn, fmin(sx, sy));
           }
         }
+      };
+      if constexpr (FAST) {
+#pragma unroll
+        for (int w2 = 0; w2 < NR; ++w2)
+          if (w2 < nk) store_and_fold(w2, k_qe[w2]);
+      } else {
+        for (int w2 = 0; w2 < nk; ++w2) store_and_fold(w2, A.spec[k0 + w2].qe);
+        // the staged rows are free for the next round's loads
+        wg_sync<W>();
       }
-      wg_sync<W>();
+      // Fast body: no barrier here.  There is no next round, so nothing overwrites the staged rows before the next step, and the
+      // first writes of the next step are already ordered behind every wave's reads: LV was last read in the stencil, before the
+      // barrier in front of this epilogue, and is written only in section 4 below; the rows themselves, and GV, are written next
+      // behind the barrier that ends this step and the one behind the Poisson section of the next.  Three barriers per step.
     }
     // ---- 4. charge row of the new state (lagged by the next step) -------------------------------
     const bool keep = single_round && (step + 1 < A.nsteps);
@@ -531,6 +608,29 @@ __global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(
     atomicOr((unsigned*)&A.status[b], v);
 #endif
   }
+}
+
+// Instances that carry the fast body next to the general one: P >= 2 (the Dirichlet/Dirichlet scan in registers needs two points per
+// lane) and no scratch.  <2,1,3> and <16,1,3> are the two instances whose general body spills (28 and 104 bytes per lane); the fast
+// body would add to that, so they keep to the general body alone.  No other instance uses scratch (profiles/step_fast_isa.md).
+template <int P, int W, int G>
+constexpr bool step_has_fast_body() {
+  return P >= 2 && !(W == 1 && G == 3 && (P == 2 || P == 16));
+}
+
+template <int P, int W, int G>
+__global__ __launch_bounds__(64 * W, (step_min_waves<P, G>())) void step_kernel(const DevArgs A) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  if constexpr (step_has_fast_body<P, W, G>()) {
+    // one wave-uniform decision per launch (kernel arguments only)
+    const bool fast = A.method == PNP_METHOD_CRANK_NICOLSON && A.use_mig && A.pb_mode == PNP_PB_DD && !A.has_rates &&
+                      A.N <= W * G && !A.step_generic;
+    if (fast) {
+      step_body<P, W, G, true>(A, lds);
+      return;
+    }
+  }
+  step_body<P, W, G, false>(A, lds);
 }
 
 // ================================================================================================

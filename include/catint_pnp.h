@@ -96,7 +96,8 @@ const char* pnp_version(void);
  * without its CATINT_ prefix (NEWTON_KERNEL = auto | generic | team | sweep | both | lane | lane2 | lane4 | workgroup, LANE_FUSED, LANE_RECORDS = f64 | f32 (the
  * columns T of the lane kernel's block-Thomas records in single precision: an inexact Newton update, the same converged state),
  * NEWTON_TEAM_THREADS, NEWTON_REGS, NEWTON_BLOCKS, NEWTON_LANE_GROUPS, NEWTON_SWEEP_BLOCKS, LANE_PIVOT_LIMIT, LANE_ORDER, PNP_KERNEL, PNP_WAVES_PER_GRID,
- * PNP_SPECIES_PER_WAVE, PNP_STEP_STREAMS, PNP_ALTERNATE_ROWS, PNP_ST_WAVES_PER_CU, PNP_NO_POST_UPLOAD_DISPATCH).  The environment is
+ * PNP_SPECIES_PER_WAVE, PNP_STEP_STREAMS, PNP_ALTERNATE_ROWS, PNP_ST_WAVES_PER_CU, PNP_NO_POST_UPLOAD_DISPATCH,
+ * PNP_STEP_GENERIC = 1: the LDS-staged step kernel keeps to its general body).  The environment is
  * read once, in pnp_create, as the defaults of the new handle; the library never reads it afterwards, so handles in one process
  * are configured independently.  PNP_EINVAL for an unknown key, PNP_ESTATE for an option that sizes a buffer already allocated.
  * Results do not depend on these switches beyond the documented rounding differences between kernel families. */
