@@ -34,6 +34,7 @@ SYMBOLS = [
     'pnp_get_surface', 'pnp_get_status', 'pnp_synchronize', 'pnp_timer_start', 'pnp_timer_stop',
     'pnp_device_bytes', 'pnp_row_pitch', 'pnp_step_row_chunks', 'pnp_set_newton', 'pnp_solve_stationary', 'pnp_get_newton_iterations',
     'pnp_set_potential', 'pnp_set_convection', 'pnp_set_option', 'pnp_get_lane_order', 'pnp_autotune', 'pnp_autotune_name', 'pnp_autotune_default', 'pnp_tune_placement', 'pnp_set_lanes', 'pnp_set_lane_mask', 'pnp_set_wall_kinetics', 'pnp_set_wall_rate_law', 'pnp_set_grid', 'pnp_solve_surface', 'pnp_scf_cycle', 'pnp_get_device_view',
+    'pnp_set_lanes_device',
 ]
 
 
@@ -134,6 +135,8 @@ def load_library():
     lib.pnp_set_potential.argtypes = [vp, dp]
     lib.pnp_set_lanes.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), dp, dp]
     lib.pnp_set_lanes.restype = C.c_int
+    lib.pnp_set_lanes_device.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+    lib.pnp_set_lanes_device.restype = C.c_int
     lib.pnp_set_lane_mask.argtypes = [vp, ip]
     lib.pnp_set_lane_mask.restype = C.c_int
     lib.pnp_set_wall_kinetics.argtypes = [vp, C.c_int32, ip, dp, dp]
@@ -247,6 +250,7 @@ class PnpSolver(object):
                      'explicit_kinetics': False}
         self._observer = None
         self._balancer = None
+        self._regridder = None
 
     def _check(self, rc):
         if rc != 0:
@@ -259,6 +263,9 @@ class PnpSolver(object):
         if getattr(self, '_balancer', None) is not None:
             self._balancer.close()
             self._balancer = None
+        if getattr(self, '_regridder', None) is not None:
+            self._regridder.close()
+            self._regridder = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -452,6 +459,43 @@ class PnpSolver(object):
         pp = None if phi is None else _f64(phi, (n, self.nx))
         self._check(self._lib.pnp_set_lanes(self._h, n, idx.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(cc), _dptr(pp)))
 
+    def set_lanes_device(self, c_dev, phi_dev=None, n=None, lanes=None):
+        """set_lanes from device memory of this handle's device (pnp_set_lanes_device): c_dev / phi_dev are integer device addresses
+        of [n][N][row_pitch] / [n][row_pitch] rows with this handle's row pitch, e.g. what resample(..., to_host=False) of another
+        handle returned.  lanes None: lanes 0 .. n-1."""
+        idx = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        n = (self.B if idx is None else len(idx)) if n is None else int(n)
+        if idx is not None and len(idx) != n:
+            raise ValueError('set_lanes_device: %d lanes for n = %d' % (len(idx), n))
+        self._check(self._lib.pnp_set_lanes_device(self._h, n, None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   C.c_void_p(c_dev), C.c_void_p(phi_dev)))
+
+    def resample(self, x_target, lanes=None, to_host=True, max_waves=0):
+        """The state of the lanes `lanes` (None: all, in order) resampled on the device onto the grid x_target, with the interpolant the
+        discretisation implies inside a cell (include/catint_regrid.h).  D, charges, ion radii, grid and velocity are the ones this
+        solver was given.  to_host: (c [n][N][nx_target], phi [n][nx_target]); otherwise nothing crosses PCIe and the result is
+        (c_dev, phi_dev), integer device addresses of rows with the pitch of a handle of len(x_target) points, valid until the next
+        resample / resample_to / close of this solver (set_lanes_device of such a handle takes them)."""
+        from . import _regrid
+        if self._regridder is None:
+            self._regridder = _regrid.Regridder(self._obs['device'])
+        o = self._obs
+        out = self._regridder.resample(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], x_target, mpb_radius=o['mpb_radius'],
+                                       velocity=o['velocity'], lanes=lanes, to_host=to_host, device=not to_host, max_waves=max_waves)
+        return (out['c'], out['phi']) if to_host else (out['c_dev'], out['phi_dev'])
+
+    def resample_to(self, other, lanes=None, dst_lanes=None):
+        """The device path of a grid transfer: the lanes `lanes` of this solver (None: all) resampled onto the grid of `other` (a
+        PnpSolver of the physical mode on the same device, with a batch set) and written into its lanes `dst_lanes` (None: 0 .. n-1)
+        by set_lanes_device.  No state crosses PCIe."""
+        if other.N != self.N:
+            raise ValueError('resample_to: %d species here, %d there' % (self.N, other.N))
+        if other._obs['device'] != self._obs['device']:
+            raise ValueError('resample_to: the two solvers live on different devices')
+        n = self.B if lanes is None else len(lanes)
+        c_dev, phi_dev = self.resample(other._obs['x'], lanes=lanes, to_host=False)
+        other.set_lanes_device(c_dev, phi_dev, n=n, lanes=dst_lanes)
+
     def set_lane_mask(self, mask=None):
         """Only lanes with a non-zero mask take part in the following solves of the physical mode (None: all lanes again)."""
         if mask is None:
@@ -612,6 +656,11 @@ class PnpSolver(object):
         ms = C.c_float(0)
         self._check(self._lib.pnp_timer_stop(self._h, C.byref(ms)))
         return float(ms.value)
+
+    @property
+    def grid(self):
+        """The grid x[nx] this solver works on (set_grid, or the uniform one of the constructor)"""
+        return self._obs['x']
 
     @property
     def device_bytes(self):

@@ -1,4 +1,4 @@
-"""What the ctypes bindings of the libraries that read a ``pnp_device_view`` (``_observe.py``, ``_balance.py``) share: the view's mirror,
+"""What the ctypes bindings of the libraries that read a ``pnp_device_view`` (``_observe.py``, ``_balance.py``, ``_regrid.py``) share: the view's mirror,
 loading a library with its five lifecycle symbols and its entry point, and the handle class."""
 import ctypes as C
 import os

@@ -14,7 +14,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wal
 
 _INCLUDE = os.path.join(_HERE, '..', 'include')
 # what every library that derives quantities from a device-resident state includes (csrc/pnp_post.h); tests/test_build_deps.py follows
-# the #include lines of all three libraries and compares with the lists here
+# the #include lines of the first three libraries and compares with the lists here (tests/test_regrid_abi.py: the fourth)
 _POST_HEADERS = [os.path.join(CSRC, h) for h in ('pnp_post.h', 'pnp_wave.h', 'pnp_math.h', 'pnp_internal.h')] + [os.path.join(_INCLUDE, 'catint_pnp.h')]
 
 # second library (include/catint_observe.h): observables derived from a device-resident state.  Its kernels stay out of SOURCES:
@@ -30,6 +30,13 @@ BALANCE_DIR = os.path.join(CSRC, 'balance')
 BALANCE_LIB = os.path.join(LIB_DIR, 'libcatint_balance.so')
 BALANCE_SOURCES = ['catbal.hip']
 BALANCE_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_balance.h')]
+
+# fourth library (include/catint_regrid.h): a device-resident state resampled onto another grid.  Again a library of its own: the kernel
+# and symbol sets of the other three stay what their tests pin
+REGRID_DIR = os.path.join(CSRC, 'regrid')
+REGRID_LIB = os.path.join(LIB_DIR, 'libcatint_regrid.so')
+REGRID_SOURCES = ['catgrid.hip']
+REGRID_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_regrid.h')]
 
 PARTIAL = os.path.join(LIB_DIR, '.partial')      # left by tools/devbuild.sh: the library holds only one block size
 
@@ -118,3 +125,12 @@ def balance_needs_build():
 def build_balance_library(force=False, verbose=False):
     """catint_amd/csrc/balance into catint_amd/lib/libcatint_balance.so"""
     return _build_unit(BALANCE_DIR, BALANCE_SOURCES, BALANCE_HEADERS, BALANCE_LIB, force, verbose)
+
+
+def regrid_needs_build():
+    return _unit_needs_build(REGRID_DIR, REGRID_SOURCES, REGRID_HEADERS, REGRID_LIB)
+
+
+def build_regrid_library(force=False, verbose=False):
+    """catint_amd/csrc/regrid into catint_amd/lib/libcatint_regrid.so"""
+    return _build_unit(REGRID_DIR, REGRID_SOURCES, REGRID_HEADERS, REGRID_LIB, force, verbose)

@@ -353,7 +353,7 @@ class Calculator(object):
                 out[:, names.index(sp)] += v * K * g
         return out
 
-    def solve_physical(self, solver, c0, phiM, flux, nramp=4, warm=False, retry=True):
+    def solve_physical(self, solver, c0, phiM, flux, nramp=4, warm=False, retry=True, _coarse=True):
         """One transport solve of every lane (run_single_step, calculator.py:408-535).
         Stationary mode: Newton from the current state (warm) or from the bulk state.  If lanes do not converge from the
         bulk state -- or the potentials are far from phiPZC, or surface kinetics are coupled in, where that is the rule --
@@ -365,7 +365,10 @@ class Calculator(object):
         rate constants are evaluated at the stage potential, each stage warm-started from the previous one (the reference's
         parametric sweeps: flux_factor / PZC / CS ramps, transport.py:877-893, comsol_model.py:1147-1167).
         Time-dependent mode: tp.nt-1 backward-Euler steps.  retry=False: no rerun ladder for lanes that fail (the first solve of an
-        SCF cycle, where a lane without a solution is an expected answer).  Returns status [B]."""
+        SCF cycle, where a lane without a solution is an expected answer).  Returns status [B].
+        tp.newton['coarse_nx'] (or an explicit grid tp.newton['coarse_mesh']), off by default: mesh continuation, see
+        _mesh_continuation.  tp.newton['regrid_on_device'], off by default: the mesh rung of the ladder below hands its solution to
+        the main handle on the device (PnpSolver.resample_to) instead of get_state + np.interp + set_lanes."""
         phiM = np.asarray(phiM, float)
         B = len(phiM)
         pb = np.zeros((B, 4)); pb[:, 0] = phiM
@@ -394,7 +397,8 @@ class Calculator(object):
         start = float(self.tp.system.get('phiPZC', 0.0)) if stern else 0.0
         span = float(np.abs(phiM - start).max())
         direct = nramp <= 1 or (span <= nk.get('direct_span', 0.6) and not getattr(self, 'surface_kinetics', None))
-        if direct:
+        coarse = self._coarse_mesh(solver, nk) if _coarse else None
+        if direct and coarse is None:
             solver.set_batch(c0, pb, vz, flux)
             self._apply_surface_kinetics(solver, phiM)
             st = solver.solve_stationary()
@@ -402,7 +406,14 @@ class Calculator(object):
                 return st
         nst = max(int(nramp), int(np.ceil(span / nk.get('dphi_stage', 0.4))))
         self.continuation_stages = nst
-        st = self._continuation(solver, c0, pb, vz, flux, phiM, start, nst)
+        first_rung = 1
+        if coarse is not None:
+            st = self._mesh_continuation(solver, coarse, c0, pb, vz, flux, phiM, nramp)
+            if not (st != 0).any():
+                return st
+            first_rung = 0       # the lanes that failed walk the usual path (nst stages) as rung 0 of the ladder below
+        else:
+            st = self._continuation(solver, c0, pb, vz, flux, phiM, start, nst)
         # Lanes that still fail: the reference reruns COMSOL up to 25 times with a load / non-linearity ramp half as coarse each time
         # (and a finer boundary mesh, which a handle cannot change: refine with tp.set_graded_mesh) -- calculator.py:455-531.  Here
         # only the failed lanes walk the path again, as a batch of their own, with 2, 4, 8 x the stages; what converges is patched
@@ -410,7 +421,8 @@ class Calculator(object):
         self.retry_log = []
         rungs = int(nk.get('retry_rungs', 3)) if retry else 0
         mesh_rungs = int(nk.get('retry_mesh_rungs', 1)) if retry else 0
-        for rung in range(1, rungs + mesh_rungs + 1):
+        on_device = bool(nk.get('regrid_on_device', False))
+        for rung in range(first_rung, rungs + mesh_rungs + 1):
             bad = np.flatnonzero(st != 0)
             if len(bad) == 0:
                 break
@@ -419,24 +431,30 @@ class Calculator(object):
             xf = None
             if mesh:
                 from .host import graded_mesh
-                x = np.asarray(self.tp.xmesh, float)
+                # (the device path needs the handle's own grid to the bit: no target point may lie outside the source grid)
+                x = np.asarray(solver.grid if on_device else self.tp.xmesh, float)
                 xf = graded_mesh(x[-1], (x[1] - x[0]) / 1.5 ** (rung - rungs), len(x))
             with self._physical_solver(len(bad), xmesh=xf) as sub:
                 st_sub = self._continuation(sub, np.asarray(c0)[bad], pb[bad], vz[bad], np.asarray(flux)[bad], phiM[bad], start, stages,
                                             lanes=bad)
-                c_sub, phi_sub = sub.get_state()[:2]
-            good = st_sub == 0
+                good = st_sub == 0
+                regridded = mesh and on_device and bool(good.any())
+                if regridded:      # the recovered lanes go from handle to handle on the device, resampled onto the batch's mesh
+                    sub.resample_to(solver, lanes=np.flatnonzero(good), dst_lanes=bad[good])
+                else:
+                    c_sub, phi_sub = sub.get_state()[:2]
             entry = {'rung': rung, 'stages': stages, 'lanes': bad.tolist(), 'recovered': [], 'mesh_refined': bool(mesh)}
             self.retry_log.append(entry)
             if good.any():
-                c_sub = np.asarray(c_sub, float).reshape(len(bad), self.tp.nspecies, -1)[good]
-                phi_sub = np.asarray(phi_sub, float).reshape(len(bad), -1)[good]
-                if mesh:      # back onto the batch's mesh: the finer solution is the initial guess of the confirming solve there
-                    x = np.asarray(self.tp.xmesh, float)
-                    c_sub = np.stack([[np.interp(x, xf, row) for row in lane] for lane in c_sub])
-                    phi_sub = np.stack([np.interp(x, xf, row) for row in phi_sub])
-                # only the recovered lanes travel (pnp_set_lanes); counters, flags and the other lanes stay as they are ...
-                solver.set_lanes(bad[good], c_sub, phi_sub)
+                if not regridded:
+                    c_sub = np.asarray(c_sub, float).reshape(len(bad), self.tp.nspecies, -1)[good]
+                    phi_sub = np.asarray(phi_sub, float).reshape(len(bad), -1)[good]
+                    if mesh:      # back onto the batch's mesh: the finer solution is the initial guess of the confirming solve there
+                        x = np.asarray(self.tp.xmesh, float)
+                        c_sub = np.stack([[np.interp(x, xf, row) for row in lane] for lane in c_sub])
+                        phi_sub = np.stack([np.interp(x, xf, row) for row in phi_sub])
+                    # only the recovered lanes travel (pnp_set_lanes); counters, flags and the other lanes stay as they are ...
+                    solver.set_lanes(bad[good], c_sub, phi_sub)
                 # ... and the main handle's own verdict on them is what is reported: one solve restricted to these lanes
                 mask = np.zeros(B, np.int32)
                 mask[bad[good]] = 1
@@ -448,6 +466,41 @@ class Calculator(object):
                 st = st.copy()
                 st[bad[good]] = st2[bad[good]]
                 entry['recovered'] = [int(b_) for b_ in bad[good] if st[b_] == 0]
+        return st
+
+    def _coarse_mesh(self, solver, nk):
+        """The coarse grid of mesh continuation: tp.newton['coarse_mesh'], or a graded mesh of tp.newton['coarse_nx'] points over the
+        handle's domain with the handle's first spacing; None when neither is set."""
+        if nk.get('coarse_mesh') is not None:
+            return np.asarray(nk['coarse_mesh'], float)
+        if not nk.get('coarse_nx'):
+            return None
+        from .host import graded_mesh
+        x = np.asarray(solver.grid, float)
+        return graded_mesh(x[-1], x[1] - x[0], int(nk['coarse_nx']))
+
+    def _mesh_continuation(self, solver, xc, c0, pb, vz, flux, phiM, nramp):
+        """Mesh continuation (stationary mode): the usual path -- direct solve or continuation stages, without the rerun ladder -- runs
+        on a handle of the coarse grid xc, from c0 restricted onto it; the lanes it solves are resampled onto the main handle's grid on
+        the device (PnpSolver.resample_to: the interpolant of the discretisation, nothing crosses PCIe), the others start from c0;
+        then ONE direct solve of the main handle at the operating point gives every lane's status.  `flux` is what reaches the wall
+        (already scaled by RF)."""
+        B = len(phiM)
+        x = np.asarray(solver.grid, float)
+        c0 = np.asarray(c0, float).reshape(B, self.tp.nspecies, len(x))
+        c0c = np.stack([[np.interp(xc, x, row) for row in lane] for lane in c0])
+        solver.set_batch(c0, pb, vz, flux)
+        self._apply_surface_kinetics(solver, phiM)
+        with self._physical_solver(B, xmesh=xc) as sub:
+            st_c = self.solve_physical(sub, c0c, phiM, flux / self.RF, nramp=nramp, retry=False, _coarse=False)
+            good = np.flatnonzero(st_c == 0)
+            if len(good):
+                sub.resample_to(solver, lanes=good, dst_lanes=good)
+        st = solver.solve_stationary()
+        it = solver.newton_iterations()
+        self.newton_iterations_total = getattr(self, 'newton_iterations_total', 0) + int(it.sum())
+        self.newton_iterations_slowest = getattr(self, 'newton_iterations_slowest', 0) + int(it.max())
+        self.mesh_continuation = {'coarse_nx': len(xc), 'coarse_failed': int((st_c != 0).sum()), 'failed': int((st != 0).sum())}
         return st
 
     def _continuation(self, solver, c0, pb, vz, flux, phiM, start, nst, lanes=None):

@@ -1492,6 +1492,33 @@ int pnp_set_lanes(pnp_handle* h, int64_t n, const int64_t* lanes, const double* 
   return PNP_OK;
 }
 
+int pnp_set_lanes_device(pnp_handle* h, int64_t n, const int64_t* lanes, const double* c_dev, const double* phi_dev) {
+  if (!h || (n > 0 && !c_dev)) return fail(h, PNP_EINVAL, "pnp_set_lanes_device: null argument");
+  if (!h->newton) return fail(h, PNP_EINVAL, "pnp_set_lanes_device: the handle was not created with PNP_METHOD_NEWTON");
+  if (!h->have_batch) return fail(h, PNP_ESTATE, "pnp_set_lanes_device: call pnp_set_batch first");
+  if (n < 0) return fail(h, PNP_EINVAL, "pnp_set_lanes_device: n < 0");
+  if (!lanes && n > h->B) return fail(h, PNP_EINVAL, "pnp_set_lanes_device: lane index out of range");
+  for (int64_t i = 0; lanes && i < n; ++i)
+    if (lanes[i] < 0 || lanes[i] >= h->B) return fail(h, PNP_EINVAL, "pnp_set_lanes_device: lane index out of range");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  std::vector<uint8_t>& hist = lane_history(h);
+  for (int64_t i = 0; i < n; ++i) hist[(size_t)(lanes ? lanes[i] : i)] = 0;
+  const int N = h->a.N, nx = h->a.nx, ldx = h->a.ldx;
+  const size_t w = (size_t)nx * sizeof(double), dp = (size_t)ldx * sizeof(double);
+  // source and destination rows have the same pitch; the width of nx doubles leaves the pads of the handle's rows alone
+  // (lanes 0 .. n-1 are one block of rows on both sides: one copy each for the concentrations and the potential)
+  const int64_t ncopies = lanes ? n : (n > 0 ? 1 : 0), per = lanes ? 1 : n;
+  for (int64_t i = 0; i < ncopies; ++i) {
+    const size_t b = (size_t)(lanes ? lanes[i] : 0);
+    HIP_TRY(h, hipMemcpy2DAsync(h->c + b * N * ldx, dp, c_dev + (size_t)i * N * ldx, dp, w, (size_t)(per * N), hipMemcpyDeviceToDevice,
+                                h->stream));
+    if (phi_dev)
+      HIP_TRY(h, hipMemcpy2DAsync(h->v + b * ldx, dp, phi_dev + (size_t)i * ldx, dp, w, (size_t)per, hipMemcpyDeviceToDevice, h->stream));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return PNP_OK;
+}
+
 int pnp_set_lane_mask(pnp_handle* h, const int32_t* mask) {
   if (!h) return PNP_EINVAL;
   if (!h->newton) return fail(h, PNP_EINVAL, "pnp_set_lane_mask: the handle was not created with PNP_METHOD_NEWTON");

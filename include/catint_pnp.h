@@ -313,6 +313,12 @@ int pnp_set_potential(pnp_handle* h, const double* phi);
  * crossing PCIe.  phi may be NULL (potential rows unchanged).  A lane's BDF2 / predictor history is its own: the patched lanes
  * restart with a backward-Euler step, every other lane keeps its history. */
 int pnp_set_lanes(pnp_handle* h, int64_t n, const int64_t* lanes, const double* c, const double* phi);
+/* pnp_set_lanes from DEVICE memory of the handle's device, e.g. what libcatint_regrid (catint_regrid.h) left there: c_dev
+ * [n][N][row_pitch], phi_dev [n][row_pitch] (nullable) with the handle's own row pitch (pnp_row_pitch).  Only the first nx doubles of
+ * a row are copied, so the pads of the handle's rows stay as they are.  lanes == NULL: lanes 0 .. n-1.  Same lane-history reset,
+ * stream ordering (the copies run on the handle's stream and the call returns when they are done: the source must be complete when it is
+ * made) and validation as pnp_set_lanes.  Strided device-to-device copies only: no kernel. */
+int pnp_set_lanes_device(pnp_handle* h, int64_t n, const int64_t* lanes, const double* c_dev, const double* phi_dev);
 /* Restrict the following pnp_step / pnp_solve_stationary / pnp_solve_surface calls of the physical mode to the lanes with a non-zero
  * mask[b] (the others keep state, status, iteration counters and their BDF2 / predictor history: a masked-out call is a skipped call);
  * mask == NULL: all lanes again.  A lane's history is its own: a stationary solve restarts only the lanes it solves (their next step is
