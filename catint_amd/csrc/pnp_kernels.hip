@@ -30,7 +30,8 @@ namespace pnp {
 // Poisson for one wave.  LV holds lapl_v by grid index (padded LDS row).  Writes grad_v by grid
 // index into GV (all nx entries incl. the extrapolated ends) and, if VV != nullptr, v into VV.
 // Returns v[1] (needed by the Robin wall condition, calculator_old.py:528-532).
-// DD: the caller has already established A.pb_mode == PNP_PB_DD (step_kernel's fast body), so the other branches are not compiled in.
+// DD: the caller is step_kernel's fast body.  It has already established A.pb_mode == PNP_PB_DD, so the other branches are not
+// compiled in; it is a Crank-Nicolson launch; and it lets the section blank the bulk slot of LV (see there).
 // ------------------------------------------------------------------------------------------------
 template <int P, bool WANT_V, int SHIFT, bool DD = false>
 __device__ __forceinline__ double poisson_wave(const DevArgs& A, double* LV, double* GV, double* VV, double* X,
@@ -49,21 +50,60 @@ __device__ __forceinline__ double poisson_wave(const DevArgs& A, double* LV, dou
       double Hi[P];
       const double dx2 = A.dx2;
       double s0 = 0.0, s1 = 0.0;
+      double hm1, hm2, h0, h1, incT, incW;
+      if constexpr (DD) {
+        // The fast body.  The bulk point is not part of the interior sum: its slot of LV is blanked, once, instead of a select per
+        // lane and point (+0.0 * dx2 is the +0.0 such a select gives).  Nothing needs the value that stood there:
+        //   * the stencil's lq = LV[pidx(r0 + j)] reaches index nx-1 = m+1 only in row r = m+1, a padded row (r >= m: don't care);
+        //   * the charge row that goes to global memory is written from registers (accp), not from LV;
+        //   * the epilogue rewrites the slot before the next step's Poisson section, and stage_first_round before the first, so
+        //     the blanking holds for this step alone.
+        if (lane == 0) LV[pidx<P>(nx - 1)] = 0.0;
+        lds_sync();
+        {
+          // products of their own: the sums they enter took them from selects and lane reads in the general body, which keeps them
+          // from being contracted there
+#pragma clang fp contract(off)
 #pragma unroll
-      for (int j = 0; j < P; ++j) {
-        double h = LV[pidx<P>(r0 + j + 1)] * dx2;
-        h = (r0 + j == m) ? 0.0 : h;                      // the bulk point is not part of the interior sum
-        Hi[j] = h;
-        s0 += h;
-        s1 = __builtin_fma((double)j, h, s1);
+          for (int j = 0; j < P; ++j) Hi[j] = LV[pidx<P>(r0 + j + 1)] * dx2;
+          // h at grid points m, m-1 (for g_last) and 1, 2 (for g_first) straight from LV: wave-uniform addresses, so each read is a
+          // broadcast, issued with the reads above.  The blanked slot is none of the four (m = nx-2).
+          hm1 = LV[pidx<P>(m)] * dx2;
+          hm2 = LV[pidx<P>(m - 1)] * dx2;
+          h0 = LV[pidx<P>(1)] * dx2;
+          h1 = LV[pidx<P>(2)] * dx2;
+        }
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+          s0 += Hi[j];
+          s1 = __builtin_fma((double)j, Hi[j], s1);
+        }
+      } else {
+        // The general body (and mol_rhs_kernel): the same values by per-lane selects.  Kept as it was because <16,1,3>, which has
+        // no fast body and already spills, gains scratch with the form above.
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+          double h = LV[pidx<P>(r0 + j + 1)] * dx2;
+          h = (r0 + j == m) ? 0.0 : h;                      // the bulk point is not part of the interior sum
+          Hi[j] = h;
+          s0 += h;
+          s1 = __builtin_fma((double)j, h, s1);
+        }
+        hm1 = pick_blocked<P>(Hi, r0, m - 1);
+        hm2 = pick_blocked<P>(Hi, r0, m - 2);
+        h0 = read_lane(Hi[0], 0);
+        h1 = read_lane(Hi[1], 0);
       }
       const double wsum = __builtin_fma((double)(m - r0), s0, -s1);
-      const double hm1 = pick_blocked<P>(Hi, r0, m - 1), hm2 = pick_blocked<P>(Hi, r0, m - 2);
-      const double h0 = read_lane(Hi[0], 0), h1 = read_lane(Hi[1], 0);
 #pragma unroll
       for (int j = 1; j < P; ++j) Hi[j] += Hi[j - 1];
-      const double incT = wave_scan_incl(Hi[P - 1]);
-      const double incW = wave_scan_incl(wsum);
+      if constexpr (DD) {
+        incT = wave_scan_incl_bc(Hi[P - 1]);
+        incW = wave_scan_incl_bc(wsum);
+      } else {
+        incT = wave_scan_incl(Hi[P - 1]);
+        incW = wave_scan_incl(wsum);
+      }
       const double base = from_prev_lane(0.0, incT);
       const double tot1 = read_lane(incT, 63), totG = read_lane(incW, 63);
 #pragma unroll
@@ -89,6 +129,8 @@ __device__ __forceinline__ double poisson_wave(const DevArgs& A, double* LV, dou
         if constexpr (SHIFT == 1) {
           GV[pidx<P>(0)] = g_first;          // interior index -1 clamps to grad_v[0]  (add_boundary_values :496)
           GV[pidx<P>(nx + 1)] = g_last;      // one past the end, read by the FTCS window of padded rows
+          // the fast body is Crank-Nicolson: grad_v[-1] parked in entry nx-2, from the register (step_body's general body reads it back)
+          if constexpr (DD) GV[pidx<P>(nx - 2 + 1)] = g_last;
         }
       }
       lds_sync();
@@ -358,7 +400,8 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
           GV[V1SLOT] = v1w;
           // CN indexes grad_v with the interior index r <= nx-3 plus, for the bulk boundary term,
           // grad_v[-1]: park the latter in the otherwise unused entry nx-2 (see the stencil below)
-          if (cn) GV[pidx<P>(nx - 2 + 1)] = GV[pidx<P>(nx - 1 + 1)];
+          // (fast body: poisson_wave has written it already)
+          if (!FAST && cn) GV[pidx<P>(nx - 2 + 1)] = GV[pidx<P>(nx - 1 + 1)];
         }
       }
     }
@@ -473,7 +516,9 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
           }
           __builtin_amdgcn_sched_barrier(0);
           lds_sync();
-          tridiag_wave<P, G>(ta, tc, x, ROW0, RB, lane);       // np.linalg.solve(A,B), :556
+          // (fast body: the three distance-1 exchanges of the solve through DPP, see tridiag_wave; 4.6 -> 4.4 us per step on the
+          // headline shape, profiles/step_poisson_bench.md)
+          tridiag_wave<P, G, FAST>(ta, tc, x, ROW0, RB, lane);       // np.linalg.solve(A,B), :556
         } else {
           // FTCS :1012-1023
           double gq[P + 2];   // grad_v at grid r0 .. r0+P+1

@@ -222,7 +222,12 @@ __device__ __forceinline__ void blocked_scan_sum(double (&x)[P], double w, doubl
 // Stage 3: back-substitution of the interior rows.
 // X + g*XSTRIDE is the strip of system g.
 // ------------------------------------------------------------------------------------------------
-template <int P, int G>
+__device__ __forceinline__ double from_prev_lane(double old_lane0, double x);
+__device__ __forceinline__ double from_next_lane(double old_lane63, double x);
+
+// DPP1: the three exchanges with the neighbouring lane (the interface close, the first reduction level and the final yL) go through
+// DPP wave shifts, whose `old` operand 0.0 stands in for the zero guards, instead of through the LDS strip: the same values.
+template <int P, int G, bool DPP1 = false>
 __device__ __forceinline__ void tridiag_wave(double (&a)[G][P], double (&c)[G][P], double (&d)[G][P], double* X,
                                              int XSTRIDE, int lane) {
   // in place: a[i] -> Vs_i, c[i] -> Ws_i, d[i] -> ds_i with x_i = ds_i - Vs_i*yL - Ws_i*y  (i < P-1)
@@ -272,21 +277,30 @@ __device__ __forceinline__ void tridiag_wave(double (&a)[G][P], double (&c)[G][P
       }
     }
     // first interior row of the next lane closes this lane's interface row
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      XA[g * XSTRIDE] = a[g][0];
-      XC[g * XSTRIDE] = c[g][0];
-      XD[g * XSTRIDE] = d[g][0];
-    }
-    lds_sync();
     double Vn0[G], Wn0[G], dn0[G];
+    if constexpr (DPP1) {
 #pragma unroll
-    for (int g = 0; g < G; ++g) {   // lane 63 reads the zero guard
-      Vn0[g] = XA[g * XSTRIDE + 1];
-      Wn0[g] = XC[g * XSTRIDE + 1];
-      dn0[g] = XD[g * XSTRIDE + 1];
+      for (int g = 0; g < G; ++g) {
+        Vn0[g] = from_next_lane(0.0, a[g][0]);
+        Wn0[g] = from_next_lane(0.0, c[g][0]);
+        dn0[g] = from_next_lane(0.0, d[g][0]);
+      }
+    } else {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        XA[g * XSTRIDE] = a[g][0];
+        XC[g * XSTRIDE] = c[g][0];
+        XD[g * XSTRIDE] = d[g][0];
+      }
+      lds_sync();
+#pragma unroll
+      for (int g = 0; g < G; ++g) {   // lane 63 reads the zero guard
+        Vn0[g] = XA[g * XSTRIDE + 1];
+        Wn0[g] = XC[g * XSTRIDE + 1];
+        dn0[g] = XD[g * XSTRIDE + 1];
+      }
+      lds_sync();
     }
-    lds_sync();
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       const double aL = a[g][P - 1], cL = c[g][P - 1];
@@ -303,24 +317,36 @@ __device__ __forceinline__ void tridiag_wave(double (&a)[G][P], double (&c)[G][P
   // parallel cyclic reduction over the 64 interface rows (unit diagonal kept by renormalising)
 #pragma unroll
   for (int s = 1; s < 64; s <<= 1) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      XA[g * XSTRIDE] = ra[g];
-      XC[g * XSTRIDE] = rc[g];
-      XD[g * XSTRIDE] = rd[g];
-    }
-    lds_sync();
     double aL[G], aR[G], cL[G], cR[G], dL[G], dR[G];
+    if (DPP1 && s == 1) {
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-      aL[g] = XA[g * XSTRIDE - s];
-      aR[g] = XA[g * XSTRIDE + s];
-      cL[g] = XC[g * XSTRIDE - s];
-      cR[g] = XC[g * XSTRIDE + s];
-      dL[g] = XD[g * XSTRIDE - s];
-      dR[g] = XD[g * XSTRIDE + s];
+      for (int g = 0; g < G; ++g) {
+        aL[g] = from_prev_lane(0.0, ra[g]);
+        aR[g] = from_next_lane(0.0, ra[g]);
+        cL[g] = from_prev_lane(0.0, rc[g]);
+        cR[g] = from_next_lane(0.0, rc[g]);
+        dL[g] = from_prev_lane(0.0, rd[g]);
+        dR[g] = from_next_lane(0.0, rd[g]);
+      }
+    } else {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        XA[g * XSTRIDE] = ra[g];
+        XC[g * XSTRIDE] = rc[g];
+        XD[g * XSTRIDE] = rd[g];
+      }
+      lds_sync();
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        aL[g] = XA[g * XSTRIDE - s];
+        aR[g] = XA[g * XSTRIDE + s];
+        cL[g] = XC[g * XSTRIDE - s];
+        cR[g] = XC[g * XSTRIDE + s];
+        dL[g] = XD[g * XSTRIDE - s];
+        dR[g] = XD[g * XSTRIDE + s];
+      }
+      lds_sync();
     }
-    lds_sync();
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       double nb = __builtin_fma(-ra[g], cL[g], 1.0);
@@ -336,13 +362,18 @@ __device__ __forceinline__ void tridiag_wave(double (&a)[G][P], double (&c)[G][P
     }
   }
   if constexpr (P > 1) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) XA[g * XSTRIDE] = rd[g];
-    lds_sync();
     double yL[G];
+    if constexpr (DPP1) {
 #pragma unroll
-    for (int g = 0; g < G; ++g) yL[g] = XA[g * XSTRIDE - 1];   // lane 0 reads the zero guard
-    lds_sync();
+      for (int g = 0; g < G; ++g) yL[g] = from_prev_lane(0.0, rd[g]);
+    } else {
+#pragma unroll
+      for (int g = 0; g < G; ++g) XA[g * XSTRIDE] = rd[g];
+      lds_sync();
+#pragma unroll
+      for (int g = 0; g < G; ++g) yL[g] = XA[g * XSTRIDE - 1];   // lane 0 reads the zero guard
+      lds_sync();
+    }
 #pragma unroll
     for (int i = 0; i < P - 1; ++i) {
 #pragma unroll
@@ -372,6 +403,26 @@ __device__ __forceinline__ double wave_scan_incl(double v) {
   v += dpp_f64<0x112>(0.0, v);        // row_shr:2
   v += dpp_f64<0x114>(0.0, v);        // row_shr:4
   v += dpp_f64<0x118>(0.0, v);        // row_shr:8
+  v += dpp_f64<0x142, 0xa>(0.0, v);   // row_bcast:15 into rows 1,3
+  v += dpp_f64<0x143, 0xc>(0.0, v);   // row_bcast:31 into rows 2,3
+  return v;
+}
+
+// x of the DPP source lane, 0.0 where there is none (bound_ctrl): every lane is written, so no `old` operand has to be seeded
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64_or_zero(double x) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+
+// wave_scan_incl with the four full-row-mask stages on bound_ctrl: the same values (a lane without a source adds 0.0 either way),
+// eight zero seeds fewer per scan.  A function of its own so that the step_kernel_rr / step_kernel_st families compile to what they did.
+__device__ __forceinline__ double wave_scan_incl_bc(double v) {
+  v += dpp_f64_or_zero<0x111>(v);     // row_shr:1
+  v += dpp_f64_or_zero<0x112>(v);     // row_shr:2
+  v += dpp_f64_or_zero<0x114>(v);     // row_shr:4
+  v += dpp_f64_or_zero<0x118>(v);     // row_shr:8
   v += dpp_f64<0x142, 0xa>(0.0, v);   // row_bcast:15 into rows 1,3
   v += dpp_f64<0x143, 0xc>(0.0, v);   // row_bcast:31 into rows 2,3
   return v;
