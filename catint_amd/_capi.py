@@ -247,7 +247,11 @@ class PnpSolver(object):
                      'mpb_radius': None, 'velocity': 0.0, 'device': int(device),
                      # ... and what get_balance hands to the balance library on top of that (recording only)
                      'reactions': [], 'wall': None, 'flux': None, 'phiM': None, 'flux_stale': False, 'wall_stale': False,
-                     'explicit_kinetics': False}
+                     'explicit_kinetics': False,
+                     # ... and what equilibrium / set_equilibrium hand to the equilibrium library
+                     'eps': float(eps), 'dx': float(dx), 'wall_bc': 'dirichlet', 'stern_capacitance': 0.0, 'phi_pzc': 0.0,
+                     'c_bulk': None, 'phi_bulk': None}
+        self._equilibrator = None
         self._observer = None
         self._balancer = None
         self._regridder = None
@@ -266,6 +270,9 @@ class PnpSolver(object):
         if getattr(self, '_regridder', None) is not None:
             self._regridder.close()
             self._regridder = None
+        if getattr(self, '_equilibrator', None) is not None:
+            self._equilibrator.close()
+            self._equilibrator = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -301,7 +308,8 @@ class PnpSolver(object):
         self._check(self._lib.pnp_set_batch(self._h, B, _dptr(c0), _dptr(pb), _dptr(_f64(vzeta, (B,))),
                                             _dptr(_f64(flux, (B, self.N)))))
         self.B = B
-        self._obs.update(flux=np.array(_f64(flux, (B, self.N))), phiM=pb[:, 0].copy(), flux_stale=False, explicit_kinetics=False)
+        self._obs.update(flux=np.array(_f64(flux, (B, self.N))), phiM=pb[:, 0].copy(), flux_stale=False, explicit_kinetics=False,
+                         c_bulk=c0[:, :, -1].copy(), phi_bulk=pb[:, 1].copy())
         # pnp_set_batch keeps the handle's wall table, but its rate constants are per lane of the batch they were set for: with another
         # batch size the recorded ones no longer say what the solver applies (get_balance refuses until set_wall_kinetics is called)
         if self._obs['wall'] is not None and len(self._obs['wall']['k']) != B:
@@ -314,7 +322,7 @@ class PnpSolver(object):
     def set_pb(self, pb, vzeta):
         pb = np.nan_to_num(_f64(pb, (self.B, 4)), nan=0.0)
         self._check(self._lib.pnp_set_pb(self._h, _dptr(pb), _dptr(_f64(vzeta, (self.B,)))))
-        self._obs['phiM'] = pb[:, 0].copy()
+        self._obs.update(phiM=pb[:, 0].copy(), phi_bulk=pb[:, 1].copy())
 
     # -- physical mode ---------------------------------------------------------------------
     def set_newton(self, wall_bc='dirichlet', stern_capacitance=0.0, phi_pzc=0.0, tol=1e-10, maxit=50, dphi_max=0.05,
@@ -327,7 +335,8 @@ class PnpSolver(object):
                             float(stern_capacitance), float(phi_pzc), float(tol), float(dphi_max), int(time_order), int(bool(predictor)))
         r = None if mpb_radius is None else _f64(mpb_radius, (self.N,))
         self._check(self._lib.pnp_set_newton(self._h, C.byref(p), _dptr(r)))
-        self._obs['mpb_radius'] = None if r is None else r.copy()
+        self._obs.update(mpb_radius=None if r is None else r.copy(), wall_bc=wall_bc, stern_capacitance=float(stern_capacitance),
+                         phi_pzc=float(phi_pzc))
 
     def set_option(self, key, value):
         """Debug / tuning switch of this handle (pnp_set_option): e.g. set_option('NEWTON_KERNEL', 'lane2').  The CATINT_* environment
@@ -495,6 +504,39 @@ class PnpSolver(object):
         n = self.B if lanes is None else len(lanes)
         c_dev, phi_dev = self.resample(other._obs['x'], lanes=lanes, to_host=False)
         other.set_lanes_device(c_dev, phi_dev, n=n, lanes=dst_lanes)
+
+    def equilibrium(self, phiM=None, lanes=None, to_host=True, tol=1e-10, maxit=100, max_waves=0):
+        """The zero-flux (equilibrium) state of the lanes `lanes` (None: all, in order; repeats allowed) at the wall potentials phiM
+        ([n], None: what set_batch / set_pb gave those lanes), solved on the device as a discrete size-modified Poisson-Boltzmann
+        problem (include/catint_equil.h): a root of this solver's own stationary residual with zero wall flux.  Bulk values, wall
+        model, ion radii and grid are the ones this solver was given.  The handle's state is not touched.  Returns a dict: 'status'
+        [n] (0, or 1: not converged within maxit), 'iterations' [n]; with to_host 'c' [n][N][nx] and 'phi' [n][nx]; otherwise nothing
+        but the flags crosses PCIe and 'c_dev' / 'phi_dev' are integer device addresses of rows with this handle's pitch, valid until
+        the next equilibrium / set_equilibrium / close of this solver (set_lanes_device takes them)."""
+        from . import _equil
+        o = self._obs
+        if o['c_bulk'] is None:
+            raise ValueError('equilibrium: no batch was set')
+        idx = np.arange(self.B) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+            raise ValueError('equilibrium: lane index outside [0, %d)' % self.B)
+        pm = o['phiM'][idx] if phiM is None else np.broadcast_to(np.asarray(phiM, float), (len(idx),))
+        if self._equilibrator is None:
+            self._equilibrator = _equil.Equilibrator(o['device'])
+        return self._equilibrator.solve(self.device_view(), o['charges'], o['x'], o['beta'], o['eps'], o['dx'], pm, o['phi_bulk'][idx],
+                                        o['c_bulk'][idx], mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
+                                        stern_capacitance=o['stern_capacitance'], phi_pzc=o['phi_pzc'], tol=tol, maxit=maxit,
+                                        to_host=to_host, device=not to_host, max_waves=max_waves)
+
+    def set_equilibrium(self, phiM=None, lanes=None, tol=1e-10, maxit=100):
+        """The device path of an equilibrium start: equilibrium(...) of the lanes `lanes` (None: all) written into those lanes by
+        set_lanes_device.  No state crosses PCIe; the other lanes, the counters and the flags stay as they are.  Returns
+        {'status', 'iterations'}."""
+        out = self.equilibrium(phiM=phiM, lanes=lanes, to_host=False, tol=tol, maxit=maxit)
+        n = len(out['status'])
+        if n:
+            self.set_lanes_device(out['c_dev'], out['phi_dev'], n=n, lanes=lanes)
+        return {'status': out['status'], 'iterations': out['iterations']}
 
     def set_lane_mask(self, mask=None):
         """Only lanes with a non-zero mask take part in the following solves of the physical mode (None: all lanes again)."""

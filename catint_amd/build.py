@@ -38,6 +38,13 @@ REGRID_LIB = os.path.join(LIB_DIR, 'libcatint_regrid.so')
 REGRID_SOURCES = ['catgrid.hip']
 REGRID_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_regrid.h')]
 
+# fifth library (include/catint_equil.h): the zero-flux (Poisson-Boltzmann) state of the physical mode solved on the device.  A library of
+# its own for the same reason: the solver library's kernel set is pinned (tests/test_kernel_census.py), and so are the other three
+EQUIL_DIR = os.path.join(CSRC, 'equil')
+EQUIL_LIB = os.path.join(LIB_DIR, 'libcatint_equil.so')
+EQUIL_SOURCES = ['cateq.hip']
+EQUIL_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_equil.h')]
+
 PARTIAL = os.path.join(LIB_DIR, '.partial')      # left by tools/devbuild.sh: the library holds only one block size
 
 
@@ -134,3 +141,12 @@ def regrid_needs_build():
 def build_regrid_library(force=False, verbose=False):
     """catint_amd/csrc/regrid into catint_amd/lib/libcatint_regrid.so"""
     return _build_unit(REGRID_DIR, REGRID_SOURCES, REGRID_HEADERS, REGRID_LIB, force, verbose)
+
+
+def equil_needs_build():
+    return _unit_needs_build(EQUIL_DIR, EQUIL_SOURCES, EQUIL_HEADERS, EQUIL_LIB)
+
+
+def build_equil_library(force=False, verbose=False):
+    """catint_amd/csrc/equil into catint_amd/lib/libcatint_equil.so"""
+    return _build_unit(EQUIL_DIR, EQUIL_SOURCES, EQUIL_HEADERS, EQUIL_LIB, force, verbose)

@@ -368,7 +368,8 @@ class Calculator(object):
         SCF cycle, where a lane without a solution is an expected answer).  Returns status [B].
         tp.newton['coarse_nx'] (or an explicit grid tp.newton['coarse_mesh']), off by default: mesh continuation, see
         _mesh_continuation.  tp.newton['regrid_on_device'], off by default: the mesh rung of the ladder below hands its solution to
-        the main handle on the device (PnpSolver.resample_to) instead of get_state + np.interp + set_lanes."""
+        the main handle on the device (PnpSolver.resample_to) instead of get_state + np.interp + set_lanes.
+        tp.newton['equilibrium_start'], off by default: where the continuation path would be walked, see _equilibrium_start."""
         phiM = np.asarray(phiM, float)
         B = len(phiM)
         pb = np.zeros((B, 4)); pb[:, 0] = phiM
@@ -412,6 +413,12 @@ class Calculator(object):
             if not (st != 0).any():
                 return st
             first_rung = 0       # the lanes that failed walk the usual path (nst stages) as rung 0 of the ladder below
+        elif nk.get('equilibrium_start', False):
+            st = self._equilibrium_start(solver, c0, pb, vz, flux, phiM)
+            self.continuation_stages = 1
+            if not (st != 0).any():
+                return st
+            first_rung = 0       # as after mesh continuation
         else:
             st = self._continuation(solver, c0, pb, vz, flux, phiM, start, nst)
         # Lanes that still fail: the reference reruns COMSOL up to 25 times with a load / non-linearity ramp half as coarse each time
@@ -501,6 +508,24 @@ class Calculator(object):
         self.newton_iterations_total = getattr(self, 'newton_iterations_total', 0) + int(it.sum())
         self.newton_iterations_slowest = getattr(self, 'newton_iterations_slowest', 0) + int(it.max())
         self.mesh_continuation = {'coarse_nx': len(xc), 'coarse_failed': int((st_c != 0).sum()), 'failed': int((st != 0).sum())}
+        return st
+
+    def _equilibrium_start(self, solver, c0, pb, vz, flux, phiM):
+        """Equilibrium start (stationary mode): instead of walking the wall potential up in stages, every lane starts from the zero-flux
+        state at its own phiM -- the double layer fully formed, solved on the device as a Poisson-Boltzmann problem and handed to the
+        handle there (PnpSolver.set_equilibrium: nothing crosses PCIe) -- and ONE direct solve with the full fluxes and kinetics gives
+        every lane's status.  A lane whose Poisson-Boltzmann iteration did not converge counts as failed.  `flux` is what reaches
+        the wall (already scaled by RF)."""
+        solver.set_batch(c0, pb, vz, flux)
+        self._apply_surface_kinetics(solver, phiM)
+        eq = solver.set_equilibrium(phiM)
+        st = np.array(solver.solve_stationary())
+        it = solver.newton_iterations()
+        self.newton_iterations_total = getattr(self, 'newton_iterations_total', 0) + int(it.sum())
+        self.newton_iterations_slowest = getattr(self, 'newton_iterations_slowest', 0) + int(it.max())
+        st[np.asarray(eq['status']) != 0] = 1
+        self.equilibrium_start = {'pb_failed': int((np.asarray(eq['status']) != 0).sum()), 'pb_iterations': int(np.max(eq['iterations'])),
+                                  'failed': int((st != 0).sum())}
         return st
 
     def _continuation(self, solver, c0, pb, vz, flux, phiM, start, nst, lanes=None):

@@ -59,12 +59,17 @@ def main():
     ap.add_argument('--balance', action='store_true',
                     help='derive species fluxes, reaction rates, wall fluxes and the mass balance on the device (Calculator(balance_on_device=True)): '
                          'prints the partial current density of every wall reaction at three voltages and the worst relative imbalance')
+    ap.add_argument('--equilibrium-start', action='store_true',
+                    help='start every lane from the zero-flux (Poisson-Boltzmann) state at its own voltage, solved on the device, and solve '
+                         'once instead of walking the continuation stages (tp.newton[\'equilibrium_start\'])')
     a = ap.parse_args()
     tp, phis = build(a.lanes, a.nx)
     rate = tafel_rate(tp)
     kin = [{'species': 'CO2', 'rate': rate, 'stoichiometry': {'CO2': -1.0, 'CO': 1.0, 'OH-': 2.0}}]
     calc = Calculator(transport=tp, calc='comsol', derive_on_device=a.device_observables, balance_on_device=a.balance)
     tp.newton = {'tol': 1e-8, 'maxit': 80}
+    if a.equilibrium_start:
+        tp.newton['equilibrium_start'] = True
     calc.set_surface_kinetics(kin)
     t0 = time.time()
     calc.run()
