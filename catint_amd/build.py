@@ -45,6 +45,13 @@ EQUIL_LIB = os.path.join(LIB_DIR, 'libcatint_equil.so')
 EQUIL_SOURCES = ['cateq.hip']
 EQUIL_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_equil.h')]
 
+# test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
+# in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
+UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
+UNITTEST_LIB = os.path.join(LIB_DIR, 'libcatint_unittest.so')
+UNITTEST_SOURCES = ['primitives_harness.hip']
+UNITTEST_HEADERS = _POST_HEADERS + [os.path.join(CSRC, 'pnp_lane_common.h')]
+
 PARTIAL = os.path.join(LIB_DIR, '.partial')      # left by tools/devbuild.sh: the library holds only one block size
 
 
@@ -150,3 +157,12 @@ def equil_needs_build():
 def build_equil_library(force=False, verbose=False):
     """catint_amd/csrc/equil into catint_amd/lib/libcatint_equil.so"""
     return _build_unit(EQUIL_DIR, EQUIL_SOURCES, EQUIL_HEADERS, EQUIL_LIB, force, verbose)
+
+
+def unittest_needs_build():
+    return _unit_needs_build(UNITTEST_DIR, UNITTEST_SOURCES, UNITTEST_HEADERS, UNITTEST_LIB)
+
+
+def build_unittest_library(force=False, verbose=False):
+    """tests/csrc into catint_amd/lib/libcatint_unittest.so"""
+    return _build_unit(UNITTEST_DIR, UNITTEST_SOURCES, UNITTEST_HEADERS, UNITTEST_LIB, force, verbose)

@@ -1,7 +1,9 @@
 // Elementary functions of the Newton kernels with every constant in SCALAR registers at the point of use.
 // The library versions keep their polynomial coefficients in vector registers hoisted out of the Newton loop; in the
 // 128-register kernels those were spilled and re-read from scratch (which misses L2) -- one dependent memory round trip per
-// Horner step.  Accuracy is checked on the device by tools/probe/mathfn_probe.hip (expm1_sc <= 2 ulp, log1p_sc <= 3 ulp against the host libm over 1e6 arguments each).
+// Horner step.  Accuracy is checked on the device by tools/probe/mathfn_probe.hip (expm1_sc <= 2 ulp, log1p_sc <= 3 ulp against the host libm over 1e6 arguments each)
+// and, against multiprecision values and including the branch switches, the clamps and 0, by tests/test_gpu_primitives.py (bars: < 4 ulp each;
+// nrcp 2.2e-16 relative): profiles/primitives_unit.md holds the measured worst cases.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,7 +11,8 @@ namespace pnp {
 
 constexpr double N_AVOGADRO = 6.022140857e23;   // catint/units.py (unit_NA), as in oracle/pnp_physical.py
 
-__device__ __forceinline__ double nrcp(double x) {   // v_rcp_f64 + two Newton steps (1.1e-16 relative)
+// nrcp(+inf) is NaN (fma(-inf, 0, 1)): callers keep |x| finite.
+__device__ __forceinline__ double nrcp(double x) {   // v_rcp_f64 + two Newton steps (1.11e-16 = 2^-53 relative, measured: profiles/primitives_unit.md)
   double r = __builtin_amdgcn_rcp(x);
   double e = __builtin_fma(-x, r, 1.0);
   r = __builtin_fma(r, e, r);

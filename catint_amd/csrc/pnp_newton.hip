@@ -311,6 +311,7 @@ struct Edge {
   double Bp, Bm, J, Ju;
 };
 
+// Domain |u| <= 709: beyond it expm1_sc is +inf and nrcp(+inf) is NaN, so B and dB are NaN; the clips of the damped update keep u far below that.
 __device__ __forceinline__ Edge edge_flux(double u, double cl, double cr, double w) {   // w = dx/h_e (1 on a uniform grid)
   double B, dB;
   if (fabs(u) < 0.05) {   // oracle/pnp_physical.py: bernoulli, SERIES_U

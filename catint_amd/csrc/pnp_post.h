@@ -79,7 +79,9 @@ __device__ __forceinline__ void store_edge_row(double* row, const double (&v)[P 
   if (tight && t == T - 1) row[nx - 2] = v[P];
 }
 
-// B(u) = u / (exp(u) - 1): the solver's evaluation (edge_flux in pnp_newton.hip, oracle/pnp_physical.py: bernoulli, SERIES_U)
+// B(u) = u / (exp(u) - 1): the solver's evaluation (edge_flux in pnp_newton.hip, oracle/pnp_physical.py: bernoulli, SERIES_U).
+// Domain |u| <= 709: beyond it expm1_sc is +inf and nrcp(+inf) is NaN, not 0; every caller bounds u far below that.  Within 8 ulp on both
+// sides of the switch (tests/test_gpu_primitives.py, profiles/primitives_unit.md).
 __device__ __forceinline__ double bernoulli(double u) {
   if (fabs(u) < 0.05) {
     const double u2 = u * u;

@@ -14,8 +14,9 @@ typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 // small device helpers
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double fast_rcp(double x) {
-  // v_rcp_f64 seed (measured on gfx950: 4.6e-8 relative) + one Newton step -> 2.2e-15 relative
-  // (tools/probe/rcp_probe.hip).  The pivots of the diagonally dominant systems solved here are
+  // v_rcp_f64 seed (measured on gfx950: 4.6e-8 relative) + one Newton step -> 2.2e-15 relative (1.8e-15 measured)
+  // (tools/probe/rcp_probe.hip; tests/test_gpu_primitives.py holds it to twice that over 1e-150 .. 1e150,
+  // measured worst case in profiles/primitives_unit.md).  The pivots of the diagonally dominant systems solved here are
   // O(1) and well away from 0, so none of hipcc's div_scale/div_fixup range handling is needed; the
   // parity tolerance against the reference's LU (1e-9) leaves six orders of magnitude of margin.
   double r = __builtin_amdgcn_rcp(x);
@@ -23,7 +24,8 @@ __device__ __forceinline__ double fast_rcp(double x) {
   return __builtin_fma(r, e, r);
 }
 
-// full-accuracy variant (two Newton steps, 1.1e-16) for the few scalar, wave-uniform quotients
+// full-accuracy variant (two Newton steps, 1.11e-16 = 2^-53 measured: tests/test_gpu_primitives.py, profiles/primitives_unit.md) for the few scalar,
+// wave-uniform quotients
 __device__ __forceinline__ double fast_rcp2(double x) {
   double r = __builtin_amdgcn_rcp(x);
   double e = __builtin_fma(-x, r, 1.0);
@@ -89,7 +91,9 @@ constexpr int PAIR_STEP = (P == 1) ? 2 : 1;
 // Global rows are accessed through buffer resources (one 128-bit descriptor per row, built from
 // wave-uniform values): the hardware range check returns 0 for loads and drops stores beyond the row
 // pitch, so the partial last chunk of an odd pitch needs neither a lane predicate nor a branch, and
-// the per-lane address is one 32-bit offset VGPR plus an immediate.
+// the per-lane address is one 32-bit offset VGPR plus an immediate.  (The check is finer than the access: a 16-byte access that straddles the end of
+// an odd pitch is served for its first double only.  tests/test_gpu_primitives.py pins this for every helper below, with canaries behind
+// the rows.)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const double* row, int ldx) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(row), 0, ldx * 8, 0x00020000);
 }
@@ -221,6 +225,10 @@ __device__ __forceinline__ void blocked_scan_sum(double (&x)[P], double w, doubl
 //   side of the 64 lanes), so one step costs 3 LDS writes + 6 reads and no select for the edges.
 // Stage 3: back-substitution of the interior rows.
 // X + g*XSTRIDE is the strip of system g.
+// With m < 64*P real rows and c of row m-1 zero, the rows r >= m are don't-care as long as they stay finite (a NaN or inf in them would
+// reach row m-1 through 0 * x): they form a trailing block that never feeds back.  tests/test_gpu_primitives.py checks this, the
+// equality of the DPP1 and LDS paths and the forward error against multiprecision solutions for all 30 <P, G, DPP1> instances, up to
+// the Crank-Nicolson limit |a| + |c| -> 1 (D dt/dx^2 = 1e4); worst cases in profiles/primitives_unit.md.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double from_prev_lane(double old_lane0, double x);
 __device__ __forceinline__ double from_next_lane(double old_lane63, double x);

@@ -1,0 +1,626 @@
+"""Unit tests of the shared device primitives (test infrastructure, no tests of its own).
+
+Three parts:
+  * the ctypes binding of libcatint_unittest.so (tests/csrc/primitives_harness.hip: every primitive of pnp_math.h, pnp_wave.h,
+    pnp_post.h and pnp_lane_common.h behind a kernel of its own),
+  * multiprecision references (mpmath, 60 digits, rounded ONCE to fp64; where an error is measured in ulp the reference is the pair
+    (hi, lo) with hi + lo the exact value to ~1e-32 relative, so that the error is taken against the exact value, not a rounded one),
+  * the assertion helpers of tests/test_gpu_primitives.py -- pure functions of arrays -- and plain fp64 NumPy emulations of the
+    operations with their mutants; tests/test_primitives_ref.py shows without a GPU that every helper passes the emulation and fails
+    the mutants.
+"""
+import ctypes as C
+import functools
+import os
+
+import mpmath
+import numpy as np
+
+MP = mpmath.mp.clone()
+MP.prec = 200
+mpf = MP.mpf
+
+PS = (1, 2, 4, 8, 16)
+FN = {'fast_rcp': 0, 'fast_rcp2': 1, 'nrcp': 2, 'expm1_sc': 3, 'log1p_sc': 4, 'bernoulli': 5}
+SYMBOLS = ('catunit_scalar', 'catunit_edge_flux', 'catunit_wave_moves', 'catunit_read_lane', 'catunit_pick_blocked', 'catunit_wave_scan',
+           'catunit_blocked_scan', 'catunit_blocked_scan_sum', 'catunit_tridiag', 'catunit_row_alloc', 'catunit_win_alloc', 'catunit_load_row',
+           'catunit_store_row', 'catunit_load_window', 'catunit_store_window')
+
+# the bars (the header comments' own figures with the allowance of the design note, or its derivations)
+RCP1_BAR = 2 * 2.2e-15          # fast_rcp, relative
+RCP2_BAR = 2 * 1.1e-16          # fast_rcp2, nrcp, relative
+ULP_BAR = 4.0                   # expm1_sc, log1p_sc: strictly below
+B_ULP_BAR = 8.0                 # B: 4 ulp of expm1_sc, doubled for the reciprocal and the product
+DB_REL_BAR = 5e-14              # B' (Jacobian only): u^7/151200 <= 5.2e-15 against |B'| >= 0.49; ulp(1)/0.025 from 1 - B - u
+FAST_RCP_REL = 2.2e-15          # the unit of the tridiagonal forward-error bar
+SERIES_U = 0.05
+
+
+# ---- the binding ------------------------------------------------------------------------------------------------------------------
+class HarnessError(RuntimeError):
+    pass
+
+
+_lib = None
+
+
+def load_library():
+    global _lib
+    if _lib is None:
+        from catint_amd import build
+        if not os.path.exists(build.UNITTEST_LIB):
+            raise HarnessError('%s is missing: run __graft_entry__.build()' % build.UNITTEST_LIB)
+        _lib = C.CDLL(build.UNITTEST_LIB)
+        for s in SYMBOLS:
+            getattr(_lib, s).restype = C.c_int
+    return _lib
+
+
+def _in(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _p(a):
+    assert a.dtype == np.float64 and a.flags.c_contiguous
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _check(rc, what):
+    if rc != 0:
+        raise HarnessError('%s returned HIP error %d' % (what, rc))
+
+
+def scalar(name, x):
+    x = _in(x)
+    y = np.empty_like(x)
+    _check(load_library().catunit_scalar(FN[name], _p(x), _p(y), C.c_int(x.size)), 'catunit_scalar(%s)' % name)
+    return y
+
+
+def edge_flux(u):
+    """B(u) and B'(u) as lane_edge_flux(u, cl=1, cr=0, w=1) returns them in Bp and Ju"""
+    u = _in(u)
+    B, dB = np.empty_like(u), np.empty_like(u)
+    _check(load_library().catunit_edge_flux(_p(u), _p(B), _p(dB), C.c_int(u.size)), 'catunit_edge_flux')
+    return B, dB
+
+
+def wave_moves(v, old):
+    v = _in(v).reshape(-1, 64)
+    prev, nxt = np.empty_like(v), np.empty_like(v)
+    _check(load_library().catunit_wave_moves(_p(v), C.c_double(old), _p(prev), _p(nxt), C.c_int(v.shape[0])), 'catunit_wave_moves')
+    return prev, nxt
+
+
+def read_lane(v):
+    v = _in(v).reshape(64)
+    out = np.empty((64, 64))
+    _check(load_library().catunit_read_lane(_p(v), _p(out)), 'catunit_read_lane')
+    return out
+
+
+def pick_blocked(P, a):
+    a = _in(a).reshape(64 * P)
+    out = np.empty((64 * P, 64))
+    _check(load_library().catunit_pick_blocked(P, _p(a), _p(out)), 'catunit_pick_blocked')
+    return out
+
+
+def wave_scan(v, bc):
+    v = _in(v).reshape(-1, 64)
+    out = np.empty_like(v)
+    _check(load_library().catunit_wave_scan(int(bc), _p(v), _p(out), C.c_int(v.shape[0])), 'catunit_wave_scan')
+    return out
+
+
+def blocked_scan(P, rev, x):
+    x = _in(x).reshape(-1, 64 * P)
+    n = x.shape[0]
+    xo, total, base = np.empty_like(x), np.empty((n, 64)), np.empty((n, 64))
+    _check(load_library().catunit_blocked_scan(P, int(rev), _p(x), _p(xo), _p(total), _p(base), C.c_int(n)), 'catunit_blocked_scan')
+    return xo, total, base
+
+
+def blocked_scan_sum(P, x, w):
+    x = _in(x).reshape(-1, 64 * P)
+    n = x.shape[0]
+    w = _in(w).reshape(n, 64)
+    xo, total, base, wtotal = np.empty_like(x), np.empty((n, 64)), np.empty((n, 64)), np.empty((n, 64))
+    _check(load_library().catunit_blocked_scan_sum(P, _p(x), _p(w), _p(xo), _p(total), _p(base), _p(wtotal), C.c_int(n)), 'catunit_blocked_scan_sum')
+    return xo, total, base, wtotal
+
+
+def tridiag(P, G, dpp1, a, c, d):
+    """a, c, d: [ncase, G, 64 P] -> x of the same shape"""
+    a, c, d = (_in(t).reshape(-1, G, 64 * P) for t in (a, c, d))
+    assert a.shape == c.shape == d.shape
+    x = np.empty_like(d)
+    _check(load_library().catunit_tridiag(P, G, int(dpp1), _p(a), _p(c), _p(d), _p(x), C.c_int(a.shape[0])), 'catunit_tridiag')
+    return x
+
+
+def row_alloc(P):
+    return load_library().catunit_row_alloc(P)
+
+
+def win_alloc(P):
+    return load_library().catunit_win_alloc(P)
+
+
+def load_row(P, src, ldx):
+    src = _in(src)
+    out = np.empty(row_alloc(P))
+    _check(load_library().catunit_load_row(P, _p(src), C.c_int(src.size), C.c_int(ldx), _p(out)), 'catunit_load_row')
+    return out
+
+
+def store_row(P, aux, vals, dst, ldx):
+    vals, dst = _in(vals), _in(dst).copy()
+    assert vals.size == row_alloc(P)
+    _check(load_library().catunit_store_row(P, aux, _p(vals), _p(dst), C.c_int(dst.size), C.c_int(ldx)), 'catunit_store_row')
+    return dst
+
+
+LOAD_WINDOW = {'load_window<P, 0>': 0, 'load_window<P, 2>': 1, 'post::load_win<P>': 2}
+STORE_WINDOW = {'store_rows<P>': 0, 'post::store_blocked (point row)': 1, 'post::store_blocked (edge row)': 2}
+
+
+def load_window(P, which, row, nrec):
+    row = _in(row)
+    w = np.empty((64, P + 2))
+    _check(load_library().catunit_load_window(P, LOAD_WINDOW[which], _p(row), C.c_int(row.size), C.c_int(nrec), _p(w)), 'catunit_load_window')
+    return w
+
+
+def store_window(P, mode, v, dst, nrec):
+    v, dst = _in(v).reshape(64, P + 2), _in(dst).copy()
+    _check(load_library().catunit_store_window(P, STORE_WINDOW[mode], _p(v), _p(dst), C.c_int(dst.size), C.c_int(nrec)), 'catunit_store_window')
+    return dst
+
+
+# ---- multiprecision references ------------------------------------------------------------------------------------------------------
+def _hilo(values):
+    hi = np.array([float(v) for v in values])
+    lo = np.array([float(v - mpf(h)) if np.isfinite(h) else 0.0 for v, h in zip(values, hi)])
+    return hi, lo
+
+
+def ref_rcp(x):
+    return _hilo([1 / mpf(float(v)) for v in x])
+
+
+def ref_expm1(u):
+    return _hilo([MP.expm1(mpf(float(v))) for v in u])
+
+
+def ref_log1p(x):
+    return _hilo([MP.log1p(mpf(float(v))) for v in x])
+
+
+def _mp_bernoulli(v):
+    u = mpf(float(v))
+    if u == 0:
+        return mpf(1), mpf(-0.5)
+    E = MP.expm1(u)
+    B = u / E
+    return B, (1 - B - u) / E
+
+
+def ref_bernoulli(u):
+    """B(u) = u / (exp(u) - 1) as (hi, lo), and B'(u) rounded once"""
+    pairs = [_mp_bernoulli(v) for v in u]
+    hi, lo = _hilo([p[0] for p in pairs])
+    return (hi, lo), np.array([float(p[1]) for p in pairs])
+
+
+def ref_prefix(x, rev=False):
+    """exact prefix (rev: suffix) sums of the rows of x, rounded once"""
+    x = np.atleast_2d(x)
+    out = np.empty_like(x)
+    for i, row in enumerate(x):
+        row = row[::-1] if rev else row
+        acc, res = mpf(0), []
+        for v in row:
+            acc += mpf(float(v))
+            res.append(float(acc))
+        out[i] = res[::-1] if rev else res
+    return out
+
+
+def ref_thomas(a, c, d, m):
+    """the m real rows a[r] x[r-1] + x[r] + c[r] x[r+1] = d[r] (a[0] and c[m-1] do not enter) solved in multiprecision, rounded once"""
+    a, c, d = ([mpf(float(v)) for v in t[:m]] for t in (a, c, d))
+    cp, dp = [None] * m, [None] * m
+    cp[0], dp[0] = c[0], d[0]
+    for i in range(1, m):
+        piv = 1 - a[i] * cp[i - 1]
+        cp[i] = c[i] / piv
+        dp[i] = (d[i] - a[i] * dp[i - 1]) / piv
+    x = [None] * m
+    x[m - 1] = dp[m - 1]
+    for i in range(m - 2, -1, -1):
+        x[i] = dp[i] - cp[i] * x[i + 1]
+    return np.array([float(v) for v in x])
+
+
+# ---- arguments (shared by the CPU and the GPU tests; every set stays below 2^16) ---------------------------------------------------------
+def neighbours(x, n):
+    """the n doubles below x, x itself and the n doubles above it"""
+    lo, hi = [x], [x]
+    for _ in range(n):
+        lo.append(np.nextafter(lo[-1], -np.inf))
+        hi.append(np.nextafter(hi[-1], np.inf))
+    return np.array(lo[:0:-1] + [x] + hi[1:])
+
+
+def rcp_args():
+    mag = np.logspace(-150, 150, 12000)
+    near = np.concatenate([np.linspace(0.5, 2.0, 2048), np.random.default_rng(11).uniform(0.5, 2.0, 2048)])
+    return np.concatenate([mag, -mag, near])
+
+
+def expm1_args():
+    """inside the clamps: |u| in [0.05, 709] (-60 on the negative side, where the result is -1 to the last bit anyway)"""
+    mag = np.logspace(np.log10(0.05), np.log10(709.0), 6000)
+    mag[0], mag[-1] = 0.05, 709.0
+    ties = np.concatenate([neighbours((k + 0.5) * np.log(2.0), 256) for k in range(-4, 5)])
+    ties = ties[np.abs(ties) >= 0.05]
+    edge = np.concatenate([neighbours(-60.0, 4), neighbours(709.0, 4)[:5], [0.05, -0.05]])
+    return np.concatenate([mag, -mag, ties, edge])
+
+
+EXPM1_BELOW = np.array([np.nextafter(-60.0, -np.inf), -60.5, -61.0, -100.0, -745.2, -1e4, -1e308, -np.inf])      # exactly -1.0
+EXPM1_ABOVE = np.array([np.nextafter(709.0, np.inf), 709.5, 710.0, 1e3, 1e308, np.inf])                           # +inf
+
+
+def log1p_args():
+    """x = -f and x = -(1 - f) (volume fractions near 0 and near 1; the latter only where it is above -1), x = 1 - f, the doubles around
+    the switch of the mantissa range at 1 + x = sqrt(1/2), and 0"""
+    f = np.logspace(-18, -1, 6000)
+    near1 = -(1.0 - f)
+    near1 = near1[near1 > -1.0]
+    return np.concatenate([-f, near1, 1.0 - f, -neighbours(1.0 - np.sqrt(0.5), 256), [0.0]])
+
+
+def bernoulli_args():
+    mag = np.logspace(-12, np.log10(700.0), 6000)
+    mag[-1] = 700.0
+    sw = neighbours(SERIES_U, 2048)
+    return np.concatenate([mag, -mag, [0.0], sw, -sw])
+
+
+# ---- assertion helpers: pure functions of arrays --------------------------------------------------------------------------------------
+def ulp_error(got, ref):
+    """|got - exact| in ulp of the exact value; ref = (hi, lo) with hi + lo exact, or one rounded array"""
+    hi, lo = ref if isinstance(ref, tuple) else (ref, 0.0)
+    got, hi = np.asarray(got, float), np.asarray(hi, float)
+    with np.errstate(invalid='ignore', over='ignore'):
+        err = np.abs((got - hi) - lo) / np.spacing(np.abs(hi))
+    same = (got == hi) | (np.isnan(got) & np.isnan(hi))          # equal infinities
+    return np.where(same & ~np.isfinite(hi), 0.0, np.where(np.isnan(err), np.inf, err))
+
+
+def check_ulp(got, ref, bar, args=None, strict=False, what=''):
+    """every error <= bar ulp (strict: < bar); returns (worst, its argument)"""
+    err = ulp_error(got, ref)
+    k = int(np.argmax(err))
+    worst, at = float(err[k]), (None if args is None else float(np.asarray(args)[k]))
+    ok = worst < bar if strict else worst <= bar
+    assert ok, '%s: %.3f ulp at %r, bar %s%g' % (what, worst, at, '< ' if strict else '', bar)
+    return worst, at
+
+
+def rel_error(got, ref):
+    hi, lo = ref if isinstance(ref, tuple) else (ref, 0.0)
+    got, hi = np.asarray(got, float), np.asarray(hi, float)
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        err = np.abs((got - hi) - lo) / np.abs(hi)
+    return np.where(np.isnan(err), np.inf, err)
+
+
+def check_rel(got, ref, bar, args=None, what=''):
+    err = rel_error(got, ref)
+    k = int(np.argmax(err))
+    worst, at = float(err[k]), (None if args is None else float(np.asarray(args)[k]))
+    assert worst <= bar, '%s: relative error %.3e at %r, bar %g' % (what, worst, at, bar)
+    return worst, at
+
+
+def check_bernoulli_switch(u, B, bar=B_ULP_BAR):
+    """the last series value below |u| = 0.05 and the first value of the other branch lie within `bar` ulp of each other; returns
+    {+0.05: (series value, other value, distance in ulp), -0.05: ...}"""
+    u, B = np.asarray(u), np.asarray(B)
+    out = {}
+    for s in (1.0, -1.0):
+        inner, outer = np.nextafter(s * SERIES_U, 0.0), s * SERIES_U
+        (ki,), (ko,) = np.nonzero(u == inner)[0][:1], np.nonzero(u == outer)[0][:1]
+        dist = abs(B[ki] - B[ko]) / np.spacing(max(B[ki], B[ko]))
+        assert dist <= bar, 'B jumps by %.2f ulp at u = %+.2f (%r -> %r)' % (dist, outer, B[ki], B[ko])
+        out[outer] = (float(B[ki]), float(B[ko]), float(dist))
+    return out
+
+
+def check_bernoulli_balance(u, B, bar=B_ULP_BAR):
+    """|B(-u) - (B(u) + u)| <= bar ulp of max(B(u), B(-u)) for every u > 0 whose mirror image is among the arguments; the combination is
+    formed in extended precision, so what is measured is the two function values.  Returns (worst in ulp, its u)"""
+    u, B = np.asarray(u), np.asarray(B)
+    index = {v: k for k, v in enumerate(u)}
+    pos = [k for k, v in enumerate(u) if v > 0 and -v in index]
+    neg = [index[-u[k]] for k in pos]
+    assert len(pos) > 1000
+    L = np.longdouble
+    gap = np.abs(L(B[neg]) - (L(B[pos]) + L(u[pos]))).astype(float) / np.spacing(np.maximum(B[pos], B[neg]))
+    k = int(np.argmax(gap))
+    assert gap[k] <= bar, 'detailed balance: B(-u) - (B(u) + u) is %.2f ulp at u = %r' % (gap[k], u[pos[k]])
+    return float(gap[k]), float(u[pos[k]])
+
+
+def check_scan_onehot(out, rev=False):
+    """out[i] = scan of the i-th unit vector: the step function from element i on (rev: up to element i), exactly"""
+    n = out.shape[0]
+    assert out.shape == (n, n)
+    want = np.triu(np.ones((n, n))) if not rev else np.tril(np.ones((n, n)))
+    bad = np.argwhere(out != want)
+    assert bad.size == 0, 'input e_%d: element %d is %r' % (bad[0][0], bad[0][1], out[tuple(bad[0])])
+
+
+def check_blocked_scan(x, xo, total, base, P, rev=False):
+    """exact (integer-valued or one-hot input): xo the inclusive prefix (rev: suffix) sums, total the sum in every lane, base what the lane
+    inherited from the lanes before (rev: after) it -- 0 in lane 0 (rev: lane 63)"""
+    x = np.atleast_2d(x)
+    want = np.cumsum(x[:, ::-1], axis=1)[:, ::-1] if rev else np.cumsum(x, axis=1)
+    bad = np.argwhere(xo != want)
+    assert bad.size == 0, 'case %d element %d: %r, expected %r' % (bad[0][0], bad[0][1], xo[tuple(bad[0])], want[tuple(bad[0])])
+    assert np.array_equal(total, np.repeat(x.sum(axis=1)[:, None], 64, axis=1)), 'total'
+    lane_sum = x.reshape(x.shape[0], 64, P).sum(axis=2)
+    if rev:
+        wb = np.concatenate([np.cumsum(lane_sum[:, ::-1], axis=1)[:, ::-1][:, 1:], np.zeros((x.shape[0], 1))], axis=1)
+    else:
+        wb = np.concatenate([np.zeros((x.shape[0], 1)), np.cumsum(lane_sum, axis=1)[:, :-1]], axis=1)
+    assert np.array_equal(base, wb), 'base'
+    assert np.all(base[:, 63 if rev else 0] == 0.0)
+
+
+def check_scan_bound(x, xo, ref, P):
+    """random doubles: |xo - exact prefix sum| <= (P + 6) 2^-53 sum|x| (P serial plus 6 tree additions); returns the worst error / bar"""
+    x = np.atleast_2d(x)
+    bar = (P + 6) * 2.0 ** -53 * np.abs(x).sum(axis=1)[:, None]
+    ratio = float((np.abs(xo - ref) / bar).max())
+    assert ratio <= 1.0, 'prefix sums off by %.2f of the bound (P + 6) 2^-53 sum|x|' % ratio
+    return ratio
+
+
+def check_load(out, src, ldx):
+    """out = what a load through a resource of ldx doubles returned: the source below ldx, 0.0 from ldx on (never what lies behind)"""
+    n = out.size
+    want = np.where(np.arange(n) < ldx, src[:n], 0.0)
+    bad = np.nonzero(out != want)[0]
+    assert bad.size == 0, 'ldx %d: element %d reads %r, expected %r' % (ldx, bad[0], out[bad[0]], want[bad[0]])
+
+
+def check_store(after, before, vals, ldx):
+    """after = the buffer a row of vals was stored into through a resource of ldx doubles: vals below ldx, untouched from ldx on"""
+    want = before.copy()
+    want[:ldx] = vals[:ldx]
+    bad = np.nonzero(after != want)[0]
+    assert bad.size == 0, 'ldx %d: element %d holds %r, expected %r' % (ldx, bad[0], after[bad[0]], want[bad[0]])
+
+
+def check_window_load(w, row, nrec, P):
+    idx = np.arange(64)[:, None] * P + np.arange(P + 2)[None, :]
+    want = np.where(idx < nrec, row[np.minimum(idx, row.size - 1)], 0.0)
+    bad = np.argwhere(w != want)
+    assert bad.size == 0, 'resource of %d doubles: lane %d position %d reads %r, expected %r' % (nrec, bad[0][0], bad[0][1], w[tuple(bad[0])], want[tuple(bad[0])])
+
+
+def window_store_expected(before, v, nrec, P, mode):
+    want = before.copy()
+    edge = STORE_WINDOW[mode] == 2
+    for lane in range(64):
+        for j in range(P):
+            i = lane * P + j + (0 if edge else 1)
+            if i < nrec:
+                want[i] = v[lane, j + (0 if edge else 1)]
+    return want
+
+
+def check_window_store(after, before, v, nrec, P, mode):
+    want = window_store_expected(before, v, nrec, P, mode)
+    bad = np.nonzero(after != want)[0]
+    assert bad.size == 0, 'resource of %d doubles: element %d holds %r, expected %r' % (nrec, bad[0], after[bad[0]], want[bad[0]])
+
+
+def dense(a, c, m):
+    T = np.eye(m)
+    T[np.arange(1, m), np.arange(m - 1)] = a[1:m]
+    T[np.arange(m - 1), np.arange(1, m)] = c[:m - 1]
+    return T
+
+
+def tridiag_bar(a, c, m, P):
+    """kappa_inf(T) (P + 6) 2.2e-15, T the dense matrix of the m real rows"""
+    return float(np.linalg.cond(dense(a, c, m), np.inf)) * (P + 6) * FAST_RCP_REL
+
+
+def check_tridiag(a, c, d, x_hat, P, m=None, x_ref=None, bar=None):
+    """forward error of the real rows against the multiprecision solution: max|x_hat - x| / max|x| <= kappa_inf(T) (P + 6) 2.2e-15.
+    Returns error / bar.  (x_ref and bar may be handed in when they are already known: they depend on the system alone)"""
+    m = 64 * P if m is None else m
+    x_ref = ref_thomas(a, c, d, m) if x_ref is None else x_ref
+    bar = tridiag_bar(a, c, m, P) if bar is None else bar
+    err = np.abs(np.asarray(x_hat)[:m] - x_ref).max() / np.abs(x_ref).max()
+    ratio = float(err / bar) if np.isfinite(err) else np.inf
+    assert ratio <= 1.0, 'forward error %.3e is %.2f of the bar %.3e (P = %d, m = %d)' % (err, ratio, bar, P, m)
+    return ratio
+
+
+# ---- the tridiagonal systems --------------------------------------------------------------------------------------------------------
+CLASSES = ('dominant', 'cn r=1', 'cn r=1e2', 'cn r=1e4', 'cn r=1 alt', 'cn r=1e2 alt', 'cn r=1e4 alt')
+CN_CLASSES = CLASSES[1:]
+
+
+def row_counts(P):
+    return (64, 63, 3) if P == 1 else (64 * P, 64 * P - 1, 32 * P + 1)
+
+
+class TriSystem(object):
+    """One padded system of 64 P rows, m of them real: unit diagonal, a[0] = 0, c[m-1] = 0.  a, c, d: the padded rows continue the real
+    ones, as step_kernel leaves them (its rows r >= m come out of the same stencil on finite inputs: pnp_kernels.hip); a2, c2, d2: a
+    second finite filling of the rows r >= m (all three changed)."""
+
+    def __init__(self, P, m, cls, g):
+        n = 64 * P
+        rng = np.random.default_rng([P, m, CLASSES.index(cls), g])
+        j = np.arange(n)
+        if cls == 'dominant':            # (i) |a| + |c| <= 0.5, random signs
+            tot, split = rng.uniform(0.05, 0.5, n), rng.uniform(0.0, 1.0, n)
+            a = tot * split * rng.choice([-1.0, 1.0], n)
+            c = tot * (1.0 - split) * rng.choice([-1.0, 1.0], n)
+            d = rng.uniform(-1.0, 1.0, n)
+        else:                            # (ii) the Crank-Nicolson limit, r = D dt/dx^2, drift skew s varying along the row
+            r = float(cls.split('=')[1].split()[0])
+            s = 0.2 * np.sin(2.0 * np.pi * (1 + g) * j / n + 0.7 * g) * rng.uniform(0.5, 1.0, n)
+            a = -(r / 2.0) * (1.0 - s) / (1.0 + r)
+            c = -(r / 2.0) * (1.0 + s) / (1.0 + r)
+            d = 1.0 + 0.5 * np.cos(2.0 * np.pi * (2 + g) * j / n) + 0.01 * rng.uniform(-1.0, 1.0, n)
+            if cls.endswith('alt'):      # (iii) d of alternating sign
+                d = d * np.where(j % 2, -1.0, 1.0)
+        a[0] = 0.0
+        c[m - 1] = 0.0
+        self.P, self.m, self.cls, self.g = P, m, cls, g
+        self.a, self.c, self.d = a, c, d
+        self.a2, self.c2, self.d2 = a.copy(), c.copy(), d.copy()
+        if m < n:
+            k = n - m
+            tot, split = rng.uniform(0.05, 0.5, k), rng.uniform(0.0, 1.0, k)
+            self.a2[m:] = tot * split * rng.choice([-1.0, 1.0], k)
+            self.c2[m:] = tot * (1.0 - split) * rng.choice([-1.0, 1.0], k)
+            self.d2[m:] = rng.uniform(-3.0, 3.0, k)
+            assert not np.any(self.a2[m:] == a[m:]) and not np.any(self.c2[m:] == c[m:]) and not np.any(self.d2[m:] == d[m:])
+        self.x_ref = ref_thomas(a, c, d, m)
+        self.bar = tridiag_bar(a, c, m, P)
+
+
+@functools.lru_cache(maxsize=None)
+def system(P, m, cls, g):
+    return TriSystem(P, m, cls, g)
+
+
+def systems(P):
+    """every system of one P: the three row counts, the seven coefficient classes, three systems each (the G of a call)"""
+    return [system(P, m, cls, g) for m in row_counts(P) for cls in CLASSES for g in range(3)]
+
+
+# ---- plain fp64 emulations and their mutants ------------------------------------------------------------------------------------------
+SEED_REL = 4.6e-8          # the bare v_rcp_f64 seed (pnp_wave.h: fast_rcp)
+
+
+def emul_tridiag(a, c, d, rcp_rel=0.0):
+    """fp64 Thomas solve of ALL padded rows, the way the device solves them (no row count: a non-zero c[m-1] lets the padding in);
+    a, c, d: [..., n].  rcp_rel: relative error of every reciprocal, of alternating sign (the mutant: SEED_REL)"""
+    a, c, d = (np.asarray(t, float) for t in (a, c, d))
+    n = d.shape[-1]
+    cp, dp, x = np.empty_like(d), np.empty_like(d), np.empty_like(d)
+    cp[..., 0], dp[..., 0] = c[..., 0], d[..., 0]
+    for i in range(1, n):
+        r = (1.0 / (1.0 - a[..., i] * cp[..., i - 1])) * (1.0 + (rcp_rel if i % 2 else -rcp_rel))
+        cp[..., i] = c[..., i] * r
+        dp[..., i] = (d[..., i] - a[..., i] * dp[..., i - 1]) * r
+    x[..., n - 1] = dp[..., n - 1]
+    for i in range(n - 2, -1, -1):
+        x[..., i] = dp[..., i] - cp[..., i] * x[..., i + 1]
+    return x
+
+
+def emul_bernoulli(u, k30240=1.0 / 30240.0):
+    """the device's formulas in fp64 NumPy (libm expm1, true division); k30240: the u^6 coefficient of the series"""
+    u = np.asarray(u, float)
+    small = np.abs(u) < SERIES_U
+    us = np.where(small, u, 0.0)
+    u2 = us * us
+    Bs = 1.0 - 0.5 * us + u2 * (1.0 / 12.0 + u2 * (-1.0 / 720.0 + u2 * k30240))
+    dBs = -0.5 + us * (1.0 / 6.0 + u2 * (-1.0 / 180.0 + u2 * (1.0 / 5040.0)))
+    ul = np.where(small, 1.0, u)
+    with np.errstate(over='ignore', invalid='ignore'):
+        rE = 1.0 / np.expm1(ul)
+        Bl = ul * rE
+        dBl = (1.0 - Bl - ul) * rE
+    return np.where(small, Bs, Bl), np.where(small, dBs, dBl)
+
+
+SCAN_STAGES = ('row_shr:1', 'row_shr:2', 'row_shr:4', 'row_shr:8', 'row_bcast:15', 'row_bcast:31')
+
+
+def emul_wave_scan(v, skip=None, bcast31_rows=(2, 3)):
+    """the six DPP stages of wave_scan_incl on [ncase, 64]; skip: index of a stage left out; bcast31_rows: the rows its last stage writes"""
+    v = np.array(np.atleast_2d(v), float)
+    lane = np.arange(64)
+    for k, s in enumerate((1, 2, 4, 8)):
+        if skip == k:
+            continue
+        src = np.where((lane % 16 >= s)[None, :], np.roll(v, s, axis=1), 0.0)
+        v = v + src
+    if skip != 4:
+        add = np.zeros_like(v)
+        for row in (1, 3):
+            add[:, 16 * row:16 * row + 16] = v[:, 16 * row - 1][:, None]
+        v = v + add
+    if skip != 5:
+        add = np.zeros_like(v)
+        for row in bcast31_rows:
+            add[:, 16 * row:16 * row + 16] = v[:, 31][:, None]
+        v = v + add
+    return v
+
+
+def emul_blocked_scan(x, P, rev=False, skip=None):
+    """blocked_scan in fp64: P - 1 serial additions per lane, six Hillis-Steele stages across the lanes (skip: one left out), the base
+    added to every element.  Returns xo [ncase, 64 P], total [ncase, 64], base [ncase, 64]"""
+    x = np.array(np.atleast_2d(x), float)
+    n = x.shape[0]
+    if rev:
+        xo, total, base = emul_blocked_scan(x[:, ::-1], P, False, skip)
+        return xo[:, ::-1], total, base[:, ::-1]
+    b = x.reshape(n, 64, P).copy()
+    for j in range(1, P):
+        b[:, :, j] += b[:, :, j - 1]
+    inc = b[:, :, P - 1].copy()
+    for k in range(6):
+        if skip == k:
+            continue
+        s = 1 << k
+        sh = np.zeros_like(inc)
+        sh[:, s:] = inc[:, :-s]
+        inc = inc + sh
+    base = np.concatenate([np.zeros((n, 1)), inc[:, :-1]], axis=1)
+    b += base[:, :, None]
+    return b.reshape(n, 64 * P), np.repeat(inc[:, 63:64], 64, axis=1), base
+
+
+def emul_load(src, ldx, n, overrun=0):
+    """n doubles read through a resource of ldx doubles (overrun: the range check ends that many doubles late)"""
+    return np.where(np.arange(n) < ldx + overrun, src[:n], 0.0)
+
+
+def emul_store(before, vals, ldx, overrun=0):
+    after = before.copy()
+    after[:ldx + overrun] = vals[:ldx + overrun]
+    return after
+
+
+def emul_window_load(row, nrec, P, overrun=0):
+    idx = np.arange(64)[:, None] * P + np.arange(P + 2)[None, :]
+    return np.where(idx < nrec + overrun, row[np.minimum(idx, row.size - 1)], 0.0)
+
+
+CANARY = 1e300
+
+
+def canaries(n, first=0):
+    """distinct, non-zero, recognisable values for the slack behind a resource's end"""
+    return -(CANARY + 1e285 * (first + np.arange(n)))
+
+
+def distinct(n, first=1):
+    """distinct non-zero source values"""
+    return (first + np.arange(n)) + 0.25

@@ -14,6 +14,7 @@ LIBRARIES = {
     'pnp': (build.CSRC, build.SOURCES, build.HEADERS),
     'observe': (build.OBSERVE_DIR, build.OBSERVE_SOURCES, build.OBSERVE_HEADERS),
     'balance': (build.BALANCE_DIR, build.BALANCE_SOURCES, build.BALANCE_HEADERS),
+    'unittest': (build.UNITTEST_DIR, build.UNITTEST_SOURCES, build.UNITTEST_HEADERS),
 }
 
 
