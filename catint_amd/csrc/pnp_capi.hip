@@ -1894,7 +1894,7 @@ static int eval_mol_rhs(pnp_handle* h, const double* y, double* f) {
     DevArgs ay = a;
     ay.c = const_cast<double*>(y);
     if (a.use_mig) {
-      HIP_TRY(h, launch_charge_row(ay, h->mol_lapl, h->stream));
+      HIP_TRY(h, launch_charge_row(ay, h->mol_lapl, h->stream, false));   // products rounded one by one, as in mol_rhs_kernel
       HIP_TRY(h, launch_poisson(a, h->mol_lapl, h->v, h->gradv, h->stream));
     }
     HIP_TRY(h, launch_mol_rhs_pointwise(a, y, h->gradv, f, h->stream));

@@ -144,7 +144,7 @@ hipError_t launch_step_rr(const DevArgs& a, int W, hipStream_t stream);
 // solve; same applicability as the register-resident kernel.  mode 0: registers only, 1: charge / gradient rows of the step in LDS
 hipError_t launch_step_st(const DevArgs& a, int mode, hipStream_t stream);
 // lapl[b][i] = -sum_k q_k c[b][k][i]/eps for all nx points (initial charge row, calculator_old.py:767-771)
-hipError_t launch_charge_row(const DevArgs& a, double* lapl, hipStream_t stream);
+hipError_t launch_charge_row(const DevArgs& a, double* lapl, hipStream_t stream, bool fused = true);
 // v, grad_v [B][ldx] from a lapl row (get_potential_and_gradient, calculator_old.py:773-803)
 hipError_t launch_poisson(const DevArgs& a, const double* lapl, double* v, double* gradv, hipStream_t stream);
 // rates[b][k][i] (get_rates, calculator_old.py:159-208)

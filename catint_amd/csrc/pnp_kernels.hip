@@ -1441,6 +1441,13 @@ __global__ __launch_bounds__(64) void poisson_kernel(const DevArgs A, const doub
 // states y[b][k][i].  One wave per operating point, rows staged through LDS like step_kernel; every
 // Poisson boundary combination is supported.  LDS = 3 padded rows (LV | GV | ROW).
 // ------------------------------------------------------------------------------------------------
+// acc - a * b with the product rounded before the subtraction (never a fused multiply-add)
+__device__ __forceinline__ double sub_rounded_product(double acc, double a, double b) {
+#pragma clang fp contract(off)
+  const double p = a * b;
+  return acc - p;
+}
+
 template <int P>
 __global__ __launch_bounds__(64) void mol_rhs_kernel(const DevArgs A, const double* __restrict__ y,
                                                       double* __restrict__ dydt) {
@@ -1471,8 +1478,11 @@ __global__ __launch_bounds__(64) void mol_rhs_kernel(const DevArgs A, const doub
       const double qe = A.spec[k].qe;
 #pragma unroll
       for (int it = 0; it < IT; ++it) {
-        acc[it].x = __builtin_fma(-rr.t[it].x, qe, acc[it].x);
-        acc[it].y = __builtin_fma(-rr.t[it].y, qe, acc[it].y);
+        // every product rounded on its own, not fused into the sum: the charge row is then exactly odd in the charges, and a state
+        // whose charges cancel term by term (a symmetric electrolyte at any uniform concentration) has a charge row of exactly zero,
+        // as in the reference's arithmetic -- a fused sum leaves the rounding residue of the last product behind
+        acc[it].x = sub_rounded_product(acc[it].x, rr.t[it].x, qe);
+        acc[it].y = sub_rounded_product(acc[it].y, rr.t[it].y, qe);
       }
     }
 #pragma unroll
@@ -1562,8 +1572,9 @@ __global__ void mol_rhs_pointwise_kernel(const DevArgs A, const double* __restri
   dydt[idx] = out;
 }
 
-// lapl[b][i] = -sum_k q_k c[b][k][i]/eps  (:767-771), thread per grid point
-__global__ void charge_row_kernel(const DevArgs A, double* __restrict__ lapl) {
+// lapl[b][i] = -sum_k q_k c[b][k][i]/eps  (:767-771), thread per grid point.  fused: the sum of the step kernels (fused multiply-adds);
+// otherwise every product is rounded on its own, as in mol_rhs_kernel (the method of lines on grids beyond one wave)
+__global__ void charge_row_kernel(const DevArgs A, double* __restrict__ lapl, const int fused) {
   const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t total = A.B * A.ldx;
   if (idx >= total) return;
@@ -1571,7 +1582,10 @@ __global__ void charge_row_kernel(const DevArgs A, double* __restrict__ lapl) {
   const int i = (int)(idx - b * A.ldx);
   double acc = 0.0;
   if (i < A.nx) {
-    for (int k = 0; k < A.N; ++k) acc = __builtin_fma(-A.c[(b * A.N + k) * (int64_t)A.ldx + i], A.spec[k].qe, acc);
+    for (int k = 0; k < A.N; ++k) {
+      const double c = A.c[(b * A.N + k) * (int64_t)A.ldx + i];
+      acc = fused ? __builtin_fma(-c, A.spec[k].qe, acc) : sub_rounded_product(acc, c, A.spec[k].qe);
+    }
   }
   lapl[idx] = acc;
 }
@@ -1833,11 +1847,11 @@ hipError_t launch_mol_rhs(const DevArgs& a, const double* y, double* dydt, hipSt
   return hipGetLastError();
 }
 
-hipError_t launch_charge_row(const DevArgs& a, double* lapl, hipStream_t stream) {
+hipError_t launch_charge_row(const DevArgs& a, double* lapl, hipStream_t stream, bool fused) {
   const int64_t total = a.B * a.ldx;
   const int threads = 256;
   const unsigned blocks = (unsigned)((total + threads - 1) / threads);
-  hipLaunchKernelGGL(charge_row_kernel, dim3(blocks), dim3(threads), 0, stream, a, lapl);
+  hipLaunchKernelGGL(charge_row_kernel, dim3(blocks), dim3(threads), 0, stream, a, lapl, fused ? 1 : 0);
   return hipGetLastError();
 }
 

@@ -33,6 +33,22 @@ enum { PH_INIT = 0, PH_RESUME, PH_F0, PH_RHO, PH_HINIT, PH_STAGE, PH_FINAL };
 enum { ACT_NONE = 0, ACT_DECIDE, ACT_RHO, ACT_HINIT, ACT_STEP };
 
 // block-wide sums of two values (tree; every thread returns the totals)
+// Element-wise arithmetic of the states is written with explicitly rounded products and sums (no fused multiply-add), in the order
+// oracle/rkc.py evaluates it: at tolerances near the precision of the states (rtol 1e-12) the error estimate is a difference at the
+// rounding level, and a contracted stage recurrence changed it by a percent -- other step sizes than the restatement's.
+__device__ __forceinline__ double mul(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ double add(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double sub(double a, double b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
 __device__ __forceinline__ void block_sum2(double& a, double& b, double* red) {
   const int t = threadIdx.x;
   red[t] = a;
@@ -151,7 +167,7 @@ __global__ __launch_bounds__(TPB) void rkc_advance_kernel(const RkcArgs A) {
     const double sc = sh_a;
     __syncthreads();
     if (r == 0) {
-      for (int e = tid; e < n; e += TPB) ev[off(e)] = arg[off(e)] - yn[off(e)];
+      for (int e = tid; e < n; e += TPB) ev[off(e)] = sub(arg[off(e)], yn[off(e)]);
       if (tid == 0) {
         s[RKI_HAVE_EV] = 1;
         s[RKI_JACATT] = 1;
@@ -159,10 +175,10 @@ __global__ __launch_bounds__(TPB) void rkc_advance_kernel(const RkcArgs A) {
       }
       act = s[RKI_FIRST] ? ACT_HINIT : ACT_STEP;
     } else if (r == 1) {
-      for (int e = tid; e < n; e += TPB) arg[off(e)] = yn[off(e)] + (F[off(e)] - fn[off(e)]) * sc;
+      for (int e = tid; e < n; e += TPB) arg[off(e)] = add(yn[off(e)], mul(sub(F[off(e)], fn[off(e)]), sc));
     } else if (r == 2) {
       const double sq = sqrt(UROUND);
-      for (int e = tid; e < n; e += TPB) arg[off(e)] = yn[off(e)] + yn[off(e)] * sq;
+      for (int e = tid; e < n; e += TPB) arg[off(e)] = add(yn[off(e)], mul(yn[off(e)], sq));
     } else if (tid == 0) {
       s[RKI_IDID] = -6;
       s[RKI_ACTIVE] = 0;
@@ -207,7 +223,7 @@ __global__ __launch_bounds__(TPB) void rkc_advance_kernel(const RkcArgs A) {
     for (int e = tid; e < n; e += TPB) {
       const size_t o = off(e);
       const double yjm1 = arg[o];
-      const double y = mu * yjm1 + nu * yjm2[o] + c0 * yn[o] + hm * (F[o] - ajm1 * fn[o]);
+      const double y = add(add(add(mul(mu, yjm1), mul(nu, yjm2[o])), mul(c0, yn[o])), mul(hm, sub(F[o], mul(ajm1, fn[o]))));
       yjm2[o] = yjm1;
       arg[o] = y;
     }
@@ -231,7 +247,7 @@ __global__ __launch_bounds__(TPB) void rkc_advance_kernel(const RkcArgs A) {
       const size_t o = off(e);
       const double y0 = yn[o], y1 = arg[o];
       const double wt = A.atol + A.rtol * fmax(fabs(y1), fabs(y0));
-      const double est = 0.8 * (y0 - y1) + 0.4 * h * (fn[o] + F[o]);
+      const double est = add(mul(0.8, sub(y0, y1)), mul(0.4 * h, add(fn[o], F[o])));
       const double q = est / wt;
       q2 += q * q;
     }
@@ -320,10 +336,10 @@ __global__ __launch_bounds__(TPB) void rkc_advance_kernel(const RkcArgs A) {
     if (ynrm != 0.0 && vnrm != 0.0) {
       dynrm = ynrm * sq;
       const double sc = dynrm / vnrm;
-      for (int e = tid; e < n; e += TPB) arg[off(e)] = yn[off(e)] + v[off(e)] * sc;
+      for (int e = tid; e < n; e += TPB) arg[off(e)] = add(yn[off(e)], mul(v[off(e)], sc));
     } else if (ynrm != 0.0) {
       dynrm = ynrm * sq;
-      for (int e = tid; e < n; e += TPB) arg[off(e)] = yn[off(e)] + yn[off(e)] * sq;
+      for (int e = tid; e < n; e += TPB) arg[off(e)] = add(yn[off(e)], mul(yn[off(e)], sq));
     } else if (vnrm != 0.0) {
       dynrm = UROUND;
       const double sc = dynrm / vnrm;
@@ -350,7 +366,7 @@ __global__ __launch_bounds__(TPB) void rkc_advance_kernel(const RkcArgs A) {
     }
     __syncthreads();
     const double absh = sh_a;
-    for (int e = tid; e < n; e += TPB) arg[off(e)] = yn[off(e)] + absh * fn[off(e)];
+    for (int e = tid; e < n; e += TPB) arg[off(e)] = add(yn[off(e)], mul(absh, fn[off(e)]));
   } else if (act == ACT_STEP) {
     if (tid == 0) {
       double absh = fmin(d[RKC_ABSH], hmax);
@@ -407,7 +423,7 @@ __global__ __launch_bounds__(TPB) void rkc_advance_kernel(const RkcArgs A) {
       const size_t o = off(e);
       const double y0 = yn[o];
       yjm2[o] = y0;
-      arg[o] = y0 + hm * fn[o];
+      arg[o] = add(y0, mul(hm, fn[o]));
     }
   }
   if (tid == 0) atomicAdd(&A.counters[A.slot], 1);

@@ -181,6 +181,15 @@ CASES = [
     dict(name='odeint_dd_n3_nx40_flux_LF', method='odeint--LF', species=K_CL_HCO3, phiM=0.02, L=2e-8, nx=40,
          pb_bound=DD, dt=2e-11, tmax=2e-10, ntout=2, flux_bound=[[0, 1e-3]], capture_rhs=True,
          c0_perturb={'seed': 19, 'amp': 0.05}),
+    # --- method of lines with homogeneous reactions (the table of ftcs_dd_n3_nx40_rates) and without migration ---------------
+    dict(name='odeint_dd_n3_nx40_rates', method='odeint', species=K_CL_HCO3, phiM=0.01, L=2e-8, nx=40,
+         pb_bound=DD, dt=2e-11, tmax=2e-10, ntout=2, capture_rhs=True, c0_perturb={'seed': 13, 'amp': 0.05},
+         reactions={'r1': {'reactants': [['K+', 'Cl-'], ['HCO3-']], 'rates': [3.0e6, 2.0e8]},
+                    'r2': {'reactants': [['HCO3-', 'H2O'], ['Cl-']], 'rates': [1.0e8, 5.0e7]},
+                    'r3': {'reactants': [['K+'], ['Cl-']]}}),
+    dict(name='odeint_nomig_n2_nx50', method='odeint', species=None, phiM=-0.025, L=5e-8, nx=50,
+         pb_bound=DD, dt=1e-10, tmax=1e-9, ntout=2, use_migration=False, capture_rhs=True,
+         c0_perturb={'seed': 17, 'amp': 0.1}),
 ]
 
 

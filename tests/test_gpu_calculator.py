@@ -1,6 +1,7 @@
 """GPU: the Calculator counterpart as a drop-in for the reference's seam
 `Calculator.integrate_pnp(dx,nx,dt,nt,ntout,method)` (calculator_old.py:210), and the batched descriptor
 sweep.  Tolerance as in test_gpu_parity_golden.py (rtol 1e-9 on the max-norm; measured ~1e-13)."""
+import json
 import os
 
 import numpy as np
@@ -118,7 +119,8 @@ def test_scf_cycle_on_gpu_converges_and_is_lane_consistent():
     assert np.allclose(out1['surface_concentration'][0], out['surface_concentration'][2], rtol=1e-10)
 
 
-@pytest.mark.parametrize('name', ['odeint_dd_n2_nx50', 'odeint_dd_n3_nx40_flux_LF', 'dopri5_dd_n2_nx50'])
+@pytest.mark.parametrize('name', ['odeint_dd_n2_nx50', 'odeint_dd_n3_nx40_flux_LF', 'dopri5_dd_n2_nx50', 'odeint_dd_n3_nx40_rates',
+                                  'odeint_nomig_n2_nx50'])
 def test_method_of_lines_rhs_and_trajectories(name):
     """ode_func (calculator_old.py:827-935) on the GPU: the RHS against the reference's own RHS samples
     (rtol 1e-11 of the max-norm; the device sums in a different order), and the scipy-driven trajectories
@@ -136,6 +138,13 @@ def test_method_of_lines_rhs_and_trajectories(name):
     tp.c0 = d['c0'].copy()
     tp.flux_bound = d['flux_bound'].copy()
     tp.system['vzeta'] = float(d['vzeta'])
+    # the fixture's switches are plain attributes as well: the rate table (used by the method of lines only with use_reactions) and
+    # the migration flag
+    tp.use_migration = bool(d['use_migration'])
+    reactions = json.loads(str(d['reactions_json']))
+    if reactions:
+        tp.reactions, tp.use_reactions = reactions, True
+    assert bool(p.reactions) == ('rates' in name) and p.use_migration == ('nomig' not in name)
     ntout = next(n for n in range(1, 8) if make_itout(int(d['nt']), n) == [int(i) for i in d['itout']])
     calc = Calculator(transport=tp, calc=str(d['method']), dt=float(d['dt']), tmax=float(d['tmax']), ntout=ntout)
     cout = calc.integrate_pnp(tp.dx, tp.nx, tp.dt, tp.nt, tp.ntout, calc.calc)

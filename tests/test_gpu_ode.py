@@ -434,3 +434,174 @@ def test_rkc_grids_beyond_one_wave_empty_requests_and_argument_checks():
         sn.set_newton()
         with pytest.raises(_capi.PnpError, match='physical mode'):
             sn.integrate_rkc(1, [0])
+
+
+# ---- the integrators against a right-hand side that is NOT the device's: oracle/pnp_ref.py mol_rhs on the CPU ------------------------------
+def hairer_rejections(log, calls):
+    """NREJCT as DOPRI5 / DOP853 count it: per call, rejected steps after the call's first accepted one (log rows: x, h, err, accepted;
+    calls: the log length after every integrate())"""
+    n, lo = 0, 0
+    for hi in calls:
+        seen = False
+        for e in log[lo:hi]:
+            n += (not e[3]) and seen
+            seen = seen or e[3]
+        lo = hi
+    return n
+
+
+MOL_LANE_FLUX = np.array([[1e-3, 0.0, -2e-3], [0.0, -1e-3, 5e-4], [-2e-3, 1e-3, 0.0], [3e-3, -2e-3, 1e-3]])
+# Interval (in units of the fixture's) per integrator.  Two conditions on the inputs, both checked on the CPU alone:
+#   * the smallest |err - 1| of any accept / reject decision of the CPU oracle is 1.4e-2 (dopri5), 0.24 (dop853) and 0.19 (rkc) -- rounding
+#     differences between the two right-hand sides (1e-14) cannot flip a decision; asserted below from the oracle's log;
+#   * the trajectory is well conditioned at the 1e-9 of the comparison: the same oracle driven by two fp64 evaluations of R.mol_rhs that
+#     differ in association only (Thomas against dense LU, d2c summed in another order) lands within 8e-14 (dop853), 4e-15 (dopri5) and
+#     2e-14 (rkc) of itself.  (At 100 fixture intervals DOP853 runs at its stability limit on the migration-free fixture and those two
+#     CPU runs are 4e-9 apart after three intervals -- no right-hand side could be told from another at 1e-9 there.)
+MOL_INTERVAL = {'dopri5': 20, 'dop853': 30, 'rkc': 1000}
+
+
+@pytest.mark.parametrize('name', ['odeint_dd_n3_nx40_rates', 'odeint_nomig_n2_nx50'])
+@pytest.mark.parametrize('integ', ['dopri5', 'dop853', 'rkc'])
+def test_integrators_against_the_cpu_right_hand_side(integ, name):
+    """Homogeneous reactions resp. migration off, four lanes with their own wall potential, wall fluxes and start state: the device
+    integrator (device right-hand side) against the pinned oracle integrating R.mol_rhs on the CPU -- same attempted / accepted /
+    rejected steps and evaluation counts, trajectories to 1e-9 (the bar of test_descriptor_sweep_with_the_integrator_on_the_device)."""
+    from oracle.rkc import Rkc
+    d, p, c0, _, _ = golden_problem(name, interval=MOL_INTERVAL[integ])
+    assert bool(p.reactions) == ('rates' in name) and p.use_migration == ('nomig' not in name)
+    B, nt = 4, 3
+    cs = np.stack([c0 * f for f in (1.0, 0.7, 1.3, 1.9)])
+    pb = np.stack([p.pb] * B); pb[:, 0] = [0.01, -0.02, 0.03, -0.005]
+    flux = MOL_LANE_FLUX[:, :p.N].copy()
+    with solver_from_problem(p, 'FTCS', batch_capacity=B) as s:
+        s.set_batch(cs, pb, [p.vzeta] * B, flux)
+        run = {'dopri5': s.integrate_dopri5, 'dop853': s.integrate_dop853, 'rkc': s.integrate_rkc}[integ]
+        cout, idid, stats, t_end = run(nt, list(range(nt)), **({} if integ == 'rkc' else {'nsteps': 10000}))
+    assert (idid == 1).all()
+    margin = np.inf
+    for b in range(B):
+        q = R.Problem(**dict(p.__dict__, pb=pb[b], flux_bound=flux[b]))
+
+        def f(t, y):
+            return R.mol_rhs(y, q, use_reactions=bool(q.reactions), solver='banded')
+        o = {'dopri5': lambda: Dopri5(f, nsteps=10000), 'dop853': lambda: Dop853(f, recompute_k1=False, nsteps=10000), 'rkc': lambda: Rkc(f)}[integ]()
+        o.set_initial_value(cs[b].copy())
+        ref, calls = [], []
+        for n in range(nt):
+            ref.append(o.integrate((n + 1) * p.dt if integ == 'rkc' else o.t + p.dt).copy())
+            calls.append(len(o.log))
+        assert o.idid == 1
+        errs = np.array([e[-2] for e in o.log])
+        margin = min(margin, float(np.abs(errs - 1.0).min()))
+        assert np.abs(errs - 1.0).min() >= 1e-3           # the condition on the inputs: no decision within rounding of the threshold
+        acc = sum(1 for e in o.log if e[-1])
+        if integ == 'rkc':
+            assert list(stats[b]) == [o.nsteps, o.naccpt, o.nrejct, o.nfe, nt - 1, o.nfesig, o.maxm], b
+        else:
+            assert len(o.log) > acc                       # rejected steps among them
+            assert list(stats[b]) == [len(o.log), acc, hairer_rejections(o.log, calls), o.nfcn, nt - 1], b
+        assert abs(t_end[b] - o.t) <= 1e-13 * o.t
+        for n in range(nt):
+            assert relerr(cout[n, b], ref[n]) < 1e-9, (b, n)
+    print('MOLODE | %s | %s | smallest |err - 1| of the oracle %.3e |' % (integ, name, margin))
+
+
+def test_rkc_rejected_steps_match_the_oracle():
+    """Twelve intervals of 1e-7 s at the default tolerances: the oracle rejects a step (none of the parameter sets of
+    test_rkc_same_steps_and_stage_counts_as_the_oracle does), so the shrink 0.8 h / err^(1/3), the spectral radius NOT being
+    re-estimated after a rejection that follows a fresh estimate, and the rejection counter are compared on values that are not 0."""
+    d, p, c0, _, _ = golden_problem(interval=10000)
+    nt = 12
+    with solver_from_problem(p, 'FTCS', batch_capacity=1) as s:
+        s.set_batch(c0[None, :], p.pb[None, :], [p.vzeta], p.flux_bound[None, :])
+        o, ref = rkc_oracle_run(s, c0[None, :].copy(), 0, nt)
+        s.set_batch(c0[None, :], p.pb[None, :], [p.vzeta], p.flux_bound[None, :])
+        cout, idid, stats, t_end = s.integrate_rkc(nt, list(range(nt)))
+    print('MOLRKC | rejections | nsteps %d nrejct %d nfesig %d maxm %d |' % (o.nsteps, o.nrejct, o.nfesig, o.maxm))
+    assert o.nrejct >= 1 and o.idid == 1 and idid[0] == 1
+    assert list(stats[0]) == [o.nsteps, o.naccpt, o.nrejct, o.nfe, nt - 1, o.nfesig, o.maxm]
+    assert t_end[0] == nt * p.dt
+    for n in range(nt):
+        assert relerr(cout[n, 0], ref[n]) < 1e-10
+
+
+@pytest.mark.parametrize('rtol,rejects', [(1e-12, False), (1e-11, True)])
+def test_rkc_stage_cap(rtol, rejects):
+    """From a stationary state (one call over 1e-4 s) two intervals of 1e-6 s at tolerances whose stage limit mmax = sqrt(rtol / (10 u))
+    is 21 resp. 67: the spectral radius asks for more stages than that, so steps are cut to (mmax^2 - 1) / (1.54 rho) and `last` is
+    withdrawn; at 1e-11 a capped step is followed by a rejection."""
+    d, p, c0, _, _ = golden_problem(interval=1)
+    p.dt = 1e-4
+    with solver_from_problem(p, 'FTCS', batch_capacity=1) as s:
+        s.set_batch(c0[None, :], p.pb[None, :], [p.vzeta], p.flux_bound[None, :])
+        cst, idid, st, _ = s.integrate_rkc(1, [0], rtol=1e-6)
+    assert idid[0] == 1 and st[0][0] > 100
+    c1 = cst[0]
+    p.dt, nt, kw = 1e-6, 2, {'rtol': rtol, 'atol': 1e-14}
+    with solver_from_problem(p, 'FTCS', batch_capacity=1) as s:
+        s.set_batch(c1, p.pb[None, :], [p.vzeta], p.flux_bound[None, :])
+        o, ref = rkc_oracle_run(s, c1.copy(), 0, nt, **kw)
+        s.set_batch(c1, p.pb[None, :], [p.vzeta], p.flux_bound[None, :])
+        cout, idid, stats, t_end = s.integrate_rkc(nt, list(range(nt)), **kw)
+    capped = sum(1 for e in o.log if e[2] == o.mmax)
+    print('MOLRKC | stage cap rtol %g | mmax %d nsteps %d capped %d nrejct %d |' % (rtol, o.mmax, o.nsteps, capped, o.nrejct))
+    assert o.mmax == (21 if rtol == 1e-12 else 67) and capped >= 1 and o.maxm == o.mmax and (o.nrejct >= 1) == rejects
+    assert o.idid == 1 and idid[0] == 1
+    assert list(stats[0]) == [o.nsteps, o.naccpt, o.nrejct, o.nfe, nt - 1, o.nfesig, o.maxm] and stats[0][6] == o.mmax
+    assert t_end[0] == nt * p.dt
+    for n in range(nt):
+        assert relerr(cout[n, 0], ref[n]) < 1e-10
+
+
+# lane 1 / lane 2 of the batch below in the CPU oracle (oracle integrator on R.mol_rhs): idid, attempted steps, evaluations
+# (rkc: of the steps, of the spectral radius estimate, largest stage count)
+DEGENERATE = {'rkc': {'still': (1, 1, 4, 2, 2), 'nan': (-6, 0, 1, 50, 0)},
+              'dopri5': {'still': (1, 1, 8), 'nan': (-2, 21, 128)},
+              'dop853': {'still': (1, 1, 14), 'nan': (-2, 21, 233)}}
+
+
+@pytest.mark.parametrize('integ', ['rkc', 'dopri5', 'dop853'])
+def test_degenerate_lanes_in_a_batch(integ):
+    """Lanes 0 and 3 ordinary; lane 1 exactly stationary (the uniform neutral bulk state, wall and bulk potential 0, no flux: a
+    descriptor point at zero wall potential); lane 2 with one NaN in its state.  Lane 1 takes the oracle's single step and returns its
+    state bit for bit, lane 2 gives up with the oracle's exit and counts at t = 0, and neither changes a bit of lanes 0 and 3."""
+    d, p, c0, _, _ = golden_problem(interval=100)
+    B, N, nx = 4, p.N, p.nx
+    still = np.repeat(d['c_bulk'], nx)
+    bad = c0.copy(); bad[nx + 7] = np.nan
+    cs = np.stack([c0, still, bad, 1.2 * c0])
+    pb = np.stack([p.pb] * B); pb[:, 0] = [-0.025, 0.0, -0.025, 0.03]
+    flux = np.array([[1e-4, 0.0], [0.0, 0.0], [0.0, 0.0], [0.0, -2e-4]])
+    kw = {} if integ == 'rkc' else {'nsteps': 20}
+    q = R.Problem(**dict(p.__dict__, pb=pb[1], flux_bound=flux[1]))
+    assert not R.mol_rhs(still, q, solver='banded').any()
+    with solver_from_problem(p, 'FTCS', batch_capacity=B) as s:
+        s.set_batch(cs, pb, [p.vzeta] * B, flux)
+        f = s.mol_rhs(cs)
+        assert (f[1] == 0.0).all() and np.isnan(f[2]).any() and np.isfinite(f[[0, 3]]).all() and f[0].any() and f[3].any()
+        run = {'dopri5': s.integrate_dopri5, 'dop853': s.integrate_dop853, 'rkc': s.integrate_rkc}[integ]
+        cout, idid, stats, t_end = run(1, [0], **kw)
+    want = DEGENERATE[integ]
+    assert list(idid) == [1, want['still'][0], want['nan'][0], 1]
+    if integ == 'rkc':
+        assert (stats[1][0], stats[1][3], stats[1][5], stats[1][6]) == want['still'][1:] and tuple(stats[1][:3]) == (1, 1, 0)
+        assert (stats[2][0], stats[2][3], stats[2][5], stats[2][6]) == want['nan'][1:]
+    else:
+        assert (stats[1][0], stats[1][3]) == want['still'][1:] and tuple(stats[1][:3]) == (1, 1, 0)
+        assert (stats[2][0], stats[2][3]) == want['nan'][1:] and stats[2][1] == 0
+    assert np.array_equal(cout[0, 1], still) and t_end[1] == p.dt
+    assert t_end[2] == 0.0
+    with solver_from_problem(p, 'FTCS', batch_capacity=2) as s2:              # lanes 0 and 3 as a batch of their own
+        s2.set_batch(cs[[0, 3]], pb[[0, 3]], [p.vzeta] * 2, flux[[0, 3]])
+        run = {'dopri5': s2.integrate_dopri5, 'dop853': s2.integrate_dop853, 'rkc': s2.integrate_rkc}[integ]
+        c2, idid2, stats2, t2 = run(1, [0], **kw)
+    assert (idid2 == 1).all() and stats2[:, 0].min() >= 4
+    assert np.array_equal(c2[0], cout[0, [0, 3]]) and np.array_equal(stats2, stats[[0, 3]]) and np.array_equal(t2, t_end[[0, 3]])
+    # through the Calculator: the lane that gave up is flagged, the others are not
+    tp = transport_from_fixture(d)
+    tp.c0 = d['c0'].copy(); tp.flux_bound = d['flux_bound'].copy(); tp.system['vzeta'] = float(d['vzeta'])
+    calc = Calculator(transport=tp, calc='odeint' if integ == 'rkc' else integ, dt=p.dt, tmax=3 * p.dt, ntout=1)
+    calc.ode_options = dict(kw)
+    _, status, _ = calc.integrate_pnp_batch(cs, pb, [p.vzeta] * B, flux)
+    assert status[2] != 0 and list(status[[0, 1, 3]]) == [0, 0, 0] and calc.ode_idid[2] == want['nan'][0]

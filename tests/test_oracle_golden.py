@@ -27,9 +27,11 @@ def load(name):
 
 def test_fixture_inventory():
     # every integrator / Poisson branch / flag the reference can run is represented
-    assert len(STEPPERS) >= 13 and len(MOL) >= 2
+    assert len(STEPPERS) >= 13 and len(MOL) >= 4
     for needle in ('cn_dd', 'cn_defaultpb', 'cn_mirrorpb', '_LF', 'ftcs_dd', 'ftcs_defaultpb', 'rates', 'nomig', 'flux'):
         assert any(needle in n for n in ALL), needle
+        if needle in ('rates', 'nomig'):      # ... by a stepper and by the method of lines
+            assert any(needle in n for n in STEPPERS) and any(needle in n for n in MOL), needle
 
 
 @pytest.mark.parametrize('name', STEPPERS)
@@ -61,7 +63,7 @@ def test_banded_and_c_oracle(name):
 def test_method_of_lines_rhs(name):
     d, (p, c0, nt, itout, method) = load(name)
     for s, val in zip(d['rhs_states'], d['rhs_values']):
-        assert np.array_equal(R.mol_rhs(s, p), val)
+        assert np.array_equal(R.mol_rhs(s, p, use_reactions=bool(p.reactions)), val)
 
 
 def test_itout_rule():
