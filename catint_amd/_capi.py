@@ -255,6 +255,7 @@ class PnpSolver(object):
         self._observer = None
         self._balancer = None
         self._regridder = None
+        self._responder = None
 
     def _check(self, rc):
         if rc != 0:
@@ -273,6 +274,9 @@ class PnpSolver(object):
         if getattr(self, '_equilibrator', None) is not None:
             self._equilibrator.close()
             self._equilibrator = None
+        if getattr(self, '_responder', None) is not None:
+            self._responder.close()
+            self._responder = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -682,6 +686,47 @@ class PnpSolver(object):
         return self._balancer.species(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], flux, phiM, mpb_radius=o['mpb_radius'],
                                       velocity=o['velocity'], reactions=o['reactions'], wall=wall, fields=fields, scalars=scalars,
                                       max_waves=max_waves)
+
+    def get_response(self, omega=(0.0,), perturbation='phiM', lanes=None, profiles=False, max_waves=0):
+        """The linear response of the stationary state this handle holds (include/catint_response.h), solved on the device: how the
+        state answers a small change of the electrode potential (perturbation='phiM', per volt) or of the prescribed wall flux of
+        species k (('flux', k), per mol m^-2 s^-1), for every lane of `lanes` (None: all, in order; repeats allowed) and every angular
+        frequency of `omega` (rad/s, >= 0; 0: the exact tangent of the stationary solution).  Returns a dict of complex128 arrays:
+        'dphi_surface' [n][F], 'dc_surface' [n][F][N], 'dsigma' [n][F] (C m^-2), 'dwall_flux' [n][F][N], 'admittance' [n][F] (A m^-2),
+        with profiles 'dc' [n][F][N][nx] and 'dphi' [n][F][nx]; 'status' [n][F] (0; 1: non-finite result or vanishing pivot; 2: the
+        lane's solver status was not 0, outputs NaN); and 'omega' [F], 'impedance' = 1 / admittance (inf where the admittance is 0),
+        'differential_capacitance' [n] = Re dsigma at the first omega = 0 of the list (absent without one; F m^-2 for 'phiM').
+        D, charges, ion radii, grid, wall model, velocity, reactions, wall table and electrode potentials are the ones this solver was
+        given.  Rate constants (set_wall_kinetics k) are numbers per lane and are held fixed: a dependence of a rate on the potential is
+        part of the response only through `alpha`, never through a host function K(phiM) that produced k.  'status' 1 also marks a
+        system whose elimination met a pivot more than 1e8 times smaller than an entry below it (CATRESP_PIVOT_GROWTH_LIMIT): its
+        numbers must not be used.  The response is that of the STATIONARY operator about the state found: after a transient step it has no physical
+        meaning.  After scf_cycle the solves took the wall reactions through the prescribed flux, so the response is formed without
+        the wall table (the rule of get_balance); after a set_batch with another batch size the recorded rate constants of the wall
+        table are not the ones the handle applies: ValueError until set_wall_kinetics is called again."""
+        from . import _response
+        o = self._obs
+        wall = None if o['explicit_kinetics'] else o['wall']
+        if wall is not None and o['wall_stale']:
+            raise ValueError('get_response: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall table '
+                             'whose rate constants were not recorded for this batch: call set_wall_kinetics again')
+        if o['phiM'] is None:
+            raise ValueError('get_response: no batch was set')
+        if self._responder is None:
+            self._responder = _response.Responder(o['device'])
+        om = np.atleast_1d(np.asarray(omega, float)).reshape(-1)
+        out = self._responder.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], omega=om,
+                                    perturbation=perturbation, lanes=lanes, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
+                                    stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], wall=wall,
+                                    profiles=profiles, max_waves=max_waves)
+        out['omega'] = om.copy()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            y = out['admittance']
+            out['impedance'] = np.where(y == 0, np.inf, 1.0 / np.where(y == 0, 1.0, y))
+        zero = np.flatnonzero(om == 0.0)
+        if len(zero):
+            out['differential_capacitance'] = out['dsigma'][:, zero[0]].real.copy()
+        return out
 
     def get_status(self):
         st = np.zeros(self.B, np.int32)

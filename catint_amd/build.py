@@ -45,6 +45,13 @@ EQUIL_LIB = os.path.join(LIB_DIR, 'libcatint_equil.so')
 EQUIL_SOURCES = ['cateq.hip']
 EQUIL_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_equil.h')]
 
+# sixth library (include/catint_response.h): the linear response of a stationary state (differential capacitance, slope of the currents,
+# admittance spectrum), one block-tridiagonal solve per operating point and frequency.  A library of its own as the four before it
+RESPONSE_DIR = os.path.join(CSRC, 'response')
+RESPONSE_LIB = os.path.join(LIB_DIR, 'libcatint_response.so')
+RESPONSE_SOURCES = ['catresp.hip']
+RESPONSE_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_response.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -157,6 +164,15 @@ def equil_needs_build():
 def build_equil_library(force=False, verbose=False):
     """catint_amd/csrc/equil into catint_amd/lib/libcatint_equil.so"""
     return _build_unit(EQUIL_DIR, EQUIL_SOURCES, EQUIL_HEADERS, EQUIL_LIB, force, verbose)
+
+
+def response_needs_build():
+    return _unit_needs_build(RESPONSE_DIR, RESPONSE_SOURCES, RESPONSE_HEADERS, RESPONSE_LIB)
+
+
+def build_response_library(force=False, verbose=False):
+    """catint_amd/csrc/response into catint_amd/lib/libcatint_response.so"""
+    return _build_unit(RESPONSE_DIR, RESPONSE_SOURCES, RESPONSE_HEADERS, RESPONSE_LIB, force, verbose)
 
 
 def unittest_needs_build():

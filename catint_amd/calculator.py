@@ -89,6 +89,12 @@ class Calculator(object):
         self.physical = self.calc in PHYSICAL_CALCS
         if self.balance_on_device and not self.physical:
             raise CalculatorError('balance_on_device is part of the physical mode (calc="comsol")')
+        # physical mode, opt-in: tp.newton['response'] = True | {'omega': [...]} -- after the sweep's solve, run() takes the linear response
+        # of every lane to the electrode potential on the device (PnpSolver.get_response, include/catint_response.h) and adds the
+        # differential capacitance and the admittance spectrum to tp.alldata
+        self.response = None              # the dict of get_response of the last such run()
+        if self._response_option() is not None and not self.physical:
+            raise CalculatorError("tp.newton['response'] is part of the physical mode (calc=\"comsol\")")
         # roughness factor: every wall flux the COMSOL model prescribes is j_i = RF*flux_factor*flux_i (comsol_model.py:1000, :1134)
         self.RF = float(self.tp.system.get('RF', 1.0)) if self.physical else 1.0
         # the reference hands system['flow rate'] (a number or a COMSOL expression) to the convection velocity tds.cdm1 "u"
@@ -634,6 +640,8 @@ class Calculator(object):
         that the FD path can provide (concentration, surface_concentration, potential, efield,
         surface_potential, surface_efield, charge_density)."""
         tp = self.tp
+        if self._response_option() is not None and not self.physical:      # (tp.newton may have been set after the constructor's check)
+            raise CalculatorError("tp.newton['response'] is part of the physical mode (calc=\"comsol\")")
         keys = list(tp.descriptors.keys())
         lanes = tp.alldata_names
         B = len(lanes)
@@ -668,12 +676,19 @@ class Calculator(object):
                     self.kinetic_flux = self.surface_kinetic_fluxes(cfin[:, :, 0], phiM, vsurf=v[:, 0])
                 if self.balance_on_device:
                     self.balance = s.get_balance()
+                if self._response_option() is not None:
+                    if any(callable(r.get('rate')) and not float(r.get('alpha', 0.0)) for r in getattr(self, 'surface_kinetics', None) or []):
+                        import warnings
+                        warnings.warn("tp.newton['response']: a surface reaction's rate is a function of phiM without 'alpha'; the response "
+                                      "holds the rate constant fixed, so dK/dphiM is missing from admittance and impedance", RuntimeWarning)
+                    self.response = s.get_response(omega=self._response_option())
             cout = cfin.reshape(1, B, tp.nspecies * tp.nx)
             if derived is not None:
                 self.status = status
                 self.observables = derived['scalars']
                 self._alldata_fill(0, self._alldata_from_device(cfin, v, derived, flux, getattr(self, 'kinetic_flux', None)), status)
                 self._alldata_balance()
+                self._alldata_response()
                 return cout
         else:
             cout, status, (v, g, l) = self.integrate_pnp_batch(c0, pb, vz, flux)
@@ -682,7 +697,36 @@ class Calculator(object):
         self.fill_alldata_batch(cout[-1].reshape(B, tp.nspecies, tp.nx), v, g, l, flux, status, kf)
         if self.physical:
             self._alldata_balance()
+            self._alldata_response()
         return cout
+
+    def _response_option(self):
+        """tp.newton['response']: None when the option is off, otherwise the angular frequencies asked for ((0.0,) for True)"""
+        opt = (getattr(self.tp, 'newton', None) or {}).get('response')
+        if not opt:
+            return None
+        om = opt.get('omega', (0.0,)) if isinstance(opt, dict) else (0.0,)
+        return tuple(float(w) for w in np.atleast_1d(om))
+
+    def _alldata_response(self):
+        """tp.newton['response']: self.response into tp.alldata[i]['system'] -- 'differential_capacitance' (F/m^2 of electrode area as the
+        solver sees it; None without omega = 0 in the list), 'response_omega' [F] (rad/s), 'admittance' [F] (A m^-2 V^-1) and
+        'impedance' [F] (Ohm m^2), complex.  Like the keys of _alldata_balance these are an extension: the reference's field contract
+        (comsol_reader.py:196-326) has no counterpart for them.
+        The response holds every rate constant fixed: surface kinetics given as a rate FUNCTION K(phiM) without 'alpha' are a constant
+        per lane to the library, so dK/dphiM is missing from 'admittance' / 'impedance' (and from the polarization resistance read off
+        them).  Potential-dependent kinetics belong in 'alpha' (the Butler-Volmer form of set_surface_kinetics), which the response
+        differentiates; run() warns when a callable rate comes without one."""
+        if self._response_option() is None or self.response is None:
+            return
+        res = self.response
+        cd = res.get('differential_capacitance')
+        for b in range(len(res['admittance'])):
+            d = self.tp.alldata[b]['system']
+            d['differential_capacitance'] = None if cd is None else float(cd[b])
+            d['response_omega'] = res['omega'].copy()
+            d['admittance'] = res['admittance'][b].copy()
+            d['impedance'] = res['impedance'][b].copy()
 
     def _alldata_balance(self):
         """balance_on_device: the per-species picture of self.balance into tp.alldata -- per species 'flux' [nx-1], 'reaction_source' [nx],
