@@ -256,6 +256,7 @@ class PnpSolver(object):
         self._balancer = None
         self._regridder = None
         self._responder = None
+        self._kinetics = None
 
     def _check(self, rc):
         if rc != 0:
@@ -277,6 +278,9 @@ class PnpSolver(object):
         if getattr(self, '_responder', None) is not None:
             self._responder.close()
             self._responder = None
+        if getattr(self, '_kinetics', None) is not None:
+            self._kinetics.close()
+            self._kinetics = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -727,6 +731,47 @@ class PnpSolver(object):
         if len(zero):
             out['differential_capacitance'] = out['dsigma'][:, zero[0]].real.copy()
         return out
+
+    def get_kinetics(self, model_or_tables, phiM=None, lanes=None, csurf=None, phi_surface=None, theta_guess=None, fields=None,
+                     potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None,
+                     tol=None, maxit=None, max_waves=0):
+        """The steady state of a mean-field surface microkinetic model (include/catint_kinetics.h) solved on the device, one operating
+        point per entry of `lanes` (None: all lanes, in order; repeats allowed): coverages, step rates, the wall fluxes into the
+        electrolyte and, when asked for, their sensitivities to the surface concentrations and potentials.  model_or_tables: a
+        catint_amd.microkinetics.MeanFieldModel or the dict of its tables().  The surface state is the one this handle holds on the
+        device (nothing crosses PCIe on the way in), or csurf [n][N] and phi_surface [n] when given (what an SCF loop holds: the mixed
+        surface concentrations).  phiM [n] defaults to the electrode potentials of the selected lanes, stern_capacitance and phi_pzc to
+        the ones this solver was given (set_newton); sigma [n], off [n][R][2], gamma [n][N] and theta_guess [n][S+1] are per selected
+        point.  fields: names out of catint_amd._kinetics.FIELDS (None: 'theta', 'rate', 'rate_gross', 'flux', 'flux_scale'; also
+        'dflux_dc' [n][N][N], 'dflux_dphi' [n][N][2]).  Returns a dict of these arrays and 'status' [n] (0 converged; 1 stopped at
+        maxit; 2 the lane's solver status is not 0 or an input is not finite: NaN; 3 a zero or non-finite pivot), 'iterations' [n].
+        The number of digits of 'flux' is what flux / flux_scale leaves of 16."""
+        from . import _kinetics
+        o = self._obs
+        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
+        if site_density is not None:
+            tables['site_density'] = float(site_density)
+        host = csurf is not None or phi_surface is not None
+        if lanes is not None:
+            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        elif host and phiM is not None:
+            idx = None
+        else:
+            idx = np.arange(self.B, dtype=np.int64)
+        if phiM is None:
+            if o['phiM'] is None:
+                raise ValueError('get_kinetics: no batch was set')
+            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+                raise ValueError('get_kinetics: lane index outside [0, %d)' % self.B)
+            phiM = np.asarray(o['phiM'], float)[idx]
+        if self._kinetics is None:
+            self._kinetics = _kinetics.KineticsSolver(o['device'])
+        return self._kinetics.solve(None if host else self.device_view(), tables, phiM, lanes=None if host else idx, csurf=csurf,
+                                    phi_surface=phi_surface, potential_drop=potential_drop,
+                                    stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
+                                    phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma,
+                                    theta_guess=theta_guess, tol=_kinetics.DEFAULT_TOL if tol is None else tol,
+                                    maxit=_kinetics.DEFAULT_MAXIT if maxit is None else maxit, fields=fields, max_waves=max_waves)
 
     def get_status(self):
         st = np.zeros(self.B, np.int32)

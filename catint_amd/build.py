@@ -52,6 +52,13 @@ RESPONSE_LIB = os.path.join(LIB_DIR, 'libcatint_response.so')
 RESPONSE_SOURCES = ['catresp.hip']
 RESPONSE_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_response.h')]
 
+# seventh library (include/catint_kinetics.h): the steady state of a mean-field surface microkinetic model per operating point, and the
+# wall fluxes and sensitivities that follow from it.  A library of its own as the five before it
+KINETICS_DIR = os.path.join(CSRC, 'kinetics')
+KINETICS_LIB = os.path.join(LIB_DIR, 'libcatint_kinetics.so')
+KINETICS_SOURCES = ['catkin.hip']
+KINETICS_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -173,6 +180,15 @@ def response_needs_build():
 def build_response_library(force=False, verbose=False):
     """catint_amd/csrc/response into catint_amd/lib/libcatint_response.so"""
     return _build_unit(RESPONSE_DIR, RESPONSE_SOURCES, RESPONSE_HEADERS, RESPONSE_LIB, force, verbose)
+
+
+def kinetics_needs_build():
+    return _unit_needs_build(KINETICS_DIR, KINETICS_SOURCES, KINETICS_HEADERS, KINETICS_LIB)
+
+
+def build_kinetics_library(force=False, verbose=False):
+    """catint_amd/csrc/kinetics into catint_amd/lib/libcatint_kinetics.so"""
+    return _build_unit(KINETICS_DIR, KINETICS_SOURCES, KINETICS_HEADERS, KINETICS_LIB, force, verbose)
 
 
 def unittest_needs_build():

@@ -313,7 +313,43 @@ class Calculator(object):
                 raise CalculatorError('surface kinetics: saturation must be >= 0')
             if float(r.get('saturation', 0.0)) != 0.0 and r.get('species') is None:
                 raise CalculatorError('surface kinetics: saturation needs a species')
+        if reactions and getattr(self, 'microkinetics', None) is not None:
+            raise CalculatorError('set_surface_kinetics and set_microkinetics exclude each other: one kinetic model per calculator')
         self.surface_kinetics = list(reactions)
+
+    def set_microkinetics(self, model, site_density=None, potential_drop='stern', gamma=None):
+        """Mean-field surface microkinetics as the kinetic half of run_scf_cycle (physical mode only): model is a
+        catint_amd.microkinetics.MeanFieldModel over this transport's species (or the dict of its tables()).  With it set,
+        run_scf_cycle() without a callback runs its host loop with the device kinetics (include/catint_kinetics.h) as the callback: the
+        steady-state coverages at the mixed surface state of every lane, warm-started from the previous iteration, give the wall
+        fluxes.  site_density in mol/m^2 (None: tp.system['active site density'], else the model's); potential_drop 'stern' (the
+        potential of a step is phiM - phi(x=0), the reference's voltage_diff_drop) or 'full' (phiM); gamma [B][N]: activity
+        coefficients, None: 1.  The surface charge handed to the model is C_S (phiM - phiPZC - phi(x=0)).  A lane whose coverages are not
+        found (kinetic status 1: stopped at maxit, 3: bad pivot, 2: non-finite input) leaves the loop as 'failed'; the result carries
+        'coverage', 'flux_scale' and 'kinetic_status'.  model=None removes it."""
+        if model is None:
+            self.microkinetics = None
+            return
+        if not self.physical:
+            raise CalculatorError('microkinetics are part of the physical mode (calc="comsol")')
+        if getattr(self, 'surface_kinetics', None):
+            raise CalculatorError('set_surface_kinetics and set_microkinetics exclude each other: one kinetic model per calculator')
+        if potential_drop not in ('stern', 'full'):
+            raise CalculatorError("potential_drop is 'stern' or 'full'")
+        tables = model.tables() if hasattr(model, 'tables') else dict(model)
+        N = self.tp.nspecies
+        nu, of = np.asarray(tables['nu']), np.asarray(tables['order_f'])
+        if of.ndim != 2 or nu.shape != (of.shape[0], N) or of.shape[1] != N + len(tables['site_count']):
+            raise CalculatorError('the microkinetic model is not over the %d species of this transport' % N)
+        if site_density is None:
+            site_density = self.tp.system.get('active site density', tables['site_density'])
+        tables['site_density'] = float(site_density)
+        self.microkinetics = {'tables': tables, 'potential_drop': potential_drop, 'gamma': None if gamma is None else np.asarray(gamma, float)}
+
+    def _kinetics_solver(self):
+        """The device context of the microkinetic solves (tests replace it)"""
+        from . import _kinetics
+        return _kinetics.KineticsSolver(self.device)
 
     def _apply_surface_kinetics(self, solver, phiM, lanes=None):
         rx = getattr(self, 'surface_kinetics', None)
@@ -961,6 +997,30 @@ class Calculator(object):
         tp = self.tp
         device_loop = flux_callback is None
         kinetics = getattr(self, 'surface_kinetics', None)
+        micro = getattr(self, 'microkinetics', None) if device_loop else None
+        kin_solver, coverage = None, {}
+        if micro is not None:
+            # the host loop below, unchanged, with the device kinetics at the mixed surface state as its callback
+            device_loop = False
+            if not self.physical:
+                raise CalculatorError('microkinetics are part of the physical mode (calc="comsol")')
+            kin_solver = self._kinetics_solver()
+            stern_c = float(tp.system.get('Stern capacitance', 0.0)) * 1e-2          # muF/cm^2 -> F/m^2
+            start = 1.0 / float(np.sum(micro['tables']['site_count']))
+
+            def flux_callback(state):
+                guess = coverage.get('theta')
+                if guess is not None:      # a lane that failed keeps no coverages: it starts again from the uniform surface
+                    guess = np.where(np.isfinite(guess).all(axis=1)[:, None], guess, start)
+                out = kin_solver.solve(None, micro['tables'], state['phiM'], csurf=state['surface_concentration'],
+                                       phi_surface=state['surface_potential'], potential_drop=micro['potential_drop'],
+                                       stern_capacitance=stern_c, phi_pzc=float(tp.system.get('phiPZC', 0.0)), gamma=micro['gamma'],
+                                       theta_guess=guess, fields=('theta', 'flux', 'flux_scale'))
+                live = coverage.get('active', np.ones(len(out['status']), bool))
+                for k in ('theta', 'flux_scale', 'status'):
+                    coverage[k] = out[k] if k not in coverage else np.where(live.reshape((-1,) + (1,) * (out[k].ndim - 1)), out[k], coverage[k])
+                coverage['unsolved'] = np.asarray(out['status']) != 0
+                return out['flux']
         if device_loop:
             if not (self.physical and self.mode == 'stationary' and kinetics and transport_fn is None):
                 raise CalculatorError('run_scf_cycle without a callback needs the physical mode (stationary) and set_surface_kinetics')
@@ -1025,7 +1085,14 @@ class Calculator(object):
                 newflux = np.asarray(flux_callback({'surface_concentration': sc.copy(), 'surface_pH': surface_pH.copy(),
                                                     'phiM': phiM, 'surface_potential': vsurf.copy(),
                                                     'surface_efield': esurf.copy(), 'istep': istep}), float)
-                flux = np.where(active[:, None], newflux.reshape(B, N), flux)               # :373
+                newflux = newflux.reshape(B, N)
+                kin_bad = np.zeros(B, bool)
+                if kin_solver is not None:
+                    # a lane whose coverages were not found (stopped at maxit, a bad pivot, a non-finite input) has no fluxes to hand to
+                    # the transport: it keeps its previous ones for this solve and leaves the loop as failed, with its kinetic status
+                    kin_bad = active & coverage['unsolved']
+                    newflux = np.where(kin_bad[:, None], flux, newflux)
+                flux = np.where(active[:, None], newflux, flux)                             # :373
                 if transport_fn is not None:                                                # :385 run_single_step
                     cs, vs, es = transport_fn(flux)
                     status = np.zeros(B, np.int32)
@@ -1061,9 +1128,11 @@ class Calculator(object):
                     acc = np.where(active, err.max(axis=1), acc)
                 cd_old = cd if cd_old is None else np.where(active[:, None], cd, cd_old)
                 history.append(acc.copy())
-                bad = active & (~np.isfinite(cs).all(axis=1) | (status == 2))
+                bad = active & (~np.isfinite(cs).all(axis=1) | (status == 2) | kin_bad)
                 failed |= bad
                 active = active & ~bad & ((acc > self.tau_scf) | (sc < 0.0).any(axis=1))
+                if kin_solver is not None:
+                    coverage['active'] = active.copy()
                 if device_loop and active.any() and istep < max_iter and istep >= 2 and not restart and self.RF == 1.0:
                     # (with a roughness factor the loop stays on the host: the device table would fold RF into the fluxes the
                     #  bookkeeping of the loop sees, the reference scales only what COMSOL is given)
@@ -1089,9 +1158,14 @@ class Calculator(object):
                 self.surface_kinetics = kinetics
             if solver is not None:
                 solver.close()
+            if kin_solver is not None:
+                kin_solver.close()
         for i in range(B):
             d = tp.alldata[i]
             d.setdefault('species', {}); d.setdefault('system', {})
+            if kin_solver is not None and 'theta' in coverage:
+                d['system']['coverage'] = coverage['theta'][i].copy()
+                d['system']['kinetic_status'] = int(coverage['status'][i])
             for k, sp in enumerate(names):
                 d['species'].setdefault(sp, {})
                 d['species'][sp]['surface_concentration'] = float(sc[i, k])
@@ -1099,10 +1173,17 @@ class Calculator(object):
                 d['species'][sp]['electrode_current_density'] = float(flux[i, k] * nel[k] * unit_F / nprod[k] / 10.)
             d['system'].update({'surface_pH': float(surface_pH[i]), 'surface_potential': float(vsurf[i]),
                                 'surface_efield': float(esurf[i]), 'phiM': float(phiM[i])})
-        return {'surface_concentration': sc, 'flux': flux, 'current_density': flux * nel * unit_F / nprod / 10.,
-                'surface_pH': surface_pH, 'accuracy': acc, 'converged': ~active & ~failed, 'failed': failed,
-                'iterations': istep, 'mix': mix,
-                'history': np.array(history)}
+        result = {'surface_concentration': sc, 'flux': flux, 'current_density': flux * nel * unit_F / nprod / 10.,
+                  'surface_pH': surface_pH, 'accuracy': acc, 'converged': ~active & ~failed, 'failed': failed,
+                  'iterations': istep, 'mix': mix,
+                  'history': np.array(history)}
+        if kin_solver is not None and 'theta' in coverage:
+            # the coverages and the gross-rate scale of the fluxes of each lane's last active iteration: the number of digits of a
+            # flux is what flux / flux_scale leaves of 16
+            result['coverage'] = coverage['theta']
+            result['flux_scale'] = coverage['flux_scale']
+            result['kinetic_status'] = coverage['status']          # of each lane's last active iteration; non-zero: the lane is 'failed'
+        return result
 
     # ------------------------------------------------------------------------------------------
     @staticmethod

@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""The CO2 reduction system of examples/co2r_inputs.py with a mean-field microkinetic model of the electrode in the place of the
+analytic rate law: the self-consistency loop of the reference (kinetics <-> transport), the kinetic half solved on the device for every
+voltage of the sweep at once (include/catint_kinetics.h, Calculator.set_microkinetics).
+
+Mechanism (one site type, adsorbed intermediates compete for the sites):
+    CO2 + *            <-> CO2*
+    CO2* + H2O + e-    <-> COOH* + OH-
+    COOH* + e-         <-> [COOH-e]  <-> CO* + OH-          (transition state, beta = 0.5)
+    CO*                <-> CO + *
+The free energies (eV, with a linear and a quadratic dependence on the surface charge in micro C/cm^2) are ILLUSTRATIVE numbers; they
+are not fitted to any surface.  With every site of tp.system['active site density'] active they ask for 400 - 1200 mA/cm^2 between
+-0.6 and -1.2 V, far beyond the 16 mA/cm^2 that diffusion of CO2 delivers here, and the SCF loop then finds no fixed point with
+positive concentrations (--site-fraction 1: 0 of 16 lanes converged in 2000 iterations on an MI355X).  The default takes one site in a
+thousand as active: 16 of 16 lanes converge in 47 SCF iterations, j_CO rises from 0.33 to 0.84 mA/cm^2 and falls again beyond -1.12 V
+as the surface CO2 concentration drops from 5.7 to 0.14 mol/m^3 and CO* gives way to free sites (same machine, --lanes 16).
+
+    python examples/co2r_microkinetic_sweep.py --lanes 16
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from catint_amd.calculator import Calculator          # noqa: E402
+from catint_amd.microkinetics import MeanFieldModel   # noqa: E402
+from catint_amd.units import unit_F                   # noqa: E402
+import co2r_physical_sweep                             # noqa: E402  (the transport of the sweep)
+
+ADSORBATES = {'CO2': 1, 'COOH': 1, 'CO': 1}
+STEPS = ['CO2_g + *_t <-> CO2*_t',
+         'CO2*_t + H2O_g + ele_g <-> COOH*_t + OH_g',
+         'COOH*_t + ele_g <-> COOH-ele_t <-> CO*_t + OH_g; beta=0.5',
+         'CO*_t <-> CO_g + *_t']
+ENERGIES = {'CO2': (0.42, 0.015, 1.0e-4), 'COOH': (0.55, 0.010, 0.0), 'CO': (0.15, 0.002, 0.0), 'COOH-ele': (1.05, 0.010, 0.0)}
+
+
+def model(tp):
+    return MeanFieldModel(list(tp.species.keys()), ADSORBATES, STEPS, ENERGIES, solution={'CO2_g': 'CO2', 'CO_g': 'CO', 'OH_g': 'OH-', 'H2O_g': None},
+                          solution_energies={'CO': 0.30}, temperature=tp.system['temperature'])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--lanes', type=int, default=16)
+    ap.add_argument('--nx', type=int, default=192)
+    ap.add_argument('--phimin', type=float, default=-0.6)
+    ap.add_argument('--phimax', type=float, default=-1.2)
+    ap.add_argument('--site-fraction', type=float, default=1e-3, help='fraction of the active site density that takes part')
+    ap.add_argument('--max-iter', type=int, default=2000)
+    a = ap.parse_args()
+    tp, phis = co2r_physical_sweep.build(a.lanes, a.nx, a.phimin, a.phimax)
+    tp.newton = {'tol': 1e-8, 'maxit': 80}
+    calc = Calculator(transport=tp, calc='comsol', tau_scf=1e-4, mix_scf=0.1)
+    calc.set_microkinetics(model(tp), site_density=a.site_fraction * float(tp.system['active site density']), potential_drop='stern')
+    names = list(tp.species.keys())
+    t0 = time.time()
+    out = calc.run_scf_cycle(nel=[2.0 if sp == 'CO' else 1.0 for sp in names], max_iter=a.max_iter)
+    print('%d lanes: %d SCF iterations, %d converged, %d failed, %.2f s' % (a.lanes, out['iterations'], out['converged'].sum(),
+                                                                          out['failed'].sum(), time.time() - t0))
+    iCO, iCO2 = names.index('CO'), names.index('CO2')
+    print('phiM [V]   j_CO [mA/cm2]   digits   c_CO2(0)   theta_*    theta_CO2   theta_COOH   theta_CO')
+    for i in range(a.lanes):
+        # the number of digits of a flux is what flux / flux_scale leaves of 16
+        with np.errstate(divide='ignore'):
+            digits = 16.0 + np.log10(abs(out['flux'][i, iCO]) / out['flux_scale'][i, iCO])
+        print('%7.3f   %12.5e   %6.1f   %8.4f   %s' % (phis[i], out['flux'][i, iCO] * 2 * unit_F / 10.0, digits, out['surface_concentration'][i, iCO2],
+                                                     '   '.join('%9.3e' % v for v in out['coverage'][i])))
+
+
+if __name__ == '__main__':
+    main()
