@@ -257,6 +257,7 @@ class PnpSolver(object):
         self._regridder = None
         self._responder = None
         self._kinetics = None
+        self._coupler = None
 
     def _check(self, rc):
         if rc != 0:
@@ -281,6 +282,9 @@ class PnpSolver(object):
         if getattr(self, '_kinetics', None) is not None:
             self._kinetics.close()
             self._kinetics = None
+        if getattr(self, '_coupler', None) is not None:
+            self._coupler.close()
+            self._coupler = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -772,6 +776,45 @@ class PnpSolver(object):
                                     phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma,
                                     theta_guess=theta_guess, tol=_kinetics.DEFAULT_TOL if tol is None else tol,
                                     maxit=_kinetics.DEFAULT_MAXIT if maxit is None else maxit, fields=fields, max_waves=max_waves)
+
+    def get_coupling(self, flux, kin, rf=1.0, lanes=None, dphi_max=0.05, fields=None, max_waves=0):
+        """One Newton step of the self-consistency between kinetics and transport (include/catint_couple.h), formed on the device
+        about the stationary state this handle holds, for every lane of `lanes` (None: all, in order; repeats allowed).  flux [B][N]:
+        the prescribed wall fluxes the state was solved with (what set_flux / solve_surface were given; None: the recorded ones).
+        kin: the kinetic half at that state, indexed by the position in the call as get_kinetics(lanes=lanes, fields=('flux',
+        'dflux_dc', 'dflux_dphi')) returns it: 'flux' [n][N], 'dflux_dc' [n][N][N], 'dflux_dphi' [n][N][2] (its column d/d phi_0 is
+        used).  rf: the roughness factor, the transport sees rf times the kinetic flux.  Returns a dict of the rows named in `fields`
+        (catint_amd._couple.FIELDS; None: all): 'T_c' [n][N][N] = d c_k(0) / d flux_j and 'T_phi' [n][N] = d phi(0) / d flux_j (all
+        columns from one elimination), 'dflux' [n][N] the Newton step, 'lambda' [n] its damping (no positive surface concentration
+        falls below a tenth of its value, the surface potential moves by dphi_max at most; dphi_max <= 0: no limit), 'flux_new' [n][N]
+        = flux + lambda dflux, 'dc_surface' [n][N] and 'dphi_surface' [n] the predicted change of the surface state; and 'status' [n]
+        (0; 1: non-finite number or failed pivot check in the elimination; 2: the lane's solver status was not 0 or an input is not
+        finite, outputs NaN; 3: the Newton matrix is singular).  D, charges, ion radii, grid, wall model, velocity and reactions are the
+        ones this solver was given.  The state must have been solved with prescribed fluxes only: with a wall table set
+        (set_wall_kinetics) the call raises ValueError."""
+        from . import _couple
+        o = self._obs
+        if o['wall'] is not None and not o['explicit_kinetics']:
+            raise ValueError('get_coupling: the handle applies a wall table (set_wall_kinetics); the coupling is defined for a state solved '
+                             'with prescribed wall fluxes only')
+        if flux is None:
+            if o['flux_stale'] or o['flux'] is None:
+                raise ValueError('get_coupling: no recorded wall fluxes; pass flux=')
+            flux = o['flux']
+        g = np.asarray(_f64(flux, (self.B, self.N)))
+        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+            raise ValueError('get_coupling: lane index outside [0, %d)' % self.B)
+        n = len(idx)
+        K = np.asarray(kin['flux'], float).reshape(n, self.N)
+        Kc = np.asarray(kin['dflux_dc'], float).reshape(n, self.N, self.N)
+        Kphi = np.ascontiguousarray(np.asarray(kin['dflux_dphi'], float).reshape(n, self.N, 2)[:, :, 1])
+        if getattr(self, '_coupler', None) is None:
+            self._coupler = _couple.Coupler(o['device'])
+        return self._coupler.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], g[idx], K, Kc, Kphi, rf=rf,
+                                   dphi_max=dphi_max, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
+                                   stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], fields=fields,
+                                   max_waves=max_waves)
 
     def get_status(self):
         st = np.zeros(self.B, np.int32)

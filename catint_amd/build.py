@@ -59,6 +59,14 @@ KINETICS_LIB = os.path.join(LIB_DIR, 'libcatint_kinetics.so')
 KINETICS_SOURCES = ['catkin.hip']
 KINETICS_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h')]
 
+# eighth library (include/catint_couple.h): one Newton step of the self-consistency between kinetics and transport per operating
+# point -- the transport tangent from one block elimination, the Newton matrix and the damped step at the wall.  A library of its
+# own as the six before it
+COUPLE_DIR = os.path.join(CSRC, 'couple')
+COUPLE_LIB = os.path.join(LIB_DIR, 'libcatint_couple.so')
+COUPLE_SOURCES = ['catcpl.hip']
+COUPLE_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_couple.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -189,6 +197,15 @@ def kinetics_needs_build():
 def build_kinetics_library(force=False, verbose=False):
     """catint_amd/csrc/kinetics into catint_amd/lib/libcatint_kinetics.so"""
     return _build_unit(KINETICS_DIR, KINETICS_SOURCES, KINETICS_HEADERS, KINETICS_LIB, force, verbose)
+
+
+def couple_needs_build():
+    return _unit_needs_build(COUPLE_DIR, COUPLE_SOURCES, COUPLE_HEADERS, COUPLE_LIB)
+
+
+def build_couple_library(force=False, verbose=False):
+    """catint_amd/csrc/couple into catint_amd/lib/libcatint_couple.so"""
+    return _build_unit(COUPLE_DIR, COUPLE_SOURCES, COUPLE_HEADERS, COUPLE_LIB, force, verbose)
 
 
 def unittest_needs_build():

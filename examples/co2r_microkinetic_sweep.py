@@ -16,6 +16,11 @@ thousand as active: 16 of 16 lanes converge in 47 SCF iterations, j_CO rises fro
 as the surface CO2 concentration drops from 5.7 to 0.14 mol/m^3 and CO* gives way to free sites (same machine, --lanes 16).
 
     python examples/co2r_microkinetic_sweep.py --lanes 16
+    python examples/co2r_microkinetic_sweep.py --lanes 16 --newton
+
+--newton: the same fixed point by a Newton iteration on the wall fluxes (Calculator.set_microkinetics(..., scf='newton'),
+include/catint_couple.h) in the place of the mixing loop: a handful of transport solves instead of one per mixing iteration.  The
+figures of both are in profiles/couple_probe.md.
 """
 import argparse
 import os
@@ -52,16 +57,20 @@ def main():
     ap.add_argument('--phimax', type=float, default=-1.2)
     ap.add_argument('--site-fraction', type=float, default=1e-3, help='fraction of the active site density that takes part')
     ap.add_argument('--max-iter', type=int, default=2000)
+    ap.add_argument('--newton', action='store_true', help='Newton iteration on the wall fluxes instead of the mixing loop')
     a = ap.parse_args()
     tp, phis = co2r_physical_sweep.build(a.lanes, a.nx, a.phimin, a.phimax)
     tp.newton = {'tol': 1e-8, 'maxit': 80}
     calc = Calculator(transport=tp, calc='comsol', tau_scf=1e-4, mix_scf=0.1)
-    calc.set_microkinetics(model(tp), site_density=a.site_fraction * float(tp.system['active site density']), potential_drop='stern')
+    calc.set_microkinetics(model(tp), site_density=a.site_fraction * float(tp.system['active site density']), potential_drop='stern',
+                          scf='newton' if a.newton else 'mixing')
     names = list(tp.species.keys())
     t0 = time.time()
     out = calc.run_scf_cycle(nel=[2.0 if sp == 'CO' else 1.0 for sp in names], max_iter=a.max_iter)
-    print('%d lanes: %d SCF iterations, %d converged, %d failed, %.2f s' % (a.lanes, out['iterations'], out['converged'].sum(),
-                                                                          out['failed'].sum(), time.time() - t0))
+    # (the mixing loop makes one transport solve per iteration)
+    print('%d lanes: %d %s, %d transport solves, %d converged, %d failed, %.2f s'
+          % (a.lanes, out['iterations'], 'Newton steps' if a.newton else 'SCF iterations', out.get('transport_solves', out['iterations']),
+             out['converged'].sum(), out['failed'].sum(), time.time() - t0))
     iCO, iCO2 = names.index('CO'), names.index('CO2')
     print('phiM [V]   j_CO [mA/cm2]   digits   c_CO2(0)   theta_*    theta_CO2   theta_COOH   theta_CO')
     for i in range(a.lanes):
