@@ -16,6 +16,8 @@ _INCLUDE = os.path.join(_HERE, '..', 'include')
 # what every library that derives quantities from a device-resident state includes (csrc/pnp_post.h); tests/test_build_deps.py follows
 # the #include lines of the first three libraries and compares with the lists here (tests/test_regrid_abi.py: the fourth)
 _POST_HEADERS = [os.path.join(CSRC, h) for h in ('pnp_post.h', 'pnp_wave.h', 'pnp_math.h', 'pnp_internal.h')] + [os.path.join(_INCLUDE, 'catint_pnp.h')]
+# what the two libraries that eliminate the stationary Jacobian with a team of lanes per system include on top (csrc/pnp_team.h)
+_TEAM_HEADERS = _POST_HEADERS + [os.path.join(CSRC, 'pnp_team.h')]
 
 # second library (include/catint_observe.h): observables derived from a device-resident state.  Its kernels stay out of SOURCES:
 # the solver library holds the solver's kernels and nothing else (tests/test_kernel_census.py)
@@ -50,7 +52,7 @@ EQUIL_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_equil.h')]
 RESPONSE_DIR = os.path.join(CSRC, 'response')
 RESPONSE_LIB = os.path.join(LIB_DIR, 'libcatint_response.so')
 RESPONSE_SOURCES = ['catresp.hip']
-RESPONSE_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_response.h')]
+RESPONSE_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_response.h')]
 
 # seventh library (include/catint_kinetics.h): the steady state of a mean-field surface microkinetic model per operating point, and the
 # wall fluxes and sensitivities that follow from it.  A library of its own as the five before it
@@ -65,7 +67,7 @@ KINETICS_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h')]
 COUPLE_DIR = os.path.join(CSRC, 'couple')
 COUPLE_LIB = os.path.join(LIB_DIR, 'libcatint_couple.so')
 COUPLE_SOURCES = ['catcpl.hip']
-COUPLE_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_couple.h')]
+COUPLE_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_couple.h')]
 
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it

@@ -11,7 +11,7 @@ Tolerance: per output and system, 10 x the disagreement of the reference's two m
 Schur recursion) on that system, not below 1e-11 -- the project's rule from tests/test_gpu_response.py.  That disagreement must itself
 stay below 1e-8 (asserted).  The worst ratios device error / tolerance are printed by every test.  Measured on the MI355X (also in
 DESIGN.md section 7i): 0.90 at N = 2, nx = 19 (dc_surface: 1.0e-11 against 1.15e-11), every other small case at most 0.36, case F 0.28,
-case E 0.17, with reference disagreements up to 1.6e-11; the tangent equals the flux response of libcatint_response bit for bit; the
+case E 0.17, with reference disagreements up to 1.6e-11; the tangent equals the flux response of libcatint_response bit for bit (asserted); the
 end-to-end case takes 2 Newton steps and 3 transport solves where the mixing loop takes 23 iterations, the fluxes equal to 8.1e-9.
 Everything that can be exact is asserted bit for bit."""
 import numpy as np
@@ -182,8 +182,9 @@ def test_the_cases_reach_every_instance():
 
 @pytest.mark.parametrize('name', ['F', 'E', 'N=4'])
 def test_the_tangent_is_the_flux_response_of_libcatint_response(name):
-    """Independent device code: column j of T equals catresp_solve(CATRESP_WALL_FLUX, species j, omega = 0), within the tolerance of
-    the parity checks (the two kernels perform the same operations on a column: the difference is printed)"""
+    """Column j of T equals catresp_solve(CATRESP_WALL_FLUX, species j, omega = 0): within the tolerance of the parity checks, and bit
+    for bit -- the two kernels form the rows of the Jacobian with the same functions (catint_amd/csrc/pnp_team.h) and eliminate them
+    with the same Gauss-Jordan step, written out in each, so a column goes through the same operations in the same order"""
     case = {'F': lambda: without_wall(RC.case_F()), 'E': lambda: without_wall(RC.case_E(34)), 'N=4': lambda: RC.small(4, 19, True, True)}[name]()
     s, phis, lin = prepared(case)
     flux = np.zeros((B, case.N))
@@ -198,6 +199,7 @@ def test_the_tangent_is_the_flux_response_of_libcatint_response(name):
         exact = exact and np.array_equal(got['T_c'][:, :, j], r['dc_surface'][:, 0].real) and np.array_equal(got['T_phi'][:, j], r['dphi_surface'][:, 0].real)
     print('%s: T against the flux response of libcatint_response: worst difference / tolerance %.3f, bit-identical: %s' % (case.name, worst, exact))
     assert worst <= 1.0
+    assert exact
 
 
 # ---- bit for bit -------------------------------------------------------------------------------------------------------------------
