@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../catint_amd/csrc/pnp_lane_cols.h"
 #include "../../catint_amd/csrc/pnp_lane_common.h"
 #include "../../catint_amd/csrc/pnp_math.h"
 #include "../../catint_amd/csrc/pnp_post.h"
@@ -67,6 +68,20 @@ __global__ __launch_bounds__(64) void pick_blocked_kernel(const double* __restri
 #pragma unroll
   for (int j = 0; j < P; ++j) r[j] = a[lane * P + j];
   for (int q = 0; q < 64 * P; ++q) out[q * 64 + lane] = pick_blocked<P>(r, lane * P, q);
+}
+
+// The exchanges of the column-lane Newton kernels (pnp_lane_cols.h; lane = 2 W point + W direction + column lane).  bcast[Q][lane]: the
+// value of column lane Q of the lane's own point and direction; other[lane]: the same column lane of the other direction; sum[lane]: the
+// sum over the column lanes of the lane's direction
+template <int W>
+__global__ __launch_bounds__(64) void col_lanes_kernel(const double* __restrict__ v, double* __restrict__ bcast, double* __restrict__ other,
+                                                       double* __restrict__ sum) {
+  const int lane = threadIdx.x;
+  const double x = v[lane];
+#pragma unroll
+  for (int Q = 0; Q < W; ++Q) bcast[Q * 64 + lane] = lane::col_bcast_sel<W>(Q, x);
+  other[lane] = lane::other_dir<W>(x);
+  sum[lane] = lane::col_sum<W>(x);
 }
 
 template <bool BC>
@@ -345,6 +360,22 @@ __attribute__((visibility("default"))) int catunit_read_lane(const double* v, do
   read_lane_kernel<<<1, 64>>>(dv.d(), dout.d());
   CATUNIT_TRY(finish());
   return dev_download(out, dout, 64 * 64);
+}
+
+// v, other, sum: [64]; bcast: [W][64]; W 2 or 4
+__attribute__((visibility("default"))) int catunit_col_lanes(int W, const double* v, double* bcast, double* other, double* sum) {
+  if (!v || !bcast || !other || !sum || (W != 2 && W != 4)) return EINVAL_;
+  Buf dv, db, dO, ds;
+  CATUNIT_TRY(dev_upload(dv, v, 64));
+  CATUNIT_TRY(dev_alloc(db, (size_t)W * 64));
+  CATUNIT_TRY(dev_alloc(dO, 64));
+  CATUNIT_TRY(dev_alloc(ds, 64));
+  if (W == 2) col_lanes_kernel<2><<<1, 64>>>(dv.d(), db.d(), dO.d(), ds.d());
+  else col_lanes_kernel<4><<<1, 64>>>(dv.d(), db.d(), dO.d(), ds.d());
+  CATUNIT_TRY(finish());
+  CATUNIT_TRY(dev_download(bcast, db, (size_t)W * 64));
+  CATUNIT_TRY(dev_download(other, dO, 64));
+  return dev_download(sum, ds, 64);
 }
 
 // a: [64 P]; out: [64 P (q)][64 (lane)]

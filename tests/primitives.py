@@ -2,7 +2,7 @@
 
 Three parts:
   * the ctypes binding of libcatint_unittest.so (tests/csrc/primitives_harness.hip: every primitive of pnp_math.h, pnp_wave.h,
-    pnp_post.h and pnp_lane_common.h behind a kernel of its own),
+    pnp_post.h, pnp_lane_common.h and pnp_lane_cols.h behind a kernel of its own),
   * multiprecision references (mpmath, 60 digits, rounded ONCE to fp64; where an error is measured in ulp the reference is the pair
     (hi, lo) with hi + lo the exact value to ~1e-32 relative, so that the error is taken against the exact value, not a rounded one),
   * the assertion helpers of tests/test_gpu_primitives.py -- pure functions of arrays -- and plain fp64 NumPy emulations of the
@@ -24,7 +24,7 @@ PS = (1, 2, 4, 8, 16)
 FN = {'fast_rcp': 0, 'fast_rcp2': 1, 'nrcp': 2, 'expm1_sc': 3, 'log1p_sc': 4, 'bernoulli': 5}
 SYMBOLS = ('catunit_scalar', 'catunit_edge_flux', 'catunit_wave_moves', 'catunit_read_lane', 'catunit_pick_blocked', 'catunit_wave_scan',
            'catunit_blocked_scan', 'catunit_blocked_scan_sum', 'catunit_tridiag', 'catunit_row_alloc', 'catunit_win_alloc', 'catunit_load_row',
-           'catunit_store_row', 'catunit_load_window', 'catunit_store_window')
+           'catunit_store_row', 'catunit_load_window', 'catunit_store_window', 'catunit_col_lanes')
 
 # the bars (the header comments' own figures with the allowance of the design note, or its derivations)
 RCP1_BAR = 2 * 2.2e-15          # fast_rcp, relative
@@ -97,6 +97,14 @@ def read_lane(v):
     out = np.empty((64, 64))
     _check(load_library().catunit_read_lane(_p(v), _p(out)), 'catunit_read_lane')
     return out
+
+
+def col_lanes(W, v):
+    """the exchanges of pnp_lane_cols.h on one wave: bcast [W, 64], other [64], total [64]"""
+    v = _in(v).reshape(64)
+    bcast, other, total = np.empty((W, 64)), np.empty(64), np.empty(64)
+    _check(load_library().catunit_col_lanes(W, _p(v), _p(bcast), _p(other), _p(total)), 'catunit_col_lanes')
+    return bcast, other, total
 
 
 def pick_blocked(P, a):
@@ -355,6 +363,30 @@ def check_bernoulli_balance(u, B, bar=B_ULP_BAR):
     return float(gap[k]), float(u[pos[k]])
 
 
+def lane_ids():
+    """what every lane feeds the column-lane exchanges: its lane id plus 0.25 (sums of four stay exact)"""
+    return np.arange(64) + 0.25
+
+
+def check_col_lanes(W, bcast, other, total):
+    """outputs of the column-lane exchanges for the input lane_ids(), against index arithmetic on lane = 2 W point + W direction + column
+    lane: bcast[Q] the lane Q of the own point and direction, other the same column lane of the other direction, total the sum over the W
+    column lanes of the own direction.  Exact."""
+    lane = np.arange(64)
+    point, direction, col = lane // (2 * W), (lane // W) % 2, lane % W
+    ident = lambda p, d, c: 2 * W * p + W * d + c
+    for Q in range(W):
+        want = ident(point, direction, Q) + 0.25
+        bad = np.nonzero(bcast[Q] != want)[0]
+        assert bad.size == 0, 'W = %d, broadcast of column lane %d: lane %d reads %r, expected %r' % (W, Q, bad[0], bcast[Q][bad[0]], want[bad[0]])
+    want = ident(point, 1 - direction, col) + 0.25
+    bad = np.nonzero(other != want)[0]
+    assert bad.size == 0, 'W = %d, other direction: lane %d reads %r, expected %r' % (W, bad[0], other[bad[0]], want[bad[0]])
+    want = sum(ident(point, direction, c) for c in range(W)) + 0.25 * W
+    bad = np.nonzero(total != want)[0]
+    assert bad.size == 0, 'W = %d, sum over the column lanes: lane %d holds %r, expected %r' % (W, bad[0], total[bad[0]], want[bad[0]])
+
+
 def check_scan_onehot(out, rev=False):
     """out[i] = scan of the i-th unit vector: the step function from element i on (rev: up to element i), exactly"""
     n = out.shape[0]
@@ -595,6 +627,38 @@ def emul_blocked_scan(x, P, rev=False, skip=None):
     base = np.concatenate([np.zeros((n, 1)), inc[:, :-1]], axis=1)
     b += base[:, :, None]
     return b.reshape(n, 64 * P), np.repeat(inc[:, 63:64], 64, axis=1), base
+
+
+def emul_quad_perm(v, sel):
+    """DPP quad_perm: lane i of every quad reads lane sel[i] of it"""
+    v = np.asarray(v, float)
+    lane = np.arange(64)
+    return v[(lane & ~3) + np.asarray(sel)[lane & 3]]
+
+
+COL_LANE_MUTANTS = ('bcast within the quad', 'other direction = partner lane', 'sum of one exchange')
+
+
+def emul_col_lanes(W, v, mutant=None):
+    """the exchanges of pnp_lane_cols.h as the moves the device makes (quad_perm, and the xor-4 shuffle of the lane quad).  Mutants: the
+    pair's broadcast with the quad's control (both directions read the upward one); the other direction taken from lane ^ 1; the sum with
+    its last exchange left out"""
+    v = np.asarray(v, float)
+    lane = np.arange(64)
+    if W == 4 or mutant == COL_LANE_MUTANTS[0]:
+        bcast = np.array([emul_quad_perm(v, [Q] * 4) for Q in range(W)])
+    else:
+        bcast = np.array([emul_quad_perm(v, [Q, Q, 2 + Q, 2 + Q]) for Q in range(W)])
+    if mutant == COL_LANE_MUTANTS[1]:
+        other = v[lane ^ 1]
+    else:
+        other = v[lane ^ 4] if W == 4 else emul_quad_perm(v, [2, 3, 0, 1])
+    total = v + emul_quad_perm(v, [1, 0, 3, 2])
+    if W == 4 and mutant != COL_LANE_MUTANTS[2]:
+        total = total + emul_quad_perm(total, [2, 3, 0, 1])
+    if W == 2 and mutant == COL_LANE_MUTANTS[2]:
+        total = v.copy()
+    return bcast, other, total
 
 
 def emul_load(src, ldx, n, overrun=0):

@@ -113,6 +113,12 @@ def test_read_lane():
     assert np.array_equal(out, np.repeat(v[:, None], 64, axis=1))
 
 
+@pytest.mark.parametrize('W', [2, 4])
+def test_column_lane_exchanges(W):
+    """pnp_lane_cols.h: lane = 2 W point + W direction + column lane; every lane feeds its id plus 0.25"""
+    U.check_col_lanes(W, *U.col_lanes(W, U.lane_ids()))
+
+
 @pytest.mark.parametrize('P', U.PS)
 def test_pick_blocked(P):
     a = np.random.default_rng(P).standard_normal(64 * P)

@@ -53,16 +53,16 @@ def test_the_harness_builds_for_gfx950(libpath):
             assert 'unittest' not in open(os.path.join(pkg, f)).read(), f
 
 
-def test_the_harness_includes_only_the_four_shared_headers():
+def test_the_harness_includes_only_the_shared_headers():
     src = open(os.path.join(ROOT, 'tests', 'csrc', 'primitives_harness.hip')).read()
     quoted = sorted(os.path.basename(n) for n in re.findall(r'^\s*#\s*include\s+"([^"]+)"', src, flags=re.M))
-    assert quoted == ['pnp_lane_common.h', 'pnp_math.h', 'pnp_post.h', 'pnp_wave.h']
+    assert quoted == ['pnp_lane_cols.h', 'pnp_lane_common.h', 'pnp_math.h', 'pnp_post.h', 'pnp_wave.h']
 
 
 def test_the_library_exports_exactly_the_declared_symbols(libpath):
     src = open(os.path.join(ROOT, 'tests', 'csrc', 'primitives_harness.hip')).read()
     declared = sorted(set(re.findall(r'\bint\s+(catunit_[a-z0-9_]+)\s*\(', src)))
-    assert declared == sorted(U.SYMBOLS) and len(declared) == 15
+    assert declared == sorted(U.SYMBOLS) and len(declared) == 16
     lib = C.CDLL(libpath)
     for s in declared:
         assert hasattr(lib, s), s
@@ -78,7 +78,7 @@ def test_every_kernel_is_in_namespace_catunit_and_every_tridiag_instance_is_ther
     assert compiled and all(n.startswith('catunit::') for n in compiled), sorted(n for n in compiled if not n.startswith('catunit::'))
     tri = {'catunit::tridiag_kernel<%d, %d, %s>' % (P, G, d) for P in U.PS for G in (1, 2, 3) for d in ('false', 'true')}
     assert len(tri) == 30 and tri <= compiled, sorted(tri - compiled)
-    for fam, count in (('scalar_kernel', 6), ('pick_blocked_kernel', 5), ('wave_scan_kernel', 2), ('blocked_scan_kernel', 10),
+    for fam, count in (('scalar_kernel', 6), ('col_lanes_kernel', 2), ('pick_blocked_kernel', 5), ('wave_scan_kernel', 2), ('blocked_scan_kernel', 10),
                        ('blocked_scan_sum_kernel', 5), ('load_row_kernel', 5), ('store_row_kernel', 10), ('load_window_kernel', 13),
                        ('store_window_kernel', 14)):
         assert sum(K.family(n) == 'catunit::' + fam for n in compiled) == count, fam
@@ -114,6 +114,7 @@ def test_invalid_arguments_are_refused_before_any_device_call(libpath):
     assert lib.catunit_store_window(2, 1, p, p, 8, 3) == 1
     assert lib.catunit_tridiag(3, 1, 0, p, p, p, p, 1) == 1 and lib.catunit_tridiag(2, 4, 0, p, p, p, p, 1) == 1
     assert lib.catunit_scalar(6, p, p, 8) == 1 and lib.catunit_scalar(0, p, p, 0) == 0
+    assert lib.catunit_col_lanes(3, p, p, p, p) == 1 and lib.catunit_col_lanes(8, p, p, p, p) == 1
     assert lib.catunit_pick_blocked(5, p, p) == 1 and lib.catunit_blocked_scan(3, 0, p, p, p, p, 1) == 1
 
 
@@ -217,6 +218,17 @@ def test_bernoulli_helpers_pass_the_emulation_and_fail_the_coefficient_mutant(be
     assert fails(U.check_bernoulli_balance, u, np.where(u < 0, B * (1.0 + 2e-15), B))
     us = np.where(np.abs(u) < U.SERIES_U, u, 0.0)
     assert fails(U.check_rel, dB + us ** 5 * (1.0 / 5000.0 - 1.0 / 5040.0), ref_dB, U.DB_REL_BAR, u)
+
+
+@pytest.mark.parametrize('W', [2, 4])
+def test_column_lane_helper_passes_the_emulation_and_fails_the_mutants(W):
+    U.check_col_lanes(W, *U.emul_col_lanes(W, U.lane_ids()))
+    for mutant in U.COL_LANE_MUTANTS:
+        if W == 4 and mutant == U.COL_LANE_MUTANTS[0]:
+            continue          # (the quad's own control)
+        assert fails(U.check_col_lanes, W, *U.emul_col_lanes(W, U.lane_ids(), mutant)), mutant
+    # the other width's map is not this one's
+    assert fails(U.check_col_lanes, W, *(t[:W] if t.ndim == 2 else t for t in U.emul_col_lanes(6 - W, U.lane_ids())))
 
 
 def test_wave_scan_helper_identifies_every_stage_and_row_mask():
