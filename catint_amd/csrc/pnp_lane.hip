@@ -405,8 +405,7 @@ __global__ __launch_bounds__(64) void newton_lane_kernel(const NewtonArgs G) {
           t[k] = -(bc[k] - s_cb[k][o]);
         }
         t[N] = -(bphi - phiB);
-        mphi = fabs(t[N]);
-        if (!(mphi == mphi)) mphi = INFINITY;
+        mphi = newton_norm_phi(0.0, t[N]);
         if constexpr (!FUSED) {
 #pragma unroll
           for (int p = 0; p < VP; ++p) {
@@ -857,33 +856,11 @@ __global__ __launch_bounds__(64) void newton_lane_kernel(const NewtonArgs G) {
               y[r] = special ? sp : y[r];
               x[r] = y[r];
             }
-            const double a = fabs(y[N]);
-            mphi_p = fmax(mphi_p, a);
-            if (!(a == a)) mphi_p = INFINITY;
+            mphi_p = newton_norm_phi(mphi_p, y[N]);
             // ---- damping, clips, update of this row --------------------------------------------------------------------------
-            double f_old = 0.0, f_new = 0.0;
 #pragma unroll
-            for (int k = 0; k < N; ++k) {
-              const double rel = fabs(y[k]) / (fabs(cc_[k]) + fabs(s_cb[k][o]) + 1e-300);
-              upd_p = fmax(upd_p, rel);
-              if (!(y[k] == y[k])) upd_p = INFINITY;
-              const double t_ = __builtin_fma(lm, y[k], cc_[k]);
-              const double lo = 0.1 * cc_[k];
-              cn[k] = t_ < lo ? lo : t_;
-              if constexpr (MPB) {
-                f_old = __builtin_fma(G.vol[k], cc_[k], f_old);
-                f_new = __builtin_fma(G.vol[k], cn[k], f_new);
-              }
-            }
-            if constexpr (MPB) {
-              const double free_ = 1.0 - f_old;
-              const double target = fmax(0.1 * free_, 1e-12);
-              if ((1.0 - f_new) < target) {
-                const double theta = (free_ - target) / (f_new - f_old);
-#pragma unroll
-                for (int k = 0; k < N; ++k) cn[k] = __builtin_fma(theta, cn[k] - cc_[k], cc_[k]);
-              }
-            }
+            for (int k = 0; k < N; ++k) upd_p = newton_norm_species(upd_p, y[k], cc_[k], s_cb[k][o]);
+            newton_clip_row<N, MPB>(lm, y, cc_, G.vol, cn);
             if (wr) {
               double out[2 * VP];
 #pragma unroll
@@ -902,7 +879,7 @@ __global__ __launch_bounds__(64) void newton_lane_kernel(const NewtonArgs G) {
         }
         if (pass == 0) {
           mphi = fmax(mphi_p, partner(mphi_p));
-          if (A.dphi_max > 0.0 && mphi > A.dphi_max) lam = A.dphi_max / mphi;
+          lam = newton_damping(mphi, A.dphi_max);
           upd = fmax(upd_p, partner(upd_p));
           upd = fmax(upd, mphi * A.vt_inv);
         }
@@ -918,6 +895,9 @@ __global__ __launch_bounds__(64) void newton_lane_kernel(const NewtonArgs G) {
         const double other = partner(own);          // (cross-lane: every lane takes part, the select comes afterwards)
         x[r] = side ? other : own;
       }
+      // (newton_norm_phi written out.  Resources decide this, not time: as a call -- under the branch, ahead of it or as a select -- this one
+      // line gives <8, 0, false, false> its first 196 bytes of scratch per lane and the other instances without the fused update 150 to
+      // 330 more, and scratch may not appear where there was none; the spilling forms were not timed: profiles/newton_rule.md section 2)
       if (!side) {
         mphi = fabs(x[N]);
         if (!(mphi == mphi)) mphi = INFINITY;
@@ -959,15 +939,12 @@ __global__ __launch_bounds__(64) void newton_lane_kernel(const NewtonArgs G) {
               v[1] = 2 * p + 1 < NB ? y[2 * p + 1 < NB ? 2 * p + 1 : 0] : 0.0;
               XS(i, p) = v;
             }
-            const double a = fabs(y[N]);
-            mphi = fmax(mphi, a);
-            if (!(a == a)) mphi = INFINITY;
+            mphi = newton_norm_phi(mphi, y[N]);
           }
         }
       }
       mphi = fmax(mphi, partner(mphi));
-      lam = 1.0;
-      if (A.dphi_max > 0.0 && mphi > A.dphi_max) lam = A.dphi_max / mphi;
+      lam = newton_damping(mphi, A.dphi_max);
 #ifdef PNP_LANE_STAMPS
       const unsigned long long ts2 = __builtin_readcyclecounter();
 #endif
@@ -1006,30 +983,12 @@ __global__ __launch_bounds__(64) void newton_lane_kernel(const NewtonArgs G) {
             double du[NB], cc_[N], cn[N];
 #pragma unroll
             for (int r = 0; r < NB; ++r) du[r] = x2[r >> 1][r & 1];
-            double f_old = 0.0, f_new = 0.0;
 #pragma unroll
             for (int k = 0; k < N; ++k) {
               cc_[k] = c2[k >> 1][k & 1];
-              const double rel = fabs(du[k]) / (fabs(cc_[k]) + fabs(s_cb[k][o]) + 1e-300);
-              upd = fmax(upd, rel);
-              if (!(du[k] == du[k])) upd = INFINITY;
-              const double t_ = __builtin_fma(lam, du[k], cc_[k]);
-              const double lo = 0.1 * cc_[k];
-              cn[k] = t_ < lo ? lo : t_;
-              if constexpr (MPB) {
-                f_old = __builtin_fma(G.vol[k], cc_[k], f_old);
-                f_new = __builtin_fma(G.vol[k], cn[k], f_new);
-              }
+              upd = newton_norm_species(upd, du[k], cc_[k], s_cb[k][o]);
             }
-            if constexpr (MPB) {
-              const double free_ = 1.0 - f_old;
-              const double target = fmax(0.1 * free_, 1e-12);
-              if ((1.0 - f_new) < target) {
-                const double theta = (free_ - target) / (f_new - f_old);
-#pragma unroll
-                for (int k = 0; k < N; ++k) cn[k] = __builtin_fma(theta, cn[k] - cc_[k], cc_[k]);
-              }
-            }
+            newton_clip_row<N, MPB>(lam, du, cc_, G.vol, cn);
             if (have) {
               double out[2 * VP];
 #pragma unroll
@@ -1063,14 +1022,7 @@ __global__ __launch_bounds__(64) void newton_lane_kernel(const NewtonArgs G) {
     alarm = fmax(alarm, partner(alarm));
     // =========================== bookkeeping of the lane's operating point (identical in both halves) ========================
     if (have) {
-      bool accept = false;
-      if (lam == 1.0) {
-        accept = upd < A.tol || (A.estimate && upd_prev < INFINITY && upd < 0.1 * upd_prev && upd * (upd / upd_prev) < A.tol) ||
-              newton_at_rounding_floor(upd, upd_prev, A.tol);
-        upd_prev = upd;
-      } else {
-        upd_prev = INFINITY;
-      }
+      const bool accept = newton_accept(lam, upd, upd_prev, A.tol, A.estimate);
       if (accept || it >= A.maxit) {
         total_it += accept ? it : A.maxit + 1;
         if (!accept) st = PNP_STATUS_MAXIT;

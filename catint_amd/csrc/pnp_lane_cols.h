@@ -109,6 +109,12 @@ template <int W> constexpr int PREFETCH_ROWS = W == 4 ? 4 : 1;
 // has been measured for the pair.
 template <int W> constexpr bool START_STAGGER = W == 4;
 
+// The update pass clips a row either through newton_clip_row (pnp_math.h) after the loop that takes the update norm, or with the same
+// scalar functions inside that loop.  Measured (profiles/newton_rule.md section 5, 8 x 512 x 8192 points, parent and forms alternating): the
+// lane pair is 1.0 to 1.5 % behind its hand-written predecessor with the first form and level (+0.3 ... +0.5 %) with the second; the
+// lane quad is 0.8 % behind with the first and 1.5 to 1.9 % with the second.  Each keeps the form that is faster for it.
+template <int W> constexpr bool CLIPS_WITH_THE_NORM = W == 2;
+
 // ---- the kernel body --------------------------------------------------------------------------------------------------------------------------------------
 // (BDF: the BDF2 history inside the launch -- a template flag here: as a run-time flag it cost the backward-Euler instances 3-8 % in
 // registers moved around, tools/probe/ab_old_new.sh)
@@ -288,8 +294,7 @@ __device__ __forceinline__ void newton_lane_cols_body(const NewtonArgs& G) {
           tb[k] = -(bc[k] - s_cb[k][o]);
         }
         tb[N] = -(bphi - phiB);
-        mphi = fabs(tb[N]);
-        if (!(mphi == mphi)) mphi = INFINITY;
+        mphi = newton_norm_phi(0.0, tb[N]);
         // t is column NB of [T | t]: it lives in column lane NB % W, local index NB / W
         if (q == NB % W) {
 #pragma unroll
@@ -745,9 +750,7 @@ __device__ __forceinline__ void newton_lane_cols_body(const NewtonArgs& G) {
       x[r] = side ? from_up : up;
     }
     if (!side) {
-      const double a = fabs(x[N]);
-      mphi = a;
-      if (!(a == a)) mphi = INFINITY;
+      mphi = newton_norm_phi(0.0, x[N]);
       if (q == 0) {
 #pragma unroll
         for (int p = 0; p < VP; ++p) {
@@ -828,16 +831,13 @@ __device__ __forceinline__ void newton_lane_cols_body(const NewtonArgs& G) {
               XS(i, p) = v;
             }
           }
-          const double a = fabs(y[N]);
-          mphi = fmax(mphi, a);
-          if (!(a == a)) mphi = INFINITY;
+          mphi = newton_norm_phi(mphi, y[N]);
         }
        }
       }
     }
     mphi = fmax(mphi, other_dir<W>(mphi));          // (the column lanes of a direction hold the same sums)
-    double lam = 1.0;
-    if (A.dphi_max > 0.0 && mphi > A.dphi_max) lam = A.dphi_max / mphi;
+    const double lam = newton_damping(mphi, A.dphi_max);
 #ifdef PNP_LANE_STAMPS
     const unsigned long long ts2 = __builtin_readcyclecounter();
 #endif
@@ -885,28 +885,26 @@ __device__ __forceinline__ void newton_lane_cols_body(const NewtonArgs& G) {
           double du[NB], cc_[N], cn[N];
 #pragma unroll
           for (int r = 0; r < NB; ++r) du[r] = x2[r >> 1][r & 1];
-          double f_old = 0.0, f_new = 0.0;
+          [[maybe_unused]] double f_old = 0.0, f_new = 0.0;
 #pragma unroll
           for (int k = 0; k < N; ++k) {
             cc_[k] = c2[k >> 1][k & 1];
-            const double rel = fabs(du[k]) / (fabs(cc_[k]) + fabs(s_cb[k][o]) + 1e-300);
-            upd = fmax(upd, rel);
-            if (!(du[k] == du[k])) upd = INFINITY;
-            const double t_ = __builtin_fma(lam, du[k], cc_[k]);
-            const double lo_ = 0.1 * cc_[k];
-            cn[k] = t_ < lo_ ? lo_ : t_;
-            if constexpr (MPB) {
-              f_old = __builtin_fma(G.vol[k], cc_[k], f_old);
-              f_new = __builtin_fma(G.vol[k], cn[k], f_new);
+            upd = newton_norm_species(upd, du[k], cc_[k], s_cb[k][o]);
+            if constexpr (CLIPS_WITH_THE_NORM<W>) {
+              cn[k] = newton_floor_step(lam, du[k], cc_[k]);
+              if constexpr (MPB) {
+                f_old = __builtin_fma(G.vol[k], cc_[k], f_old);
+                f_new = __builtin_fma(G.vol[k], cn[k], f_new);
+              }
             }
           }
-          if constexpr (MPB) {
-            const double free_ = 1.0 - f_old;
-            const double target = fmax(0.1 * free_, 1e-12);
-            if ((1.0 - f_new) < target) {
-              const double theta = (free_ - target) / (f_new - f_old);
+          if constexpr (!CLIPS_WITH_THE_NORM<W>) {
+            newton_clip_row<N, MPB>(lam, du, cc_, G.vol, cn);
+          } else if constexpr (MPB) {
+            double theta;
+            if (newton_free_volume(f_old, f_new, theta)) {
 #pragma unroll
-              for (int k = 0; k < N; ++k) cn[k] = __builtin_fma(theta, cn[k] - cc_[k], cc_[k]);
+              for (int k = 0; k < N; ++k) cn[k] = newton_backtrack(theta, cn[k], cc_[k]);
             }
           }
           if (have) {
@@ -942,14 +940,7 @@ __device__ __forceinline__ void newton_lane_cols_body(const NewtonArgs& G) {
 #endif
     // =========================== bookkeeping (identical in the 2 W lanes of an operating point) ======================================================
     if (have) {
-      bool accept = false;
-      if (lam == 1.0) {
-        accept = upd < A.tol || (A.estimate && upd_prev < INFINITY && upd < 0.1 * upd_prev && upd * (upd / upd_prev) < A.tol) ||
-                 newton_at_rounding_floor(upd, upd_prev, A.tol);
-        upd_prev = upd;
-      } else {
-        upd_prev = INFINITY;
-      }
+      const bool accept = newton_accept(lam, upd, upd_prev, A.tol, A.estimate);
       if (accept || it >= A.maxit) {
         total_it += accept ? it : A.maxit + 1;
         if (!accept) st = PNP_STATUS_MAXIT;

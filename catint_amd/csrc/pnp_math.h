@@ -40,6 +40,86 @@ __device__ __forceinline__ bool newton_at_rounding_floor(double upd, double upd_
 #endif
 }
 
+// ---- The damped update of the physical mode's Newton iteration (oracle/pnp_physical.py: newton_step), stated once for every kernel.
+// ---- Scalars in, scalars out; how a kernel holds its row, reduces the norms and predicates its stores is the kernel's own.
+
+// Update norms, one unknown at a time: the largest scaled update of a concentration and the largest change of the potential.  fmax drops
+// a NaN operand, so a NaN update is tested for separately: it makes the norm infinite and the state is never accepted.
+__device__ __forceinline__ double newton_norm_species(double upd, double x, double c, double cbulk) {
+  upd = fmax(upd, fabs(x) / (fabs(c) + fabs(cbulk) + 1e-300));
+  if (!(x == x)) upd = INFINITY;
+  return upd;
+}
+__device__ __forceinline__ double newton_norm_phi(double mphi, double x) {
+  const double a = fabs(x);
+  mphi = fmax(mphi, a);
+  if (!(a == a)) mphi = INFINITY;
+  return mphi;
+}
+
+// The whole update is scaled so that the potential moves by at most dphi_max per iteration (dphi_max <= 0: no limit)
+__device__ __forceinline__ double newton_damping(double mphi, double dphi_max) {
+  double lam = 1.0;
+  if (dphi_max > 0.0 && mphi > dphi_max) lam = dphi_max / mphi;
+  return lam;
+}
+
+// A concentration never loses more than 90 % per iteration
+__device__ __forceinline__ double newton_floor_step(double lam, double du, double c) {
+  const double t_ = __builtin_fma(lam, du, c);
+  const double lo = 0.1 * c;
+  return t_ < lo ? lo : t_;
+}
+
+// ... and neither does the free volume fraction 1 - phi0 of steric ions (at least 1e-12 of it stays): f_old, f_new are the occupied
+// fractions sum_k vol_k c_k before and after the floored step.  True when the step has to be shortened, theta then being the fraction
+// of it that is taken (newton_backtrack).  A conditional: a step that is not shortened is not multiplied by one.
+__device__ __forceinline__ bool newton_free_volume(double f_old, double f_new, double& theta) {
+  const double free_ = 1.0 - f_old;
+  const double target = fmax(0.1 * free_, 1e-12);
+  const bool over = (1.0 - f_new) < target;
+  if (over) theta = (free_ - target) / (f_new - f_old);
+  return over;
+}
+__device__ __forceinline__ double newton_backtrack(double theta, double cn, double c) { return __builtin_fma(theta, cn - c, c); }
+
+// The two clips on a row held by one lane: cn = the floored step of c by lam du (du may hold the potential's update behind the N species)
+template <int N, bool MPB, int ND>
+__device__ __forceinline__ void newton_clip_row(double lam, const double (&du)[ND], const double (&c)[N], const double* vol, double (&cn)[N]) {
+  double f_old = 0.0, f_new = 0.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    cn[k] = newton_floor_step(lam, du[k], c[k]);
+    if constexpr (MPB) {
+      f_old = __builtin_fma(vol[k], c[k], f_old);
+      f_new = __builtin_fma(vol[k], cn[k], f_new);
+    }
+  }
+  if constexpr (MPB) {
+    double theta;
+    if (newton_free_volume(f_old, f_new, theta)) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) cn[k] = newton_backtrack(theta, cn[k], c[k]);
+    }
+  }
+}
+
+// Acceptance of the state just computed; upd_prev becomes the scaled update of this iteration if it was a full (undamped) step and
+// INFINITY otherwise.  Only a full step is ever accepted.  Strict: the update itself is below tol.  With `estimate` the state is accepted
+// as soon as the quadratic error estimate of the state just computed, upd^2/upd_prev (two consecutive contracting full steps), is below
+// tol -- the iteration that would only confirm it is skipped (oracle/pnp_physical.py: newton_step(estimate=True)).  Third: the rounding floor.
+__device__ __forceinline__ bool newton_accept(double lam, double upd, double& upd_prev, double tol, bool estimate) {
+  bool accept = false;
+  if (lam == 1.0) {
+    accept = upd < tol || (estimate && upd_prev < INFINITY && upd < 0.1 * upd_prev && upd * (upd / upd_prev) < tol) ||
+             newton_at_rounding_floor(upd, upd_prev, tol);
+    upd_prev = upd;
+  } else {
+    upd_prev = INFINITY;
+  }
+  return accept;
+}
+
 // exp(u) - 1 for |u| >= 0.05 (smaller arguments take the Taylor branch of the caller), all constants in scalar registers.
 // The library expm1 keeps its ~10 polynomial coefficients in vector registers hoisted out of the Newton loop; in the
 // 128-register kernels they were spilled and re-read from scratch -- one dependent memory round trip per Horner step.

@@ -631,14 +631,8 @@ __global__ __launch_bounds__(TMAX) void newton_kernel(const NewtonArgs A) {
           double du[NB];
           load_rhs<NB>(src, RS, row, du);
 #pragma unroll
-          for (int k = 0; k < N; ++k) {
-            const double ck = c[k * ldx + row];
-            upd = fmax(upd, fabs(du[k]) / (fabs(ck) + fabs(cb[k]) + 1e-300));
-            if (!(du[k] == du[k])) upd = INFINITY;
-          }
-          const double a = fabs(du[N]);
-          mphi = fmax(mphi, a);
-          if (!(a == a)) mphi = INFINITY;
+          for (int k = 0; k < N; ++k) upd = newton_norm_species(upd, du[k], c[k * ldx + row], cb[k]);
+          mphi = newton_norm_phi(mphi, du[N]);
         }
         upd = fmax(upd, mphi * A.vt_inv);
         mphi = wave_max(mphi);
@@ -654,51 +648,22 @@ __global__ __launch_bounds__(TMAX) void newton_kernel(const NewtonArgs A) {
           mphi = fmax(mphi, red[0][w]);
           upd = fmax(upd, red[1][w]);
         }
-        double lam = 1.0;
-        if (A.dphi_max > 0.0 && mphi > A.dphi_max) lam = A.dphi_max / mphi;
+        const double lam = newton_damping(mphi, A.dphi_max);
         for (int row = tid; row < nx; row += T) {
           double du[NB];
           load_rhs<NB>(src, RS, row, du);
           double cn[N], cc_[N];
 #pragma unroll
-          for (int k = 0; k < N; ++k) {
-            cc_[k] = c[k * ldx + row];
-            const double t_ = __builtin_fma(lam, du[k], cc_[k]);
-            const double lo = 0.1 * cc_[k];
-            cn[k] = t_ < lo ? lo : t_;      // a concentration never loses more than 90 % per iteration
-          }
-          if constexpr (MPB) {               // ... and neither does the free volume fraction 1 - phi0
-            double f_old = 0.0, f_new = 0.0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-              f_old = __builtin_fma(A.vol[k], cc_[k], f_old);
-              f_new = __builtin_fma(A.vol[k], cn[k], f_new);
-            }
-            const double free_ = 1.0 - f_old;
-            const double target = fmax(0.1 * free_, 1e-12);
-            if ((1.0 - f_new) < target) {
-              const double theta = (free_ - target) / (f_new - f_old);
-#pragma unroll
-              for (int k = 0; k < N; ++k) cn[k] = __builtin_fma(theta, cn[k] - cc_[k], cc_[k]);
-            }
-          }
+          for (int k = 0; k < N; ++k) cc_[k] = c[k * ldx + row];
+          newton_clip_row<N, MPB>(lam, du, cc_, A.vol, cn);
 #pragma unroll
           for (int k = 0; k < N; ++k) c[k * ldx + row] = cn[k];
           phi[row] = __builtin_fma(lam, du[N], phi[row]);
         }
         __syncthreads();
-        if (lam == 1.0) {
-          // strict: the update itself is below tol.  With A.estimate the state is accepted as soon as the quadratic error
-          // estimate of the state just computed, upd^2/upd_prev (two consecutive contracting full steps), is below tol --
-          // the iteration that would only confirm it is skipped (oracle/pnp_physical.py: newton_step(estimate=True))
-          if (upd < A.tol || (A.estimate && upd_prev < INFINITY && upd < 0.1 * upd_prev && upd * (upd / upd_prev) < A.tol) ||
-              newton_at_rounding_floor(upd, upd_prev, A.tol)) {
-            conv = true;
-            break;
-          }
-          upd_prev = upd;
-        } else {
-          upd_prev = INFINITY;
+        if (newton_accept(lam, upd, upd_prev, A.tol, A.estimate)) {
+          conv = true;
+          break;
         }
       }
       total_it += conv ? it : A.maxit + 1;
@@ -999,13 +964,9 @@ __global__ __launch_bounds__(NB >= 5 ? 256 : 512) void newton_pair_kernel(const 
         for (int k = 0; k < N; ++k) {
           ca[k] = ra < nx ? c[k * ldx + ra] : 1.0;
           cbv[k] = rb < nx ? c[k * ldx + rb] : 1.0;
-          upd = fmax(upd, fabs(dua[k]) / (fabs(ca[k]) + fabs(cb[k]) + 1e-300));
-          upd = fmax(upd, fabs(dub[k]) / (fabs(cbv[k]) + fabs(cb[k]) + 1e-300));
-          if (!(dua[k] == dua[k]) || !(dub[k] == dub[k])) upd = INFINITY;
+          upd = newton_norm_species(newton_norm_species(upd, dua[k], ca[k], cb[k]), dub[k], cbv[k], cb[k]);
         }
-        mphi = fmax(fabs(dua[N]), fabs(dub[N]));
-        // fmax drops a NaN operand: test both potential updates, as the other kernels do, so that a NaN update is never accepted
-        if (!(dua[N] == dua[N]) || !(dub[N] == dub[N])) mphi = INFINITY;
+        mphi = newton_norm_phi(newton_norm_phi(mphi, dua[N]), dub[N]);
         upd = fmax(upd, mphi * A.vt_inv);
         mphi = wave_max(mphi);
         upd = wave_max(upd);
@@ -1020,56 +981,22 @@ __global__ __launch_bounds__(NB >= 5 ? 256 : 512) void newton_pair_kernel(const 
           mphi = fmax(mphi, red[0][w]);
           upd = fmax(upd, red[1][w]);
         }
-        double lam = 1.0;
-        if (A.dphi_max > 0.0 && mphi > A.dphi_max) lam = A.dphi_max / mphi;
+        const double lam = newton_damping(mphi, A.dphi_max);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
           const int row = half == 0 ? ra : rb;
           if (row < nx) {
             double cn[N];
-            double f_old = 0.0, f_new = 0.0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-              const double cc_ = half == 0 ? ca[k] : cbv[k];
-              const double du = half == 0 ? dua[k] : dub[k];
-              const double t_ = __builtin_fma(lam, du, cc_);
-              const double lo = 0.1 * cc_;
-              cn[k] = t_ < lo ? lo : t_;
-              if constexpr (MPB) {
-                f_old = __builtin_fma(A.vol[k], cc_, f_old);
-                f_new = __builtin_fma(A.vol[k], cn[k], f_new);
-              }
-            }
-            if constexpr (MPB) {
-              const double free_ = 1.0 - f_old;
-              const double target = fmax(0.1 * free_, 1e-12);
-              if ((1.0 - f_new) < target) {
-                const double theta = (free_ - target) / (f_new - f_old);
-#pragma unroll
-                for (int k = 0; k < N; ++k) {
-                  const double cc_ = half == 0 ? ca[k] : cbv[k];
-                  cn[k] = __builtin_fma(theta, cn[k] - cc_, cc_);
-                }
-              }
-            }
+            newton_clip_row<N, MPB>(lam, half == 0 ? dua : dub, half == 0 ? ca : cbv, A.vol, cn);
 #pragma unroll
             for (int k = 0; k < N; ++k) c[k * ldx + row] = cn[k];
             phi[row] = __builtin_fma(lam, half == 0 ? dua[N] : dub[N], phi[row]);
           }
         }
         __syncthreads();
-        if (lam == 1.0) {
-          // strict: the update itself is below tol.  With A.estimate the state is accepted as soon as the quadratic error
-          // estimate of the state just computed, upd^2/upd_prev (two consecutive contracting full steps), is below tol --
-          // the iteration that would only confirm it is skipped (oracle/pnp_physical.py: newton_step(estimate=True))
-          if (upd < A.tol || (A.estimate && upd_prev < INFINITY && upd < 0.1 * upd_prev && upd * (upd / upd_prev) < A.tol) ||
-              newton_at_rounding_floor(upd, upd_prev, A.tol)) {
-            conv = true;
-            break;
-          }
-          upd_prev = upd;
-        } else {
-          upd_prev = INFINITY;
+        if (newton_accept(lam, upd, upd_prev, A.tol, A.estimate)) {
+          conv = true;
+          break;
         }
       }
       total_it += conv ? it : A.maxit + 1;
@@ -1558,15 +1485,8 @@ __global__ __launch_bounds__(1024, 4) void newton_team_kernel(const NewtonArgs G
         double mphi = 0.0, upd = 0.0;
         for (int row = tid; row < nx; row += T) {
 #pragma unroll
-          for (int k = 0; k < N; ++k) {
-            const double du = REC(row, k)[2 * NB];
-            const double ck = c[k * ldx + row];
-            upd = fmax(upd, fabs(du) / (fabs(ck) + fabs(cb[k]) + 1e-300));
-            if (!(du == du)) upd = INFINITY;
-          }
-          const double a = fabs(REC(row, N)[2 * NB]);
-          mphi = fmax(mphi, a);
-          if (!(a == a)) mphi = INFINITY;
+          for (int k = 0; k < N; ++k) upd = newton_norm_species(upd, REC(row, k)[2 * NB], c[k * ldx + row], cb[k]);
+          mphi = newton_norm_phi(mphi, REC(row, N)[2 * NB]);
         }
         upd = fmax(upd, mphi * A.vt_inv);
         mphi = wave_max(mphi);
@@ -1582,49 +1502,23 @@ __global__ __launch_bounds__(1024, 4) void newton_team_kernel(const NewtonArgs G
           mphi = fmax(mphi, red[0][w]);
           upd = fmax(upd, red[1][w]);
         }
-        double lam = 1.0;
-        if (A.dphi_max > 0.0 && mphi > A.dphi_max) lam = A.dphi_max / mphi;
+        const double lam = newton_damping(mphi, A.dphi_max);
         for (int row = tid; row < nx; row += T) {
-          double cn[N], cc_[N];
+          double du[N], cn[N], cc_[N];
 #pragma unroll
           for (int k = 0; k < N; ++k) {
+            du[k] = REC(row, k)[2 * NB];
             cc_[k] = c[k * ldx + row];
-            const double t_ = __builtin_fma(lam, REC(row, k)[2 * NB], cc_[k]);
-            const double lo = 0.1 * cc_[k];
-            cn[k] = t_ < lo ? lo : t_;
           }
-          if constexpr (MPB) {
-            double f_old = 0.0, f_new = 0.0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-              f_old = __builtin_fma(A.vol[k], cc_[k], f_old);
-              f_new = __builtin_fma(A.vol[k], cn[k], f_new);
-            }
-            const double free_ = 1.0 - f_old;
-            const double target = fmax(0.1 * free_, 1e-12);
-            if ((1.0 - f_new) < target) {
-              const double theta = (free_ - target) / (f_new - f_old);
-#pragma unroll
-              for (int k = 0; k < N; ++k) cn[k] = __builtin_fma(theta, cn[k] - cc_[k], cc_[k]);
-            }
-          }
+          newton_clip_row<N, MPB>(lam, du, cc_, A.vol, cn);
 #pragma unroll
           for (int k = 0; k < N; ++k) c[k * ldx + row] = cn[k];
           phi[row] = __builtin_fma(lam, REC(row, N)[2 * NB], phi[row]);
         }
         __syncthreads();
-        if (lam == 1.0) {
-          // strict: the update itself is below tol.  With A.estimate the state is accepted as soon as the quadratic error
-          // estimate of the state just computed, upd^2/upd_prev (two consecutive contracting full steps), is below tol --
-          // the iteration that would only confirm it is skipped (oracle/pnp_physical.py: newton_step(estimate=True))
-          if (upd < A.tol || (A.estimate && upd_prev < INFINITY && upd < 0.1 * upd_prev && upd * (upd / upd_prev) < A.tol) ||
-              newton_at_rounding_floor(upd, upd_prev, A.tol)) {
-            conv = true;
-            break;
-          }
-          upd_prev = upd;
-        } else {
-          upd_prev = INFINITY;
+        if (newton_accept(lam, upd, upd_prev, A.tol, A.estimate)) {
+          conv = true;
+          break;
         }
       }
       total_it += conv ? it : A.maxit + 1;
@@ -1674,6 +1568,128 @@ struct SweepLayout {
 };
 size_t newton_sweep_doubles(int nb, int nx) { return (size_t)nx * nb * ((nb + 2) / 2 * 2); }
 
+// ---- The iteration engine of the two sweep kernels.  CONTROL FLOW IS WAVE-UNIFORM: every pass of a kernel's loop is ONE Newton
+// iteration of whatever operating point each team currently holds; a team that finishes its point (all timesteps converged or out of
+// iterations) takes its next one (gteam, gteam + nteams, ...) at the top of the next pass, so the teams of a wave never wait
+// for each other's iteration counts.  A team without work (batch exhausted, masked lane, the leftover lanes of the wave) runs
+// along on valid data with its state stores switched off, and the loop ends on a wave-wide vote.  (Letting teams diverge --
+// skip rounds, leave a Newton loop early -- produced wild addresses in the instances that spill registers: values spilled
+// under a partial exec mask came back undefined for the other lanes.)  So every function below is called by all 64 lanes, returns
+// at its end only and branches on wave-wide votes only; what a lane without work must not do is a predicate on a store.
+struct SweepPoint {               // the bookkeeping of a team's operating point (two-sided: the same in both teams of a pair)
+  int64_t bnext;                  // the team's next operating point
+  int64_t b = 0;                  // ... and its current one (valid memory even while the team has no work)
+  bool have = false, fresh = false;
+  int step = 0, it = 0, total_it = 0, st = PNP_STATUS_OK;
+  double upd_prev = INFINITY;
+};
+enum SweepDraw { SWEEP_ITERATE, SWEEP_DRAW_AGAIN, SWEEP_DONE };
+
+// A team without an operating point takes its next one; the vote: iterate, draw again (only masked lanes were drawn), or the batch is done
+__device__ __forceinline__ SweepDraw sweep_draw(SweepPoint& P, const NewtonArgs& G, bool real_team, int64_t nteams) {
+  if (!P.have && real_team && P.bnext < G.B) {
+    P.b = P.bnext;
+    P.bnext += nteams;
+    P.have = !(G.lane_mask && !G.lane_mask[P.b]);
+    P.fresh = true;
+    P.step = 0;
+    P.total_it = 0;
+    P.st = PNP_STATUS_OK;
+  }
+  if (__ballot(P.have) != 0ull) return SWEEP_ITERATE;
+  return __ballot(real_team && P.bnext < G.B) == 0ull ? SWEEP_DONE : SWEEP_DRAW_AGAIN;
+}
+
+// Start of a timestep: the previous time level (elements first, first + stride, ... of the state), then the count of this iteration
+__device__ __forceinline__ void sweep_begin_iteration(SweepPoint& P, const NewtonArgs& G, const double* c, double* co, int first, int stride, int count) {
+  if (__ballot(P.have && P.fresh) != 0ull) {
+    for (int e = first; e < count; e += stride) {
+      const double v = c[e];
+      if (P.have && P.fresh && !G.ext_old) co[e] = v;
+    }
+    team_sync();
+  }
+  if (P.fresh) {
+    P.it = 0;
+    P.upd_prev = INFINITY;
+    P.fresh = false;
+  }
+  P.it += 1;
+}
+
+// Damping, clips, update of row i (oracle/pnp_physical.py: newton_step), lane r holding unknown r of it: the occupied volume fractions
+// before and after the floored step are summed through strip / xs.  store: the team holds an operating point and this row is its own
+template <int NB, bool MPB>
+__device__ __forceinline__ void sweep_update_row(const NewtonArgs& A, double* c, double* phi, const double* W, int ldx, int i, int r, bool spec, bool store,
+                                                 double lam, double* strip, double* xs) {
+  constexpr int N = NB - 1;
+  const double du = W[((size_t)i * NB + r) * SweepLayout<NB>::NW + NB];
+  double cc_ = 0.0, cn = 0.0;
+  if (spec) {
+    cc_ = c[r * ldx + i];
+    cn = newton_floor_step(lam, du, cc_);
+  }
+  if constexpr (MPB) {
+    strip[r] = cc_;
+    xs[r] = cn;
+    team_sync();
+    double f_old = 0.0, f_new = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      f_old = __builtin_fma(A.vol[k], strip[k], f_old);
+      f_new = __builtin_fma(A.vol[k], xs[k], f_new);
+    }
+    team_sync();
+    double theta;
+    if (newton_free_volume(f_old, f_new, theta)) cn = newton_backtrack(theta, cn, cc_);
+  }
+  if (store) {
+    if (spec) c[r * ldx + i] = cn;
+    else phi[i] = __builtin_fma(lam, du, phi[i]);
+  }
+}
+
+// Bookkeeping of the team's operating point: iteration -> timestep -> finished (returned)
+__device__ __forceinline__ bool sweep_advance(SweepPoint& P, const NewtonArgs& A, double lam, double upd) {
+  bool finished = false;
+  if (P.have) {
+    const bool accept = newton_accept(lam, upd, P.upd_prev, A.tol, A.estimate);
+    if (accept || P.it >= A.maxit) {
+      P.total_it += accept ? P.it : A.maxit + 1;
+      if (!accept) P.st = PNP_STATUS_MAXIT;
+      P.step += 1;
+      P.fresh = true;
+      finished = P.step >= A.nsteps;
+    }
+  }
+  return finished;
+}
+
+// A finished operating point: non-finite state -> NaN status; lane `writer` of it writes status and iteration count
+template <int NB>
+__device__ __forceinline__ void sweep_finish(SweepPoint& P, const NewtonArgs& G, bool finished, bool writer, const double* c, const double* phi, int nx,
+                                             int ldx, int r0_, double* strip) {
+  if (__ballot(finished) != 0ull) {
+    double bad = 0.0;
+    for (int e = r0_; e < nx; e += NB) {
+      double sacc = phi[e];
+#pragma unroll
+      for (int k = 0; k < NB - 1; ++k) sacc += c[k * ldx + e];
+      if (!(fabs(sacc) < INFINITY)) bad = 1.0;
+    }
+    strip[r0_] = bad;
+    team_sync();
+#pragma unroll
+    for (int j = 0; j < NB; ++j) bad = fmax(bad, strip[j]);
+    if (finished && writer) {
+      G.status[P.b] = bad > 0.0 ? PNP_STATUS_NAN : P.st;
+      G.iters[P.b] = P.total_it;
+    }
+    team_sync();
+  }
+  if (finished) P.have = false;
+}
+
 template <int NB, int MODE>
 __global__ __launch_bounds__(64, 2) void newton_sweep_kernel(const NewtonArgs G) {
   __shared__ NewtonArgs sA;
@@ -1694,57 +1710,24 @@ __global__ __launch_bounds__(64, 2) void newton_sweep_kernel(const NewtonArgs G)
   const int64_t nteams = (int64_t)gridDim.x * TPW;
   double* W = G.sweep + (size_t)gteam * G.sweep_stride;
   const bool spec = r0_ < N;
-  // CONTROL FLOW IS WAVE-UNIFORM.  The kernel is an iteration engine: every pass of the loop below is ONE Newton iteration of
-  // whatever operating point each team currently holds; a team that finishes its point (all timesteps converged or out of
-  // iterations) takes its next one (gteam, gteam + nteams, ...) at the top of the next pass, so the teams of a wave never wait
-  // for each other's iteration counts.  A team without work (batch exhausted, masked lane, the leftover lanes of the wave) runs
-  // along on valid data with its state stores switched off, and the loop ends on a wave-wide vote.  (Letting teams diverge --
-  // skip rounds, leave a Newton loop early -- produced wild addresses in the instances that spill registers: values spilled
-  // under a partial exec mask came back undefined for the other lanes.)
   const int nx = sA.nx, ldx = sA.ldx;
-  int64_t bnext = gteam;          // the team's next operating point
-  int64_t b = 0;                  // ... and its current one (valid memory even while the team has no work)
-  bool have = false, fresh = false;
-  int step = 0, it = 0, total_it = 0, st = PNP_STATUS_OK;
-  double upd_prev = INFINITY;
+  SweepPoint P{gteam};
 #ifdef PNP_SWEEP_STAMPS
   int stamp_code = 0, stamp_cycles = 0;
 #endif
-  for (;;) {
-    if (!have && real_team && bnext < G.B) {
-      b = bnext;
-      bnext += nteams;
-      have = !(G.lane_mask && !G.lane_mask[b]);
-      fresh = true;
-      step = 0;
-      total_it = 0;
-      st = PNP_STATUS_OK;
-    }
-    if (__ballot(have) == 0ull) {
-      if (__ballot(real_team && bnext < G.B) == 0ull) break;
-      continue;                   // (only masked lanes were drawn: draw again)
-    }
+  for (;;) {      // (the iteration engine: see SweepPoint)
+    const SweepDraw drawn = sweep_draw(P, G, real_team, nteams);
+    if (drawn == SWEEP_DONE) break;
+    if (drawn == SWEEP_DRAW_AGAIN) continue;
     const NewtonArgs& A = sA;
+    const int64_t b = P.b;
     double* c = G.c + (size_t)b * N * ldx;
     double* co = G.c_old + (size_t)b * N * ldx;
     double* phi = G.phi + (size_t)b * ldx;
     const double* cb = G.cbulk + (size_t)b * N;
     const double* wk = G.wk_k + (size_t)b * PNP_MAX_WALL_REACTIONS;
     const double phiM = G.pb[b * 4 + 0], phiB = G.pb[b * 4 + 1];
-    // ---- start of a timestep: previous time level ------------------------------------------------------------------------
-    if (__ballot(have && fresh) != 0ull) {
-      for (int e = r0_; e < N * ldx; e += NB) {
-        const double v = c[e];
-        if (have && fresh && !G.ext_old) co[e] = v;
-      }
-      team_sync();
-    }
-    if (fresh) {
-      it = 0;
-      upd_prev = INFINITY;
-      fresh = false;
-    }
-    it += 1;
+    sweep_begin_iteration(P, G, c, co, r0_, NB, N * ldx);
 #ifdef PNP_SWEEP_STAMPS
     const unsigned long long ts0 = __builtin_readcyclecounter();
 #endif
@@ -1803,16 +1786,9 @@ __global__ __launch_bounds__(64, 2) void newton_sweep_kernel(const NewtonArgs G)
         xs[r] = x;
         if (real_team) rec[NB] = x;
         team_sync();
-        const double ck = c[(spec ? r : 0) * ldx + i];
-        const double rel = fabs(x) / (fabs(ck) + fabs(cb[spec ? r : 0]) + 1e-300);
-        const double a = fabs(x);
-        if (spec) {
-          upd = fmax(upd, rel);
-          if (!(x == x)) upd = INFINITY;
-        } else {
-          mphi = fmax(mphi, a);
-          if (!(a == a)) mphi = INFINITY;
-        }
+        const double ck = c[(spec ? r : 0) * ldx + i], cbk = cb[spec ? r : 0];      // (one unknown per lane: the species lanes feed upd, the potential lane mphi)
+        if (spec) upd = newton_norm_species(upd, x, ck, cbk);
+        else mphi = newton_norm_phi(mphi, x);
       }
     }
     auto team_max = [&](double v) {
@@ -1827,45 +1803,12 @@ __global__ __launch_bounds__(64, 2) void newton_sweep_kernel(const NewtonArgs G)
     mphi = team_max(mphi);
     upd = team_max(upd);
     upd = fmax(upd, mphi * A.vt_inv);
-    double lam = 1.0;
-    if (A.dphi_max > 0.0 && mphi > A.dphi_max) lam = A.dphi_max / mphi;
+    const double lam = newton_damping(mphi, A.dphi_max);
 #ifdef PNP_SWEEP_STAMPS
     const unsigned long long ts2 = __builtin_readcyclecounter();
 #endif
-    // ---- damping, clips, update (oracle/pnp_physical.py: newton_step), row by row -----------------------------------------
-    for (int i = 0; i < nx; ++i) {
-      const int r = r0_;
-      const double du = W[((size_t)i * NB + r) * NW + NB];
-      double cc_ = 0.0, cn = 0.0;
-      if (spec) {
-        cc_ = c[r * ldx + i];
-        const double t_ = __builtin_fma(lam, du, cc_);
-        const double lo = 0.1 * cc_;
-        cn = t_ < lo ? lo : t_;
-      }
-      if constexpr (MPB) {
-        strip[r] = cc_;
-        xs[r] = cn;
-        team_sync();
-        double f_old = 0.0, f_new = 0.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          f_old = __builtin_fma(A.vol[k], strip[k], f_old);
-          f_new = __builtin_fma(A.vol[k], xs[k], f_new);
-        }
-        team_sync();
-        const double free_ = 1.0 - f_old;
-        const double target = fmax(0.1 * free_, 1e-12);
-        if ((1.0 - f_new) < target) {
-          const double theta = (free_ - target) / (f_new - f_old);
-          cn = __builtin_fma(theta, cn - cc_, cc_);
-        }
-      }
-      if (have) {
-        if (spec) c[r * ldx + i] = cn;
-        else phi[i] = __builtin_fma(lam, du, phi[i]);
-      }
-    }
+    // ---- damping, clips, update, row by row --------------------------------------------------------------------------------
+    for (int i = 0; i < nx; ++i) sweep_update_row<NB, MPB>(A, c, phi, W, ldx, i, r0_, spec, P.have, lam, strip, xs);
     team_sync();
 #ifdef PNP_SWEEP_STAMPS
     {   // diagnosis build: per-mille shares of the forward and backward passes of the LAST iteration, cycles per row in the rest
@@ -1875,48 +1818,14 @@ __global__ __launch_bounds__(64, 2) void newton_sweep_kernel(const NewtonArgs G)
       stamp_cycles = (int)(tot / nx);
     }
 #endif
-    // ---- bookkeeping of the team's operating point: iteration -> timestep -> finished -------------------------------------
-    bool finished = false;
-    if (have) {
-      bool accept = false;
-      if (lam == 1.0) {
-        accept = upd < A.tol || (A.estimate && upd_prev < INFINITY && upd < 0.1 * upd_prev && upd * (upd / upd_prev) < A.tol) ||
-              newton_at_rounding_floor(upd, upd_prev, A.tol);
-        upd_prev = upd;
-      } else {
-        upd_prev = INFINITY;
-      }
-      if (accept || it >= A.maxit) {
-        total_it += accept ? it : A.maxit + 1;
-        if (!accept) st = PNP_STATUS_MAXIT;
-        step += 1;
-        fresh = true;
-        finished = step >= A.nsteps;
-      }
-    }
-    if (__ballot(finished) != 0ull) {
-      double bad = 0.0;
-      for (int e = r0_; e < nx; e += NB) {
-        double sacc = phi[e];
-#pragma unroll
-        for (int k = 0; k < N; ++k) sacc += c[k * ldx + e];
-        if (!(fabs(sacc) < INFINITY)) bad = 1.0;
-      }
-      strip[r0_] = bad;
-      team_sync();
-#pragma unroll
-      for (int j = 0; j < NB; ++j) bad = fmax(bad, strip[j]);
-      if (finished && r0_ == 0) {
-        G.status[b] = bad > 0.0 ? PNP_STATUS_NAN : st;
-        G.iters[b] = total_it;
+    const bool finished = sweep_advance(P, A, lam, upd);
+    sweep_finish<NB>(P, G, finished, r0_ == 0, c, phi, nx, ldx, r0_, strip);
 #ifdef PNP_SWEEP_STAMPS
-        G.iters[b] = stamp_code;
-        G.status[b] = stamp_cycles;
-#endif
-      }
-      team_sync();
+    if (finished && r0_ == 0) {      // (in place of the point's iteration count and status)
+      G.iters[b] = stamp_code;
+      G.status[b] = stamp_cycles;
     }
-    if (finished) have = false;
+#endif
   }
 }
 
@@ -1930,7 +1839,7 @@ __global__ __launch_bounds__(64, 2) void newton_sweep_kernel(const NewtonArgs G)
 // occupies twice the waves: for the batch sizes where the one-sided sweep leaves the SIMDs with one or two waves (B ~ 4-16 k at
 // N = 8) that is where the time goes (66 % of a wave's life parked).  Both teams of a pair sit in the same wave
 // and run the same instruction stream; which off-diagonal block is "behind" and which "ahead" is a per-lane select.  Everything
-// else -- assembly, damping, update, stopping rule, wave-uniform iteration engine -- is the one-sided kernel's.
+// else is shared with the one-sided kernel: the assembly (team_assemble_row) and the iteration engine with its update (SweepPoint).
 // ------------------------------------------------------------------------------------------------
 template <int NB, int MODE>
 __global__ __launch_bounds__(64, 2) void newton_sweep2_kernel(const NewtonArgs G) {
@@ -1957,45 +1866,20 @@ __global__ __launch_bounds__(64, 2) void newton_sweep2_kernel(const NewtonArgs G
   const int nx = sA.nx, ldx = sA.ldx;
   const int m = nx >> 1;              // middle row; team 0 owns rows [0, m), team 1 rows (m, nx)
   const int n_up = nx - 1 - m;        // rows of team 1 (m or m - 1)
-  int64_t bnext = gteam;
-  int64_t b = 0;
-  bool have = false, fresh = false;
-  int step = 0, it = 0, total_it = 0, st = PNP_STATUS_OK;
-  double upd_prev = INFINITY;
-  for (;;) {      // CONTROL FLOW IS WAVE-UNIFORM, see newton_sweep_kernel
-    if (!have && real_team && bnext < G.B) {
-      b = bnext;
-      bnext += nteams;
-      have = !(G.lane_mask && !G.lane_mask[b]);
-      fresh = true;
-      step = 0;
-      total_it = 0;
-      st = PNP_STATUS_OK;
-    }
-    if (__ballot(have) == 0ull) {
-      if (__ballot(real_team && bnext < G.B) == 0ull) break;
-      continue;
-    }
+  SweepPoint P{gteam};
+  for (;;) {      // (the iteration engine: see SweepPoint)
+    const SweepDraw drawn = sweep_draw(P, G, real_team, nteams);
+    if (drawn == SWEEP_DONE) break;
+    if (drawn == SWEEP_DRAW_AGAIN) continue;
     const NewtonArgs& A = sA;
+    const int64_t b = P.b;
     double* c = G.c + (size_t)b * N * ldx;
     double* co = G.c_old + (size_t)b * N * ldx;
     double* phi = G.phi + (size_t)b * ldx;
     const double* cb = G.cbulk + (size_t)b * N;
     const double* wk = G.wk_k + (size_t)b * PNP_MAX_WALL_REACTIONS;
     const double phiM = G.pb[b * 4 + 0], phiB = G.pb[b * 4 + 1];
-    if (__ballot(have && fresh) != 0ull) {      // previous time level: each team of the pair copies every other stripe
-      for (int e = r0_ + side * NB; e < N * ldx; e += 2 * NB) {
-        const double v = c[e];
-        if (have && fresh && !G.ext_old) co[e] = v;
-      }
-      team_sync();
-    }
-    if (fresh) {
-      it = 0;
-      upd_prev = INFINITY;
-      fresh = false;
-    }
-    it += 1;
+    sweep_begin_iteration(P, G, c, co, r0_ + side * NB, 2 * NB, N * ldx);      // (each team of the pair copies every other stripe)
     // ---- elimination from both ends ---------------------------------------------------------------------------------------------
     for (int j = 0; j < m; ++j) {
       int r = r0_;
@@ -2061,17 +1945,9 @@ __global__ __launch_bounds__(64, 2) void newton_sweep2_kernel(const NewtonArgs G
       xs[myk] = Y1[0];
       if (real_team && side == 0) W[((size_t)m * NB + myk) * NW + NB] = Y1[0];
       team_sync();
-      const double x = xs[r];
-      const double ck = c[(spec ? r : 0) * ldx + m];
-      const double rel = fabs(x) / (fabs(ck) + fabs(cb[spec ? r : 0]) + 1e-300);
-      const double a = fabs(x);
-      if (spec) {
-        upd = fmax(upd, rel);
-        if (!(x == x)) upd = INFINITY;
-      } else {
-        mphi = fmax(mphi, a);
-        if (!(a == a)) mphi = INFINITY;
-      }
+      const double x = xs[r], ck = c[(spec ? r : 0) * ldx + m], cbk = cb[spec ? r : 0];
+      if (spec) upd = newton_norm_species(upd, x, ck, cbk);
+      else mphi = newton_norm_phi(mphi, x);
     }
     // ---- substitution outwards from the middle ------------------------------------------------------------------------------------
     {
@@ -2087,17 +1963,10 @@ __global__ __launch_bounds__(64, 2) void newton_sweep2_kernel(const NewtonArgs G
         if (act) xs[r] = x;
         if (real_team && act) rec[NB] = x;
         team_sync();
-        const double ck = c[(spec ? r : 0) * ldx + i];
-        const double rel = fabs(x) / (fabs(ck) + fabs(cb[spec ? r : 0]) + 1e-300);
-        const double a = fabs(x);
+        const double ck = c[(spec ? r : 0) * ldx + i], cbk = cb[spec ? r : 0];
         if (act) {
-          if (spec) {
-            upd = fmax(upd, rel);
-            if (!(x == x)) upd = INFINITY;
-          } else {
-            mphi = fmax(mphi, a);
-            if (!(a == a)) mphi = INFINITY;
-          }
+          if (spec) upd = newton_norm_species(upd, x, ck, cbk);
+          else mphi = newton_norm_phi(mphi, x);
         }
       }
     }
@@ -2113,13 +1982,16 @@ __global__ __launch_bounds__(64, 2) void newton_sweep2_kernel(const NewtonArgs G
     mphi = pair_max(mphi);
     upd = pair_max(upd);
     upd = fmax(upd, mphi * A.vt_inv);
-    double lam = 1.0;
-    if (A.dphi_max > 0.0 && mphi > A.dphi_max) lam = A.dphi_max / mphi;
+    const double lam = newton_damping(mphi, A.dphi_max);
     // ---- damping, clips, update: team 0 rows [0, m), team 1 rows [m, nx) ------------------------------------------------------------
     for (int idx = 0; idx < nx - m; ++idx) {
-      const int r = r0_;
       const bool act = side ? true : idx < m;
       const int i = side ? m + idx : (act ? idx : 0);
+      // (The row update written out, floor and backtrack in their formulas.  Through sweep_update_row, and written here with
+      // newton_floor_step / newton_free_volume / newton_backtrack, this kernel is 1.3 to 1.9 % behind its predecessor at N = 8 and 1024
+      // points in three jobs, beyond the parent's spread; in this form it is level (+0.3 ... +0.6 %): profiles/newton_rule.md section 5.
+      // The one-sided kernel is level with the shared form and keeps it.)
+      const int r = r0_;
       const double du = W[((size_t)i * NB + r) * NW + NB];
       double cc_ = 0.0, cn = 0.0;
       if (spec) {
@@ -2146,49 +2018,14 @@ __global__ __launch_bounds__(64, 2) void newton_sweep2_kernel(const NewtonArgs G
           cn = __builtin_fma(theta, cn - cc_, cc_);
         }
       }
-      if (have && act) {
+      if (P.have && act) {
         if (spec) c[r * ldx + i] = cn;
         else phi[i] = __builtin_fma(lam, du, phi[i]);
       }
     }
     team_sync();
-    bool finished = false;
-    if (have) {
-      bool accept = false;
-      if (lam == 1.0) {
-        accept = upd < A.tol || (A.estimate && upd_prev < INFINITY && upd < 0.1 * upd_prev && upd * (upd / upd_prev) < A.tol) ||
-              newton_at_rounding_floor(upd, upd_prev, A.tol);
-        upd_prev = upd;
-      } else {
-        upd_prev = INFINITY;
-      }
-      if (accept || it >= A.maxit) {
-        total_it += accept ? it : A.maxit + 1;
-        if (!accept) st = PNP_STATUS_MAXIT;
-        step += 1;
-        fresh = true;
-        finished = step >= A.nsteps;
-      }
-    }
-    if (__ballot(finished) != 0ull) {
-      double bad = 0.0;
-      for (int e = r0_; e < nx; e += NB) {
-        double sacc = phi[e];
-#pragma unroll
-        for (int k = 0; k < N; ++k) sacc += c[k * ldx + e];
-        if (!(fabs(sacc) < INFINITY)) bad = 1.0;
-      }
-      strip[r0_] = bad;
-      team_sync();
-#pragma unroll
-      for (int jj = 0; jj < NB; ++jj) bad = fmax(bad, strip[jj]);
-      if (finished && r0_ == 0 && side == 0) {
-        G.status[b] = bad > 0.0 ? PNP_STATUS_NAN : st;
-        G.iters[b] = total_it;
-      }
-      team_sync();
-    }
-    if (finished) have = false;
+    const bool finished = sweep_advance(P, A, lam, upd);
+    sweep_finish<NB>(P, G, finished, r0_ == 0 && side == 0, c, phi, nx, ldx, r0_, strip);
   }
 }
 

@@ -238,6 +238,53 @@ __global__ __launch_bounds__(64) void store_window_kernel(const double* __restri
   }
 }
 
+// ---- the damped Newton update of the physical mode (pnp_math.h), one row of N species and the potential per thread ------------------------
+// in: c, du, cb, vol [n][N]; lam, dphi, dphi_max [n].  out: cf = the floored steps and cn = the row after both clips [n][N]; per row
+// row [n][4]: backtrack taken (0 / 1), theta (0 where it is not taken), the largest scaled update of the row's species and the change of its
+// potential (infinite for a NaN); damp [n] = newton_damping(that change, dphi_max)
+template <int N>
+__global__ __launch_bounds__(256) void newton_rule_kernel(const double* __restrict__ c, const double* __restrict__ du, const double* __restrict__ cb,
+                                                          const double* __restrict__ vol, const double* __restrict__ lam, const double* __restrict__ dphi,
+                                                          const double* __restrict__ dphi_max, double* __restrict__ cf, double* __restrict__ cn,
+                                                          double* __restrict__ row, double* __restrict__ damp, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double cc[N], dd[N], out[N];
+  double f_old = 0.0, f_new = 0.0, upd = 0.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    cc[k] = c[i * N + k];
+    dd[k] = du[i * N + k];
+    const double f = newton_floor_step(lam[i], dd[k], cc[k]);
+    cf[i * N + k] = f;
+    f_old = __builtin_fma(vol[i * N + k], cc[k], f_old);
+    f_new = __builtin_fma(vol[i * N + k], f, f_new);
+    upd = newton_norm_species(upd, dd[k], cc[k], cb[i * N + k]);
+  }
+  double theta = 0.0;
+  const bool back = newton_free_volume(f_old, f_new, theta);
+  newton_clip_row<N, true>(lam[i], dd, cc, vol + i * N, out);
+#pragma unroll
+  for (int k = 0; k < N; ++k) cn[i * N + k] = out[k];
+  const double mphi = newton_norm_phi(0.0, dphi[i]);
+  row[i * 4 + 0] = back ? 1.0 : 0.0;
+  row[i * 4 + 1] = back ? theta : 0.0;
+  row[i * 4 + 2] = upd;
+  row[i * 4 + 3] = mphi;
+  damp[i] = newton_damping(mphi, dphi_max[i]);
+}
+
+// in [n]: lam, upd, upd_prev, tol, estimate (0 / 1).  out [n]: accepted (0 / 1) and upd_prev after the call
+__global__ __launch_bounds__(256) void newton_accept_kernel(const double* __restrict__ lam, const double* __restrict__ upd, const double* __restrict__ upd_prev,
+                                                            const double* __restrict__ tol, const double* __restrict__ estimate,
+                                                            double* __restrict__ accept, double* __restrict__ prev_out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double prev = upd_prev[i];
+  accept[i] = newton_accept(lam[i], upd[i], prev, tol[i], estimate[i] != 0.0) ? 1.0 : 0.0;
+  prev_out[i] = prev;
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
 struct Buf {
   void* p = nullptr;
@@ -461,6 +508,63 @@ __attribute__((visibility("default"))) int catunit_tridiag(int P, int G, int dpp
     rc = dev_download(x, dx, n);
   });
   return ok ? rc : EINVAL_;
+}
+
+// c, du, cb, vol, cf, cn: [n][N]; lam, dphi, dphi_max, damp: [n]; row: [n][4] (newton_rule_kernel); N 1, 2, 7 or 8
+__attribute__((visibility("default"))) int catunit_newton_rule(int N, int n, const double* c, const double* du, const double* cb, const double* vol,
+                                                               const double* lam, const double* dphi, const double* dphi_max, double* cf, double* cn,
+                                                               double* row, double* damp) {
+  if (!c || !du || !cb || !vol || !lam || !dphi || !dphi_max || !cf || !cn || !row || !damp || n < 1 || (N != 1 && N != 2 && N != 7 && N != 8)) return EINVAL_;
+  Buf dc, ddu, dcb, dvol, dlam, dph, dmx, dcf, dcn, drow, ddamp;
+  const size_t nn = (size_t)n * N;
+  CATUNIT_TRY(dev_upload(dc, c, nn));
+  CATUNIT_TRY(dev_upload(ddu, du, nn));
+  CATUNIT_TRY(dev_upload(dcb, cb, nn));
+  CATUNIT_TRY(dev_upload(dvol, vol, nn));
+  CATUNIT_TRY(dev_upload(dlam, lam, n));
+  CATUNIT_TRY(dev_upload(dph, dphi, n));
+  CATUNIT_TRY(dev_upload(dmx, dphi_max, n));
+  CATUNIT_TRY(dev_alloc(dcf, nn));
+  CATUNIT_TRY(dev_alloc(dcn, nn));
+  CATUNIT_TRY(dev_alloc(drow, (size_t)n * 4));
+  CATUNIT_TRY(dev_alloc(ddamp, n));
+  const int blocks = (n + 255) / 256;
+  switch (N) {
+#define CATUNIT_RULE(NN)                                                                                                                   \
+  case NN:                                                                                                                                 \
+    newton_rule_kernel<NN><<<blocks, 256>>>(dc.d(), ddu.d(), dcb.d(), dvol.d(), dlam.d(), dph.d(), dmx.d(), dcf.d(), dcn.d(), drow.d(), \
+                                            ddamp.d(), n);                                                                                 \
+    break;
+    CATUNIT_RULE(1)
+    CATUNIT_RULE(2)
+    CATUNIT_RULE(7)
+    CATUNIT_RULE(8)
+#undef CATUNIT_RULE
+    default: return EINVAL_;
+  }
+  CATUNIT_TRY(finish());
+  CATUNIT_TRY(dev_download(cf, dcf, nn));
+  CATUNIT_TRY(dev_download(cn, dcn, nn));
+  CATUNIT_TRY(dev_download(row, drow, (size_t)n * 4));
+  return dev_download(damp, ddamp, n);
+}
+
+// lam, upd, upd_prev, tol, estimate, accept, prev_out: [n] (newton_accept_kernel)
+__attribute__((visibility("default"))) int catunit_newton_accept(int n, const double* lam, const double* upd, const double* upd_prev, const double* tol,
+                                                                 const double* estimate, double* accept, double* prev_out) {
+  if (!lam || !upd || !upd_prev || !tol || !estimate || !accept || !prev_out || n < 1) return EINVAL_;
+  Buf dl, du, dp, dt, de, da, dpo;
+  CATUNIT_TRY(dev_upload(dl, lam, n));
+  CATUNIT_TRY(dev_upload(du, upd, n));
+  CATUNIT_TRY(dev_upload(dp, upd_prev, n));
+  CATUNIT_TRY(dev_upload(dt, tol, n));
+  CATUNIT_TRY(dev_upload(de, estimate, n));
+  CATUNIT_TRY(dev_alloc(da, n));
+  CATUNIT_TRY(dev_alloc(dpo, n));
+  newton_accept_kernel<<<(n + 255) / 256, 256>>>(dl.d(), du.d(), dp.d(), dt.d(), de.d(), da.d(), dpo.d(), n);
+  CATUNIT_TRY(finish());
+  CATUNIT_TRY(dev_download(accept, da, n));
+  return dev_download(prev_out, dpo, n);
 }
 
 // doubles every row buffer (catunit_load_row, catunit_store_row) resp. window buffer (catunit_load_window, catunit_store_window) must hold

@@ -1,8 +1,11 @@
 """Driven inputs for the physical mode's damped Newton update (test infrastructure, no tests of its own).
 
 The update has four data-dependent branches -- the dphi_max scaling, the floor at a tenth of the previous iterate, the free-volume
-backtrack of steric ions and three exits -- in nine hand-written copies (pnp_newton.hip: pair, row-per-thread, team, sweep, two-sided
-sweep; pnp_lane.hip: separate passes and the fused update; pnp_lane2.hip; pnp_lane4.hip).  The census's inputs (|phiM| <= 0.15 V,
+backtrack of steric ions and three exits -- in one definition (pnp_math.h: newton_damping, newton_floor_step, newton_free_volume,
+newton_backtrack, newton_accept) with seven call sites for the eight kernel families (pnp_newton.hip: pair, row-per-thread, team, the
+one-sided sweep's row update and the bookkeeping both sweep kernels share; pnp_lane.hip: separate passes and the fused update;
+pnp_lane_cols.h for the lane pair and quad).  The two-sided sweep writes floor and backtrack out in its row update (measured:
+profiles/newton_rule.md section 5).  The census's inputs (|phiM| <= 0.15 V,
 cref = 10, radius 3.5e-10 m, Stern capacitance 0.25 F/m^2) never reach the backtrack; the cases of REGIMES do.
 
 Recipes (RECIPES).  'crowded': radius 5.0e-10 m on every species, Stern capacitance 1.0 F/m^2, cref = 200, phiM in -0.8 .. 0.8 V: the

@@ -24,7 +24,7 @@ PS = (1, 2, 4, 8, 16)
 FN = {'fast_rcp': 0, 'fast_rcp2': 1, 'nrcp': 2, 'expm1_sc': 3, 'log1p_sc': 4, 'bernoulli': 5}
 SYMBOLS = ('catunit_scalar', 'catunit_edge_flux', 'catunit_wave_moves', 'catunit_read_lane', 'catunit_pick_blocked', 'catunit_wave_scan',
            'catunit_blocked_scan', 'catunit_blocked_scan_sum', 'catunit_tridiag', 'catunit_row_alloc', 'catunit_win_alloc', 'catunit_load_row',
-           'catunit_store_row', 'catunit_load_window', 'catunit_store_window', 'catunit_col_lanes')
+           'catunit_store_row', 'catunit_load_window', 'catunit_store_window', 'catunit_col_lanes', 'catunit_newton_rule', 'catunit_newton_accept')
 
 # the bars (the header comments' own figures with the allowance of the design note, or its derivations)
 RCP1_BAR = 2 * 2.2e-15          # fast_rcp, relative
@@ -688,3 +688,269 @@ def canaries(n, first=0):
 def distinct(n, first=1):
     """distinct non-zero source values"""
     return (first + np.arange(n)) + 0.25
+
+
+# ---- the damped Newton update of the physical mode (pnp_math.h: newton_norm_species, newton_norm_phi, newton_damping, newton_floor_step, newton_free_volume,
+# ---- newton_backtrack, newton_clip_row, newton_accept), written from oracle/pnp_physical.py: newton_step and at_rounding_floor -------------
+RULE_NS = (1, 2, 7, 8)
+RULE_TOL = 1e-10
+FREE_MIN = 1e-12               # oracle/pnp_physical.py: FREE_MIN (tests/test_primitives_ref.py compares)
+RULE_MUTANTS = ('no floor', 'floor at a fifth', 'no backtrack', 'backtrack always', 'no free_min', 'nan dropped (species)', 'nan dropped (potential)',
+                'no damping', 'damping without the switch')
+ACCEPT_MUTANTS = ('damped steps accepted', 'no tol exit', 'no estimate exit', 'estimate on the first iteration', 'estimate without contraction',
+                  'no rounding floor', 'rounding floor at half', 'upd_prev kept after a damped step')
+
+
+def newton_rule(N, rows):
+    """the rule functions on the device: rows as newton_rule_rows returns them -> the dictionary newton_rule_twin returns (no 'free_min')"""
+    c, du, cb, vol = (_in(rows[k]).reshape(-1, N) for k in ('c', 'du', 'cb', 'vol'))
+    n = c.shape[0]
+    lam, dphi, dphi_max = (_in(rows[k]).reshape(n) for k in ('lam', 'dphi', 'dphi_max'))
+    cf, cn, row, damp = np.empty((n, N)), np.empty((n, N)), np.empty((n, 4)), np.empty(n)
+    _check(load_library().catunit_newton_rule(N, n, _p(c), _p(du), _p(cb), _p(vol), _p(lam), _p(dphi), _p(dphi_max), _p(cf), _p(cn), _p(row), _p(damp)),
+           'catunit_newton_rule')
+    return {'cf': cf, 'cn': cn, 'floor': cf == 0.1 * c, 'back': row[:, 0] != 0.0, 'theta': row[:, 1], 'upd': row[:, 2], 'mphi': row[:, 3], 'damp': damp, 'damped': damp != 1.0}
+
+
+def newton_accept(t):
+    """newton_accept on the device: t [n][5] = (lam, upd, upd_prev, tol, estimate) -> accepted [n] (bool), upd_prev afterwards [n]"""
+    t = _in(t).reshape(-1, 5)
+    cols = [np.ascontiguousarray(t[:, k]) for k in range(5)]
+    acc, prev = np.empty(t.shape[0]), np.empty(t.shape[0])
+    _check(load_library().catunit_newton_accept(t.shape[0], *[_p(v) for v in cols], _p(acc), _p(prev)), 'catunit_newton_accept')
+    return acc != 0.0, prev
+
+
+class _FP(object):
+    """fp64 as the device computes: every operation rounded once, a multiply-add where the header writes one"""
+    num = staticmethod(float)
+
+    @staticmethod
+    def fma(a, b, c):
+        if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(c)):
+            with np.errstate(invalid='ignore', over='ignore'):
+                return float(np.float64(a) * np.float64(b) + np.float64(c))
+        return float(mpf(a) * mpf(b) + mpf(c))
+
+    @staticmethod
+    def div(a, b):
+        with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+            return float(np.float64(a) / np.float64(b))
+
+
+class _MP(object):
+    """exact arithmetic on the same doubles (200 bits)"""
+    num = staticmethod(lambda v: mpf(float(v)))
+    fma = staticmethod(lambda a, b, c: a * b + c)
+    div = staticmethod(lambda a, b: a / b)
+
+
+def _rule_row(X, c, du, cb, vol, lam, dphi, dphi_max, mutant):
+    N = len(c)
+    inf = X.num(np.inf)
+    cf, floor = [], []
+    for k in range(N):
+        t = X.fma(lam, du[k], c[k])
+        lo = (X.num(0.2) if mutant == 'floor at a fifth' else X.num(0.1)) * c[k]
+        fl = bool(t < lo) and mutant != 'no floor'
+        floor.append(fl)
+        cf.append(lo if fl else t)
+    f_old = f_new = X.num(0.0)
+    for k in range(N):
+        f_old = X.fma(vol[k], c[k], f_old)
+        f_new = X.fma(vol[k], cf[k], f_new)
+    free = 1 - f_old
+    free_min = bool(X.num(0.1) * free < X.num(FREE_MIN)) and mutant != 'no free_min'
+    target = X.num(FREE_MIN) if free_min else X.num(0.1) * free
+    back = (bool((1 - f_new) < target) or mutant == 'backtrack always') and mutant != 'no backtrack'
+    theta = X.div(free - target, f_new - f_old) if back else X.num(0.0)
+    cn = [X.fma(theta, cf[k] - c[k], c[k]) for k in range(N)] if back else list(cf)
+
+    upd = X.num(0.0)
+    for k in range(N):
+        rel = X.div(abs(du[k]), abs(c[k]) + abs(cb[k]) + X.num(1e-300))
+        if du[k] != du[k] and mutant != 'nan dropped (species)':
+            rel = inf
+        upd = rel if rel > upd else upd            # (fmax: a NaN operand is dropped)
+    mphi = abs(dphi)
+    if mphi != mphi and mutant != 'nan dropped (potential)':
+        mphi = inf
+    damped = bool(mphi > dphi_max) and (dphi_max > 0 or mutant == 'damping without the switch') and mutant != 'no damping'
+    return {'cf': cf, 'cn': cn, 'floor': floor, 'back': back, 'free_min': back and free_min, 'theta': theta, 'upd': upd, 'mphi': mphi,
+            'damp': X.div(dphi_max, mphi) if damped else X.num(1.0), 'damped': damped}
+
+
+RULE_VALUES = ('cf', 'cn', 'theta', 'upd', 'mphi', 'damp')
+# ulp of the exact value: twice the worst error measured on the MI355X (profiles/primitives_unit.md: cf 0.500, cn 2.230, theta 10.168,
+# upd 1.090, damp 0.498; mphi is |x|, exact).  theta is a quotient of two rounded sums, and cn after a backtrack carries its error
+RULE_BARS = {'cf': 1.0, 'cn': 4.46, 'theta': 20.34, 'upd': 2.18, 'mphi': 0.0, 'damp': 1.0}
+RULE_DECISIONS = ('floor', 'back', 'damped')
+
+
+def newton_rule_twin(rows, exact=False, mutant=None):
+    """the CPU twin, row by row.  exact: in multiprecision, the values as (hi, lo) pairs (rows with a non-finite input: evaluated in fp64,
+    lo = 0).  Decisions: 'floor' [n][N], 'back', 'free_min' (the backtrack with 0.1 free < FREE_MIN), 'damped' [n]"""
+    N = np.asarray(rows['c']).shape[1]
+    out = {k: [] for k in RULE_VALUES + RULE_DECISIONS + ('free_min',)}
+    for i in range(len(rows['lam'])):
+        args = [rows[k][i] for k in ('c', 'du', 'cb', 'vol', 'lam', 'dphi', 'dphi_max')]
+        finite = all(np.isfinite(np.asarray(a, float)).all() for a in args)
+        X = _MP if exact and finite else _FP
+        r = _rule_row(X, *[[X.num(v) for v in a] if np.ndim(a) else X.num(a) for a in args], mutant)
+        for k in out:
+            out[k].append(r[k])
+    res = {k: np.array(out[k], dtype=bool).reshape(-1, N) if k == 'floor' else np.array(out[k], dtype=bool) for k in RULE_DECISIONS + ('free_min',)}
+    for k in RULE_VALUES:
+        flat = [v for r in out[k] for v in (r if isinstance(r, list) else [r])]
+        if exact:
+            hi, lo = _hilo([v if isinstance(v, mpf) else mpf(v) for v in flat])
+            res[k] = (hi.reshape(-1, N), lo.reshape(-1, N)) if k in ('cf', 'cn') else (hi, lo)
+        else:
+            res[k] = np.array(flat, float).reshape(-1, N) if k in ('cf', 'cn') else np.array(flat, float)
+    return res
+
+
+def newton_rule_rows(N):
+    """About 130 rows of N species: 'kind' names what each row is there for.  No comparison of the rule sits at a tie: the floor is missed
+    or overshot by 5 % of c at least, the free volume left is at least four times or at most a tenth of what the backtrack allows, and
+    where the 1e-12 floor of the free volume decides, the occupied fraction is exact in fp64 (dyadic volumes, concentrations powers of two)."""
+    rng = np.random.default_rng(7000 + N)
+    rows = {k: [] for k in ('c', 'du', 'cb', 'vol', 'lam', 'dphi', 'dphi_max', 'kind')}
+
+    def add(kind, c, du, vol, lam, dphi=None, dphi_max=0.05):
+        rows['kind'].append(kind)
+        rows['c'].append(c)
+        rows['du'].append(du)
+        rows['cb'].append(rng.uniform(0.0, 20.0, N))
+        rows['vol'].append(vol)
+        rows['lam'].append(lam)
+        rows['dphi'].append(rng.uniform(0.06, 0.3) * rng.choice([-1.0, 1.0]) if dphi is None else dphi)
+        rows['dphi_max'].append(dphi_max)
+
+    def filled(c, f):          # volumes with sum_k vol_k c_k = f (to rounding)
+        w = rng.uniform(0.2, 1.0, N)
+        return f * w / w.sum() / c
+    for j in range(24):         # mild rows: no clip; the potential below and above dphi_max, dphi_max switched off
+        c = rng.uniform(0.5, 50.0, N)
+        add('plain', c, c * rng.uniform(-0.5, 0.5, N), filled(c, rng.uniform(0.05, 0.4)), 1.0 if j % 2 else rng.uniform(0.05, 0.95),
+            dphi=rng.uniform(0.001, 0.04) * (-1.0) ** j if j % 3 == 0 else None, dphi_max=(0.05, 0.05, 0.0, -1.0)[j % 4])
+    for j in range(24):         # the floor in some slots (every slot at N = 1), the others mild
+        c = rng.uniform(0.5, 50.0, N)
+        lam = 1.0 if j % 2 else rng.uniform(0.05, 0.95)
+        hit = rng.uniform(size=N) < 0.5
+        hit[rng.integers(N)] = True
+        add('floor', c, np.where(hit, -c * rng.uniform(0.95, 3.0, N) / lam, c * rng.uniform(-0.5, 0.5, N)), filled(c, rng.uniform(0.05, 0.4)), lam)
+    for j in range(24):         # crowded rows whose ions grow: the free volume would fall below a tenth
+        c = rng.uniform(0.5, 50.0, N)
+        lam = 1.0 if j % 2 else rng.uniform(0.3, 0.95)
+        add('backtrack', c, c * rng.uniform(0.5, 2.0, N) / lam, filled(c, rng.uniform(0.7, 0.95)), lam)
+    for j in range(12):         # ... with the floor in one slot as well (N >= 2: the others carry the growth)
+        c = rng.uniform(0.5, 50.0, N)
+        du = c * rng.uniform(0.8, 2.0, N)
+        vol = filled(c, rng.uniform(0.7, 0.95))
+        if N > 1:               # (the floored slot holds a tenth of the occupied volume)
+            k = rng.integers(N)
+            du[k] *= -1.5
+            rest = (vol * c).sum() - vol[k] * c[k]
+            vol = np.where(np.arange(N) == k, 0.1 * (vol * c).sum() / c, vol * 0.9 * (vol * c).sum() / rest)
+        add('backtrack', c, du, vol, 1.0)
+    for j in range(24):         # 0.1 free < 1e-12: f_old = 1 - d 2^-43 exactly, d = 36 .. 52 (free 4.1e-12 .. 5.9e-12)
+        c = 2.0 ** rng.integers(-2, 4, N)
+        w = rng.integers(1, 1024 // N, N) / 1024.0
+        w[-1] = 1.0 - rng.integers(36, 53) * 2.0 ** -43 - w[:-1].sum()
+        grow = j % 3 != 0       # two in three grow (backtrack with the 1e-12 target), the others shrink (no backtrack)
+        add('free_min' if grow else 'free_min, shrinking', c, c * rng.uniform(0.1, 0.6, N) * (1.0 if grow else -1.0), w / c, 1.0)
+    for bad in (np.nan, np.inf, -np.inf):       # a non-finite update in a species slot and in the potential slot
+        for slot in sorted({0, N - 1}):
+            c = rng.uniform(0.5, 50.0, N)
+            du = c * rng.uniform(-0.5, 0.5, N)
+            du[slot] = bad
+            add('non-finite species', c, du, filled(c, 0.3), 1.0)
+        c = rng.uniform(0.5, 50.0, N)
+        add('non-finite potential', c, c * rng.uniform(-0.5, 0.5, N), filled(c, 0.3), 1.0, dphi=bad)
+    return {k: (v if k == 'kind' else np.array(v)) for k, v in rows.items()}
+
+
+def perturbed(rows, rel, seed):
+    """every input moved by a relative `rel` of random sign"""
+    rng = np.random.default_rng(seed)
+    return {k: (v if k == 'kind' else v * (1.0 + rel * rng.choice([-1.0, 1.0], np.shape(v)))) for k, v in rows.items()}
+
+
+def check_newton_rule(got, fp, exact, bars, kinds=None):
+    """got against the twin: the decisions equal those of BOTH evaluations of the twin (fp64 and multiprecision agree: no tie), the values
+    within bars[name] ulp of the multiprecision ones (non-finite rows: equal to the fp64 twin's, NaN matching NaN).  Returns the worst
+    error per value in ulp"""
+    for k in RULE_DECISIONS:
+        assert np.array_equal(fp[k], exact[k]), 'the twin decides %r differently in fp64 and in multiprecision: an input sits at a tie' % k
+        bad = np.argwhere(np.asarray(got[k]) != exact[k])
+        assert bad.size == 0, '%s: row %d (%s) decides %r, the twin %r' % (k, bad[0][0], None if kinds is None else kinds[bad[0][0]], got[k][tuple(bad[0])], exact[k][tuple(bad[0])])
+    worst = {}
+    for k in RULE_VALUES:
+        err = ulp_error(got[k], exact[k])
+        err = np.where((np.asarray(got[k]) == 0.0) & (exact[k][0] == 0.0), 0.0, err)
+        j = np.unravel_index(int(np.argmax(err)), err.shape)
+        worst[k] = float(err[j])
+        assert worst[k] <= bars[k], '%s: %.3f ulp in row %d (%s), bar %g' % (k, worst[k], j[0], None if kinds is None else kinds[j[0]], bars[k])
+    return worst
+
+
+# (lam, upd, upd_prev, tol, estimate) and what each tuple is there for; 'alone': exactly this exit fires
+def newton_accept_tuples():
+    tol, inf = RULE_TOL, np.inf
+    t = [((1.0, 5e-11, inf, tol, 0), 'tol exit alone, first iteration'),
+         ((1.0, 5e-11, 1e-3, tol, 0), 'tol exit alone'),
+         ((1.0, 5e-11, 3e-5, tol, 1), 'below tol with the estimate as well'),
+         ((1.0, 1e-8, 1e-4, tol, 1), 'estimate exit alone'),
+         ((1.0, 1e-8, 1e-4, tol, 0), 'estimate switched off'),
+         ((1.0, 1e-8, inf, tol, 1), 'estimate on the first iteration (upd_prev = inf)'),
+         ((1.0, 3e-10, 1.5e-9, tol, 1), 'estimate below tol but contraction above a tenth'),
+         ((1.0, 1e-6, 1e-4, tol, 1), 'estimate above tol'),
+         ((1.0, 3.2e-9, 3e-9, tol, 0), 'rounding floor alone'),
+         ((1.0, 3.2e-9, 3e-9, tol, 1), 'rounding floor alone (estimate on)'),
+         ((1.0, 2.9e-9, 3e-9, tol, 0), 'inside 100 tol but shrinking'),
+         ((1.0, 2e-8, 3e-9, tol, 0), 'not smaller, but above 100 tol'),
+         ((1.0, 3e-9, 2e-8, tol, 0), 'previous update above 100 tol'),
+         ((1.0, 3e-9, inf, tol, 0), 'inside 100 tol on the first iteration'),
+         ((0.5, 1e-12, inf, tol, 0), 'damped step below tol'),
+         ((0.999999, 1e-12, 1e-12, tol, 1), 'damped step below tol, every exit otherwise open'),
+         ((0.25, 3.2e-9, 3e-9, tol, 1), 'damped step on the rounding floor'),
+         ((1.0, 0.3, 0.9, tol, 1), 'far from the solution'),
+         ((1.0, inf, 1e-9, tol, 1), 'infinite update (a NaN in the update)'),
+         ((1.0, 5e-7, 1e-3, 1e-6, 0), 'another tolerance: tol exit'),
+         ((1.0, 4e-5, 3e-5, 1e-6, 0), 'another tolerance: rounding floor')]
+    for ratio in (0.5, 0.7, 0.9, 0.99):      # linearly converging: every update a fixed fraction of the one before, from 5e-9 down to below tol
+        u = 5e-9
+        while u / ratio >= tol:
+            t.append(((1.0, u * ratio, u, tol, 0), 'linear sequence, ratio %g' % ratio))
+            t.append(((1.0, u * ratio, u, tol, 1), 'linear sequence, ratio %g (estimate on)' % ratio))
+            u *= ratio
+    return np.array([a for a, _ in t], float), [w for _, w in t]
+
+
+def newton_accept_twin(t, mutant=None):
+    """oracle/pnp_physical.py: newton_step's exits and at_rounding_floor.  Returns accepted [n], upd_prev afterwards [n] and which of the three
+    conditions held [n][3] (tol, estimate, rounding floor; all False on a damped step)"""
+    acc, prev_out, fired = [], [], []
+    for lam, upd, prev, tol, est in np.asarray(t, float).reshape(-1, 5):
+        full = lam == 1.0 or mutant == 'damped steps accepted'
+        w = 100.0 * tol
+        with np.errstate(invalid='ignore', divide='ignore'):
+            f = (bool(upd < tol) and mutant != 'no tol exit',
+                 bool(est != 0 and (np.isfinite(prev) or mutant == 'estimate on the first iteration') and
+                      (upd < 0.1 * prev or mutant == 'estimate without contraction') and upd * (upd / prev) < tol) and mutant != 'no estimate exit',
+                 bool(prev < w and upd < w and (upd > 0.5 * prev if mutant == 'rounding floor at half' else upd >= prev)) and mutant != 'no rounding floor')
+        f = f if full else (False, False, False)
+        acc.append(any(f))
+        fired.append(f)
+        prev_out.append(upd if lam == 1.0 else (prev if mutant == 'upd_prev kept after a damped step' else np.inf))
+    return np.array(acc), np.array(prev_out), np.array(fired)
+
+
+def check_newton_accept(acc, prev_out, t, what=None):
+    """the decision and the new upd_prev against the twin, exactly"""
+    want, wprev, _ = newton_accept_twin(t)
+    bad = np.nonzero(np.asarray(acc) != want)[0]
+    assert bad.size == 0, 'tuple %d %r (%s): accepted %r, the twin %r' % (bad[0], tuple(np.asarray(t)[bad[0]]), None if what is None else what[bad[0]], acc[bad[0]], want[bad[0]])
+    bad = np.nonzero(np.asarray(prev_out) != wprev)[0]
+    assert bad.size == 0, 'tuple %d (%s): upd_prev becomes %r, the twin %r' % (bad[0], None if what is None else what[bad[0]], prev_out[bad[0]], wprev[bad[0]])

@@ -277,3 +277,29 @@ def test_tridiag_wave(P):
             report('tridiag_wave<%d, %d, %s>: worst forward error / (kappa_inf (P + 6) 2.2e-15): %s' % (
                 P, G, str(dpp).lower(), ', '.join('%s %.4f' % (cls, worst[(G, dpp, cls)]) for cls in U.CLASSES)))
     report('tridiag_wave<%d>: system g of a G-wide call bit-identical to the same system alone: %s; DPP1 bit-identical to the LDS path: True' % (P, identical_alone))
+
+
+# ---- the damped Newton update (pnp_math.h): decisions exactly, values in ulp of the twin evaluated in multiprecision ---------------------------------
+# (bars: U.RULE_BARS, twice the worst error measured on the MI355X: profiles/primitives_unit.md)
+@pytest.mark.parametrize('N', U.RULE_NS)
+def test_newton_rule(N):
+    rows = U.newton_rule_rows(N)
+    fp, exact = U.newton_rule_twin(rows), U.newton_rule_twin(rows, exact=True)
+    got = U.newton_rule(N, rows)
+    free = {k: np.inf for k in U.RULE_VALUES}
+    worst = U.check_newton_rule(got, fp, exact, free, rows['kind'])          # the decisions; the figures before anything is held to them
+    report('newton rule, N = %d: worst ulp %s; %d rows, floor in %d, backtrack in %d (1e-12 floor of the free volume in %d), damped %d' % (
+        N, ', '.join('%s %.3f' % (k, worst[k]) for k in U.RULE_VALUES), len(rows['lam']), got['floor'].any(axis=1).sum(), got['back'].sum(),
+        exact['free_min'].sum(), got['damped'].sum()))
+    same = all(np.array_equal(got[k], fp[k], equal_nan=True) for k in U.RULE_VALUES)
+    report('newton rule, N = %d: bit-identical to the fp64 twin with the header\'s multiply-adds: %s' % (N, same))
+    bad = ~np.isfinite(rows['du']).all(axis=1) | ~np.isfinite(rows['dphi'])
+    assert bad.sum() >= 6 and all(np.array_equal(got[k][bad], fp[k][bad], equal_nan=True) for k in U.RULE_VALUES)
+    U.check_newton_rule(got, fp, exact, U.RULE_BARS, rows['kind'])
+
+
+def test_newton_accept():
+    t, what = U.newton_accept_tuples()
+    acc, prev = U.newton_accept(t)
+    report('newton_accept: %d tuples, %d accepted' % (len(what), acc.sum()))
+    U.check_newton_accept(acc, prev, t, what)

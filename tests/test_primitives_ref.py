@@ -6,7 +6,8 @@ the bars of the device functions over the same arguments (it had never been chec
 helper the GPU tests use is shown to bite: a plain fp64 NumPy emulation of the operation passes it and each mutant fails it --
 reciprocals of seed accuracy (4.6e-8) in the Thomas solve, a prefix scan with one of its six stages skipped or with the row_bcast:31
 stage written into rows 1, 3, the 1/30240 coefficient of B replaced by 1/30000, a system whose c[m-1] is not zeroed, a store (and a
-load) whose range check ends one double late."""
+load) whose range check ends one double late; for the damped Newton update (pnp_math.h) a twin with each branch of the rule taken out,
+moved or taken always."""
 import ctypes as C
 import math
 import os
@@ -62,7 +63,7 @@ def test_the_harness_includes_only_the_shared_headers():
 def test_the_library_exports_exactly_the_declared_symbols(libpath):
     src = open(os.path.join(ROOT, 'tests', 'csrc', 'primitives_harness.hip')).read()
     declared = sorted(set(re.findall(r'\bint\s+(catunit_[a-z0-9_]+)\s*\(', src)))
-    assert declared == sorted(U.SYMBOLS) and len(declared) == 16
+    assert declared == sorted(U.SYMBOLS) and len(declared) == 18
     lib = C.CDLL(libpath)
     for s in declared:
         assert hasattr(lib, s), s
@@ -78,7 +79,7 @@ def test_every_kernel_is_in_namespace_catunit_and_every_tridiag_instance_is_ther
     assert compiled and all(n.startswith('catunit::') for n in compiled), sorted(n for n in compiled if not n.startswith('catunit::'))
     tri = {'catunit::tridiag_kernel<%d, %d, %s>' % (P, G, d) for P in U.PS for G in (1, 2, 3) for d in ('false', 'true')}
     assert len(tri) == 30 and tri <= compiled, sorted(tri - compiled)
-    for fam, count in (('scalar_kernel', 6), ('col_lanes_kernel', 2), ('pick_blocked_kernel', 5), ('wave_scan_kernel', 2), ('blocked_scan_kernel', 10),
+    for fam, count in (('scalar_kernel', 6), ('newton_rule_kernel', 4), ('newton_accept_kernel', 1), ('col_lanes_kernel', 2), ('pick_blocked_kernel', 5), ('wave_scan_kernel', 2), ('blocked_scan_kernel', 10),
                        ('blocked_scan_sum_kernel', 5), ('load_row_kernel', 5), ('store_row_kernel', 10), ('load_window_kernel', 13),
                        ('store_window_kernel', 14)):
         assert sum(K.family(n) == 'catunit::' + fam for n in compiled) == count, fam
@@ -116,6 +117,8 @@ def test_invalid_arguments_are_refused_before_any_device_call(libpath):
     assert lib.catunit_scalar(6, p, p, 8) == 1 and lib.catunit_scalar(0, p, p, 0) == 0
     assert lib.catunit_col_lanes(3, p, p, p, p) == 1 and lib.catunit_col_lanes(8, p, p, p, p) == 1
     assert lib.catunit_pick_blocked(5, p, p) == 1 and lib.catunit_blocked_scan(3, 0, p, p, p, p, 1) == 1
+    assert lib.catunit_newton_rule(3, 1, *([p] * 11)) == 1 and lib.catunit_newton_rule(2, 0, *([p] * 11)) == 1      # N is 1, 2, 7 or 8
+    assert lib.catunit_newton_accept(0, *([p] * 7)) == 1
 
 
 # ---- the references --------------------------------------------------------------------------------------------------------------------
@@ -339,3 +342,93 @@ def test_row_and_window_helpers_fail_a_range_check_that_ends_one_double_late(P):
             if not np.array_equal(late, good):
                 assert fails(U.check_window_store, late, before, v, nrec, P, mode)
             assert fails(U.check_window_store, before, before, v, nrec, P, mode)      # nothing stored at all
+
+
+# ---- the damped Newton update: the twin (oracle/pnp_physical.py: newton_step, at_rounding_floor) and its mutants ---------------------------------
+# the fp64 twin with the header's multiply-adds is held to the bars of the device (U.RULE_BARS; on the MI355X the two agree bit for bit)
+TWIN_BARS = U.RULE_BARS
+
+
+@pytest.fixture(scope='module', params=U.RULE_NS)
+def rule(request):
+    rows = U.newton_rule_rows(request.param)
+    return rows, U.newton_rule_twin(rows), U.newton_rule_twin(rows, exact=True)
+
+
+def test_newton_rule_rows_hold_what_the_design_asks_for(rule):
+    rows, fp, exact = rule
+    kind = np.array(rows['kind'])
+    N = rows['c'].shape[1]
+    assert 100 <= kind.size <= 400 and FREE_MIN_IS_THE_ORACLES()
+    assert exact['floor'][kind == 'floor'].any(axis=1).all() and not exact['floor'][kind == 'plain'].any()
+    assert exact['back'][kind == 'backtrack'].all() and not exact['back'][kind == 'plain'].any()
+    if N > 1:          # floor and backtrack in one row
+        assert (exact['floor'].any(axis=1) & exact['back']).any()
+    fm = kind == 'free_min'
+    assert fm.sum() >= 12 and exact['free_min'][fm].all() and not exact['free_min'][~fm].any() and not exact['back'][kind == 'free_min, shrinking'].any()
+    free = 1.0 - (rows['vol'] * rows['c']).sum(axis=1)
+    assert (0.1 * free[fm] < U.FREE_MIN).all() and (free[fm] > 4 * U.FREE_MIN).all()
+    assert exact['damped'].sum() >= 10 and (~exact['damped'] & (rows['dphi_max'] > 0)).sum() >= 4 and (np.abs(rows['dphi'])[rows['dphi_max'] <= 0] > 0.05).any()
+    assert (rows['lam'] < 1.0).sum() >= 20 and (rows['lam'] == 1.0).sum() >= 20
+    for bad in (np.isnan, np.isposinf, np.isneginf):
+        assert bad(rows['du']).any() and bad(rows['dphi']).any()
+    assert np.isinf(fp['upd'][np.isnan(rows['du']).any(axis=1)]).all() and np.isinf(fp['mphi'][np.isnan(rows['dphi'])]).all()
+
+
+def FREE_MIN_IS_THE_ORACLES():
+    return U.FREE_MIN == PH.FREE_MIN
+
+
+def test_newton_rule_twin_passes_its_own_helper_and_every_mutant_fails(rule):
+    rows, fp, exact = rule
+    worst = U.check_newton_rule(fp, fp, exact, TWIN_BARS, rows['kind'])
+    print('N = %d: fp64 twin against exact arithmetic, worst ulp: %s' % (rows['c'].shape[1], {k: round(v, 3) for k, v in worst.items()}))
+    for mutant in U.RULE_MUTANTS:
+        assert fails(U.check_newton_rule, U.newton_rule_twin(rows, mutant=mutant), fp, exact, TWIN_BARS), mutant
+    # theta = 1 applied where the backtrack is not taken changes no decision and, in exact arithmetic, no value: the helper cannot see it
+    # (the kernels' bits can: profiles/newton_rule.md); a theta that is 1e-12 off is seen
+    off = dict(fp, theta=fp['theta'] * (1.0 + 1e-12))
+    assert fails(U.check_newton_rule, off, fp, exact, TWIN_BARS)
+
+
+def test_newton_rule_decisions_do_not_sit_at_a_tie(rule):
+    """a relative perturbation of 1e-12 of every input (fused against unfused multiply-add moves far less) flips no decision"""
+    rows, fp, _ = rule
+    for seed in range(4):
+        moved = U.newton_rule_twin(U.perturbed(rows, 1e-12, seed))
+        for k in U.RULE_DECISIONS + ('free_min',):
+            assert np.array_equal(moved[k], fp[k]), k
+
+
+def test_newton_accept_tuples_hold_what_the_design_asks_for():
+    t, what = U.newton_accept_tuples()
+    acc, prev, fired = U.newton_accept_twin(t)
+    alone = {'tol': (True, False, False), 'estimate': (False, True, False), 'rounding floor': (False, False, True)}
+    for name, pattern in alone.items():
+        rows = [k for k, w in enumerate(what) if w.startswith(name) and 'alone' in w]
+        assert rows and all(tuple(fired[k]) == pattern and acc[k] for k in rows), name
+    damped = t[:, 0] < 1.0
+    assert damped.sum() >= 3 and not acc[damped].any() and np.isinf(prev[damped]).all() and np.array_equal(prev[~damped], t[~damped, 1])
+    first = np.array(['first iteration' in w for w in what])
+    assert (first & (t[:, 4] != 0) & np.isinf(t[:, 2])).any() and not acc[first & (t[:, 1] > U.RULE_TOL)].any()
+    lin = np.array([w.startswith('linear sequence') for w in what])
+    assert lin.sum() >= 40 and not fired[lin][:, 2].any()                      # never through the rounding-floor rule
+    assert np.array_equal(acc[lin & (t[:, 4] == 0)], (t[:, 1] < U.RULE_TOL)[lin & (t[:, 4] == 0)])
+    assert (lin & (t[:, 1] < 100 * U.RULE_TOL) & (t[:, 2] < 100 * U.RULE_TOL) & ~acc).sum() >= 10      # ... while inside its window
+
+
+def test_newton_accept_twin_is_the_oracle_s_rule_and_every_mutant_fails():
+    t, what = U.newton_accept_tuples()
+    acc, prev, fired = U.newton_accept_twin(t)
+    for k, (lam, upd, up, tol, est) in enumerate(t):
+        if lam == 1.0:
+            assert fired[k][2] == PH.at_rounding_floor(upd, up, tol), what[k]
+    U.check_newton_accept(acc, prev, t, what)
+    for mutant in U.ACCEPT_MUTANTS:
+        a, p, _ = U.newton_accept_twin(t, mutant=mutant)
+        assert fails(U.check_newton_accept, a, p, t), mutant
+    for seed in range(4):          # no tie: 1e-12 on every number of every tuple flips no decision
+        rng = np.random.default_rng(seed)
+        moved = t.copy()
+        moved[:, 1:4] *= 1.0 + 1e-12 * rng.choice([-1.0, 1.0], (t.shape[0], 3))
+        assert np.array_equal(U.newton_accept_twin(moved)[0], acc) and np.array_equal(U.newton_accept_twin(moved)[2], fired)
