@@ -576,6 +576,10 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
         const __amdgpu_buffer_rsrc_t rs = row_rsrc(grow, ldx);
 #pragma unroll
         for (int it = 0; it < IT2; ++it) {
+          // Fast body: a wave whose whole 1-KiB chunk of this iteration lies beyond the pitch skips it (wave-uniform): everything
+          // below would be don't-care reads, dropped stores and sums that nobody uses (headline shape: the second iteration
+          // holds 128 doubles, all of them wave 0's).  The first iteration is left alone: one branch less on every wave's path.
+          if (FAST && W > 1 && it > 0 && 128 * (W * it + wave) >= ldx) continue;
           // threads past the staged row (W > 1: the workgroup spans more than one row buffer) read a
           // clamped, don't-care slot; their global store is dropped by the range check
           const int sl = min(pair_slot<P>(ls2, W * it), RB - 4);
@@ -614,6 +618,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
       const __amdgpu_buffer_rsrc_t rs = row_rsrc(lout, ldx);
 #pragma unroll
       for (int it = 0; it < IT2; ++it) {
+        if (FAST && W > 1 && it > 0 && 128 * (W * it + wave) >= ldx) continue;   // (as in the epilogue: nothing of this chunk is in the row)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, accp[it]), rs, tid * 16 + it * (1024 * W), 0, 0);
         // LV stays zero beyond the row (the Poisson scans run unmasked): only in-row pairs are written
         if (keep && 2 * tid + 128 * W * it < ldx) {

@@ -230,11 +230,12 @@ __device__ __forceinline__ void blocked_scan_sum(double (&x)[P], double w, doubl
 // equality of the DPP1 and LDS paths and the forward error against multiprecision solutions for all 30 <P, G, DPP1> instances, up to
 // the Crank-Nicolson limit |a| + |c| -> 1 (D dt/dx^2 = 1e4); worst cases in profiles/primitives_unit.md.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double from_prev_lane(double old_lane0, double x);
-__device__ __forceinline__ double from_next_lane(double old_lane63, double x);
+__device__ __forceinline__ double from_prev_lane_or_zero(double x);
+__device__ __forceinline__ double from_next_lane_or_zero(double x);
 
 // DPP1: the three exchanges with the neighbouring lane (the interface close, the first reduction level and the final yL) go through
-// DPP wave shifts, whose `old` operand 0.0 stands in for the zero guards, instead of through the LDS strip: the same values.
+// DPP wave shifts on bound_ctrl, whose 0.0 in the lane without a source stands in for the zero guards, instead of through the LDS
+// strip: the same values (and no `old` operand to seed with zero: 20 moves fewer per solve at G = 1).
 template <int P, int G, bool DPP1 = false>
 __device__ __forceinline__ void tridiag_wave(double (&a)[G][P], double (&c)[G][P], double (&d)[G][P], double* X,
                                              int XSTRIDE, int lane) {
@@ -289,9 +290,9 @@ __device__ __forceinline__ void tridiag_wave(double (&a)[G][P], double (&c)[G][P
     if constexpr (DPP1) {
 #pragma unroll
       for (int g = 0; g < G; ++g) {
-        Vn0[g] = from_next_lane(0.0, a[g][0]);
-        Wn0[g] = from_next_lane(0.0, c[g][0]);
-        dn0[g] = from_next_lane(0.0, d[g][0]);
+        Vn0[g] = from_next_lane_or_zero(a[g][0]);
+        Wn0[g] = from_next_lane_or_zero(c[g][0]);
+        dn0[g] = from_next_lane_or_zero(d[g][0]);
       }
     } else {
 #pragma unroll
@@ -329,12 +330,12 @@ __device__ __forceinline__ void tridiag_wave(double (&a)[G][P], double (&c)[G][P
     if (DPP1 && s == 1) {
 #pragma unroll
       for (int g = 0; g < G; ++g) {
-        aL[g] = from_prev_lane(0.0, ra[g]);
-        aR[g] = from_next_lane(0.0, ra[g]);
-        cL[g] = from_prev_lane(0.0, rc[g]);
-        cR[g] = from_next_lane(0.0, rc[g]);
-        dL[g] = from_prev_lane(0.0, rd[g]);
-        dR[g] = from_next_lane(0.0, rd[g]);
+        aL[g] = from_prev_lane_or_zero(ra[g]);
+        aR[g] = from_next_lane_or_zero(ra[g]);
+        cL[g] = from_prev_lane_or_zero(rc[g]);
+        cR[g] = from_next_lane_or_zero(rc[g]);
+        dL[g] = from_prev_lane_or_zero(rd[g]);
+        dR[g] = from_next_lane_or_zero(rd[g]);
       }
     } else {
 #pragma unroll
@@ -373,7 +374,7 @@ __device__ __forceinline__ void tridiag_wave(double (&a)[G][P], double (&c)[G][P
     double yL[G];
     if constexpr (DPP1) {
 #pragma unroll
-      for (int g = 0; g < G; ++g) yL[g] = from_prev_lane(0.0, rd[g]);
+      for (int g = 0; g < G; ++g) yL[g] = from_prev_lane_or_zero(rd[g]);
     } else {
 #pragma unroll
       for (int g = 0; g < G; ++g) XA[g * XSTRIDE] = rd[g];
@@ -435,6 +436,11 @@ __device__ __forceinline__ double wave_scan_incl_bc(double v) {
   v += dpp_f64<0x143, 0xc>(0.0, v);   // row_bcast:31 into rows 2,3
   return v;
 }
+
+// the wave shifts with 0.0 in lane 0 / lane 63: from_prev_lane(0.0, x) / from_next_lane(0.0, x) without the seeded `old` operand.
+// Functions of their own so that every other user of the shifts compiles to what it did.
+__device__ __forceinline__ double from_prev_lane_or_zero(double x) { return dpp_f64_or_zero<0x138>(x); }   // wave_shr:1
+__device__ __forceinline__ double from_next_lane_or_zero(double x) { return dpp_f64_or_zero<0x130>(x); }   // wave_shl:1
 
 __device__ __forceinline__ double read_lane(double v, int l) {   // l wave-uniform
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
