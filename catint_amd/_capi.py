@@ -258,6 +258,7 @@ class PnpSolver(object):
         self._responder = None
         self._kinetics = None
         self._coupler = None
+        self._sensitizer = None
 
     def _check(self, rc):
         if rc != 0:
@@ -285,6 +286,9 @@ class PnpSolver(object):
         if getattr(self, '_coupler', None) is not None:
             self._coupler.close()
             self._coupler = None
+        if getattr(self, '_sensitizer', None) is not None:
+            self._sensitizer.close()
+            self._sensitizer = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -815,6 +819,124 @@ class PnpSolver(object):
                                    dphi_max=dphi_max, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
                                    stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], fields=fields,
                                    max_waves=max_waves)
+
+    def get_sensitivities(self, parameters, lanes=None, fields=None, flux=None, max_waves=0):
+        """The sensitivities of the stationary state this handle holds to its model parameters (include/catint_sens.h), solved on the
+        device: for every lane of `lanes` (None: all, in order; repeats allowed) and every entry of `parameters` the exact derivative
+        of the surface state, the charge on the metal and the wall fluxes.  An entry is 'phiM' (per volt), ('flux', k) (the prescribed
+        wall flux of species k), ('c_bulk', k), ('c_bulk', weights [N]) (a direction in bulk composition, e.g. an electroneutral salt:
+        the weighted sum of the single-species columns, formed on the host), ('D', k), ('kf', r), ('kr', r) (reaction r of
+        set_reactions), ('wall_k', r) (the lane's own rate constant of wall reaction r), 'stern_capacitance' or 'velocity'.  Returns a
+        dict of the rows named in `fields` (catint_amd._sens.FIELDS; None: all): 'dphi_surface' [n][P], 'dc_surface' [n][P][N], 'dsigma'
+        [n][P], 'dwall_flux' [n][P][N], 'dcurrent' [n][P] = sum_k q_k dwall_flux_k; 'status' [n] (0; 1: failed pivot check or non-finite
+        number; 2: the lane's solver status was not 0 or an input is not finite, outputs NaN); 'parameters' (the list as given); and
+        'elasticity': {'dcurrent' [n][P], 'dwall_flux' [n][P][N]} = d ln|y| / d ln p (what 'dcurrent' and 'dwall_flux' were asked
+        for), NaN where y or p is 0; for a direction p is the multiplier of the weights, 1.  Medium, tables, potentials and fluxes are
+        the ones this solver was given, with the rules of get_response / get_balance: after scf_cycle pass flux= (ValueError otherwise)
+        and the wall table is left out; after a set_batch with another batch size the wall table must be set again (ValueError)."""
+        from . import _sens
+        o = self._obs
+        wall = None if o['explicit_kinetics'] else o['wall']
+        if wall is not None and o['wall_stale']:
+            raise ValueError('get_sensitivities: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall '
+                             'table whose rate constants were not recorded for this batch: call set_wall_kinetics again')
+        if flux is None:
+            if o['flux_stale']:
+                raise ValueError('get_sensitivities: scf_cycle updated the wall fluxes on the device; pass flux= (state["flux"] of the loop)')
+            flux = o['flux']
+        if flux is None or o['phiM'] is None:
+            raise ValueError('get_sensitivities: no batch was set')
+        g = np.asarray(_f64(flux, (self.B, self.N)))
+        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+            raise ValueError('get_sensitivities: lane index outside [0, %d)' % self.B)
+        n, N = len(idx), self.N
+        names = list(_sens.FIELDS) if fields is None else list(fields)
+        # the columns the device solves: one per distinct (kind, index); a direction takes the single-species columns it weighs
+        specs, cols, plan = list(parameters), {}, []
+        if not specs:
+            raise ValueError('get_sensitivities: no parameters')
+
+        def column(name, i=0):
+            return cols.setdefault((name, int(i)), len(cols))
+        for spec in specs:
+            if isinstance(spec, str):
+                if spec not in _sens.KINDS or spec in _sens.INDEXED:
+                    raise ValueError('get_sensitivities: unknown parameter %r' % (spec,))
+                plan.append([(column(spec), 1.0)])
+            elif spec[0] == 'c_bulk' and np.ndim(spec[1]) > 0:
+                wts = np.asarray(spec[1], float).reshape(-1)
+                if len(wts) != N:
+                    raise ValueError("get_sensitivities: ('c_bulk', weights) needs %d weights" % N)
+                plan.append([(column('c_bulk', k), float(wts[k])) for k in range(N) if wts[k] != 0.0])
+            else:
+                if spec[0] not in _sens.INDEXED:
+                    raise ValueError('get_sensitivities: unknown parameter %r' % (spec,))
+                plan.append([(column(spec[0], spec[1]), 1.0)])
+        if len(cols) > _sens.MAX_PARAMS:
+            raise ValueError('get_sensitivities: %d columns, at most %d in one call' % (len(cols), _sens.MAX_PARAMS))
+        if getattr(self, '_sensitizer', None) is None:
+            self._sensitizer = _sens.Sensitizer(o['device'])
+        dev = [k if k[0] in _sens.INDEXED else k[0] for k in sorted(cols, key=cols.get)]
+        raw = self._sensitizer.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], g[idx], dev,
+                                     lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'], stern_capacitance=o['stern_capacitance'],
+                                     phi_pzc=o['phi_pzc'], velocity=o['velocity'], reactions=o['reactions'], wall=wall, fields=names,
+                                     max_waves=max_waves)
+        out = {'status': raw['status'], 'parameters': specs}
+        for name in names:
+            a = raw[name]
+            res = np.empty((n, len(specs)) + a.shape[2:])
+            for m, terms in enumerate(plan):
+                if len(terms) == 1 and terms[0][1] == 1.0:
+                    res[:, m] = a[:, terms[0][0]]
+                else:
+                    acc = np.zeros((n,) + a.shape[2:])
+                    for col, wt in terms:
+                        acc = acc + wt * a[:, col]
+                    res[:, m] = acc
+            out[name] = res
+        # elasticities d ln|y| / d ln p of the current and the wall fluxes
+        el = {}
+        if 'dcurrent' in out or 'dwall_flux' in out:
+            q = np.asarray(o['charges'], float)
+            wf = g[idx].copy()                                  # the flux into the domain: prescribed + wall table
+            if wall is not None:
+                cs, vs, _ = self.get_surface()
+                al = np.zeros(len(wall['species'])) if wall['alpha'] is None else wall['alpha']
+                ks = np.zeros(len(wall['species'])) if wall['saturation'] is None else wall['saturation']
+                for r, s in enumerate(wall['species']):
+                    c_s = cs[idx, s] if s >= 0 else np.ones(n)
+                    gr = c_s / (1.0 + ks[r] * c_s) * np.exp(al[r] * (o['phiM'][idx] - vs[idx]))
+                    wf = wf + wall['nu'][r][None, :] * (wall['k'][idx, r] * gr)[:, None]
+            pv = np.empty((n, len(specs)))
+            for m, spec in enumerate(specs):
+                name, i = (spec, 0) if isinstance(spec, str) else (spec[0], spec[1])
+                if name == 'phiM':
+                    pv[:, m] = o['phiM'][idx]
+                elif name == 'flux':
+                    pv[:, m] = g[idx, int(i)]
+                elif name == 'c_bulk':
+                    pv[:, m] = 1.0 if np.ndim(i) > 0 else (np.nan if o['c_bulk'] is None else o['c_bulk'][idx, int(i)])
+                elif name == 'D':
+                    pv[:, m] = o['D'][int(i)]
+                elif name in ('kf', 'kr'):
+                    pv[:, m] = o['reactions'][int(i)][2 if name == 'kf' else 3]
+                elif name == 'wall_k':
+                    pv[:, m] = wall['k'][idx, int(i)]
+                elif name == 'stern_capacitance':
+                    pv[:, m] = o['stern_capacitance']
+                else:
+                    pv[:, m] = o['velocity']
+            with np.errstate(divide='ignore', invalid='ignore'):
+                if 'dcurrent' in out:
+                    y = (wf * q[None, :]).sum(axis=1)[:, None]
+                    el['dcurrent'] = np.where((y == 0) | (pv == 0), np.nan, out['dcurrent'] * pv / np.where(y == 0, 1.0, y))
+                if 'dwall_flux' in out:
+                    y = wf[:, None, :]
+                    el['dwall_flux'] = np.where((y == 0) | (pv[:, :, None] == 0), np.nan,
+                                                out['dwall_flux'] * pv[:, :, None] / np.where(y == 0, 1.0, y))
+        out['elasticity'] = el
+        return out
 
     def get_status(self):
         st = np.zeros(self.B, np.int32)

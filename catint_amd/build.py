@@ -69,6 +69,14 @@ COUPLE_LIB = os.path.join(LIB_DIR, 'libcatint_couple.so')
 COUPLE_SOURCES = ['catcpl.hip']
 COUPLE_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_couple.h')]
 
+# ninth library (include/catint_sens.h): the sensitivities of a stationary state to its model parameters (bulk concentrations, diffusion
+# coefficients, rate constants, Stern capacitance, velocity) -- right-hand sides at every grid row carried through the team's block
+# elimination.  A library of its own as the seven before it
+SENS_DIR = os.path.join(CSRC, 'sens')
+SENS_LIB = os.path.join(LIB_DIR, 'libcatint_sens.so')
+SENS_SOURCES = ['catsens.hip']
+SENS_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_sens.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -208,6 +216,15 @@ def couple_needs_build():
 def build_couple_library(force=False, verbose=False):
     """catint_amd/csrc/couple into catint_amd/lib/libcatint_couple.so"""
     return _build_unit(COUPLE_DIR, COUPLE_SOURCES, COUPLE_HEADERS, COUPLE_LIB, force, verbose)
+
+
+def sens_needs_build():
+    return _unit_needs_build(SENS_DIR, SENS_SOURCES, SENS_HEADERS, SENS_LIB)
+
+
+def build_sens_library(force=False, verbose=False):
+    """catint_amd/csrc/sens into catint_amd/lib/libcatint_sens.so"""
+    return _build_unit(SENS_DIR, SENS_SOURCES, SENS_HEADERS, SENS_LIB, force, verbose)
 
 
 def unittest_needs_build():

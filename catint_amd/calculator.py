@@ -95,6 +95,12 @@ class Calculator(object):
         self.response = None              # the dict of get_response of the last such run()
         if self._response_option() is not None and not self.physical:
             raise CalculatorError("tp.newton['response'] is part of the physical mode (calc=\"comsol\")")
+        # physical mode, opt-in: tp.newton['sensitivities'] = [parameter specs] -- after the sweep's solve, run() takes the sensitivities of
+        # every lane to these model parameters on the device (PnpSolver.get_sensitivities, include/catint_sens.h) and adds them to
+        # tp.alldata[i]['system']['sensitivities'].  Off by default: nothing else changes.
+        self.sensitivities = None         # the dict of get_sensitivities of the last such run()
+        if self._sensitivity_option() is not None and not self.physical:
+            raise CalculatorError("tp.newton['sensitivities'] is part of the physical mode (calc=\"comsol\")")
         # roughness factor: every wall flux the COMSOL model prescribes is j_i = RF*flux_factor*flux_i (comsol_model.py:1000, :1134)
         self.RF = float(self.tp.system.get('RF', 1.0)) if self.physical else 1.0
         # the reference hands system['flow rate'] (a number or a COMSOL expression) to the convection velocity tds.cdm1 "u"
@@ -685,6 +691,8 @@ class Calculator(object):
         tp = self.tp
         if self._response_option() is not None and not self.physical:      # (tp.newton may have been set after the constructor's check)
             raise CalculatorError("tp.newton['response'] is part of the physical mode (calc=\"comsol\")")
+        if self._sensitivity_option() is not None and not self.physical:
+            raise CalculatorError("tp.newton['sensitivities'] is part of the physical mode (calc=\"comsol\")")
         keys = list(tp.descriptors.keys())
         lanes = tp.alldata_names
         B = len(lanes)
@@ -725,6 +733,8 @@ class Calculator(object):
                         warnings.warn("tp.newton['response']: a surface reaction's rate is a function of phiM without 'alpha'; the response "
                                       "holds the rate constant fixed, so dK/dphiM is missing from admittance and impedance", RuntimeWarning)
                     self.response = s.get_response(omega=self._response_option())
+                if self._sensitivity_option() is not None:
+                    self.sensitivities = s.get_sensitivities(self._sensitivity_option())
             cout = cfin.reshape(1, B, tp.nspecies * tp.nx)
             if derived is not None:
                 self.status = status
@@ -732,6 +742,7 @@ class Calculator(object):
                 self._alldata_fill(0, self._alldata_from_device(cfin, v, derived, flux, getattr(self, 'kinetic_flux', None)), status)
                 self._alldata_balance()
                 self._alldata_response()
+                self._alldata_sensitivities()
                 return cout
         else:
             cout, status, (v, g, l) = self.integrate_pnp_batch(c0, pb, vz, flux)
@@ -741,6 +752,7 @@ class Calculator(object):
         if self.physical:
             self._alldata_balance()
             self._alldata_response()
+            self._alldata_sensitivities()
         return cout
 
     def _response_option(self):
@@ -770,6 +782,44 @@ class Calculator(object):
             d['response_omega'] = res['omega'].copy()
             d['admittance'] = res['admittance'][b].copy()
             d['impedance'] = res['impedance'][b].copy()
+
+    def _sensitivity_option(self):
+        """tp.newton['sensitivities']: None when the option is off, otherwise the parameter list in the solver's terms (a species named
+        by its tp.species key becomes its index)"""
+        opt = (getattr(self.tp, 'newton', None) or {}).get('sensitivities')
+        if not opt:
+            return None
+        names = list(self.tp.species.keys())
+        specs = []
+        for spec in opt:
+            if not isinstance(spec, str) and isinstance(spec[1], str):
+                if spec[0] not in ('flux', 'c_bulk', 'D') or spec[1] not in names:
+                    raise CalculatorError("tp.newton['sensitivities']: %r names no species of tp.species" % (spec,))
+                spec = (spec[0], names.index(spec[1]))
+            specs.append(spec if isinstance(spec, str) else tuple(spec))
+        return specs
+
+    def _alldata_sensitivities(self):
+        """tp.newton['sensitivities']: self.sensitivities into tp.alldata[i]['system']['sensitivities'] -- 'parameters' (the list as the
+        user gave it), 'dcurrent_density' [P] (A m^-2 per unit of the parameter), 'dsurface_concentration' [P][N], 'dsurface_potential'
+        [P], 'dsurface_charge' [P] and 'elasticity' {'dcurrent' [P], 'dwall_flux' [P][N]}.  In the convention of _alldata_balance:
+        currents per geometric area, derivatives with respect to the user's value of the parameter.  The solver was handed RF * flux and
+        RF * k, so the columns of a flux and of a wall rate constant are chained with RF, and the current is divided by RF.  Like the
+        keys of _alldata_balance these are an extension: the reference's field contract has no counterpart for them."""
+        opt = (getattr(self.tp, 'newton', None) or {}).get('sensitivities')
+        if not opt or self.sensitivities is None:
+            return
+        res = self.sensitivities
+        rf = self.RF if self.RF not in (0.0, 1.0) else 1.0
+        chain = np.array([rf if (not isinstance(s, str) and s[0] in ('flux', 'wall_k')) else 1.0 for s in res['parameters']])
+        for b in range(len(res['status'])):
+            self.tp.alldata[b]['system']['sensitivities'] = {
+                'parameters': list(opt),
+                'dcurrent_density': res['dcurrent'][b] * chain / rf,
+                'dsurface_concentration': res['dc_surface'][b] * chain[:, None],
+                'dsurface_potential': res['dphi_surface'][b] * chain,
+                'dsurface_charge': res['dsigma'][b] * chain,
+                'elasticity': {k: v[b].copy() for k, v in res['elasticity'].items()}}
 
     def _alldata_balance(self):
         """balance_on_device: the per-species picture of self.balance into tp.alldata -- per species 'flux' [nx-1], 'reaction_source' [nx],
