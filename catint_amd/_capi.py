@@ -259,6 +259,7 @@ class PnpSolver(object):
         self._kinetics = None
         self._coupler = None
         self._sensitizer = None
+        self._rate_control = None
 
     def _check(self, rc):
         if rc != 0:
@@ -289,6 +290,9 @@ class PnpSolver(object):
         if getattr(self, '_sensitizer', None) is not None:
             self._sensitizer.close()
             self._sensitizer = None
+        if getattr(self, '_rate_control', None) is not None:
+            self._rate_control.close()
+            self._rate_control = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -780,6 +784,63 @@ class PnpSolver(object):
                                     phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma,
                                     theta_guess=theta_guess, tol=_kinetics.DEFAULT_TOL if tol is None else tol,
                                     maxit=_kinetics.DEFAULT_MAXIT if maxit is None else maxit, fields=fields, max_waves=max_waves)
+
+    def get_rate_control(self, model_or_tables, theta=None, phiM=None, lanes=None, csurf=None, phi_surface=None, fields=None,
+                         potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None,
+                         residual_tol=1e-8, max_waves=0, kin=None, coupling=None, rf=1.0):
+        """The degree of rate control of the microkinetic steady state (include/catint_drc.h), computed on the device, one operating
+        point per entry of `lanes`: which transition state and which intermediate control each wall flux.  The arguments and their
+        defaults are those of get_kinetics.  theta [n][S+1]: the steady-state coverages at the same arguments (None: get_kinetics is
+        called first and its coverages are used).  fields: names out of catint_amd._drc.FIELDS (None: 'drc' [n][R][N] Campbell's degree
+        of rate control of step r's transition state for the flux of species k, 'tdrc' [n][S][N] the thermodynamic one of adsorbate
+        s + 1, the raw derivatives 'dflux_drc', 'dflux_dG', and 'flux', 'flux_scale'; also 'dflux_dlnkf', 'dflux_dlnkb' [n][R][N],
+        'dy_drc' [n][R][S+1]).  Returns a dict of these and 'status' [n] (0; 1: the residual of the state is above residual_tol; 2:
+        unsolved lane or non-finite input, NaN; 3: bad pivot), 'residual' [n].  These are INTRINSIC derivatives, at a fixed surface
+        state.  With kin (get_kinetics(..., fields=('dflux_dc', 'dflux_dphi')) and coupling (get_coupling's 'T_c', 'T_phi') for the
+        same lanes the result also carries the APPARENT ones of the coupled electrode, where the surface state answers the flux
+        through mass transport: 'dflux_drc_apparent', 'dflux_dG_apparent' = M^-1 (rf dflux), M = I - rf (K_c T_c + K_phi (x) T_phi)
+        formed per point on the host, and 'drc_apparent', 'tdrc_apparent' normalised by rf flux (NaN rows where M is singular)."""
+        from . import _drc
+        o = self._obs
+        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
+        if site_density is not None:
+            tables['site_density'] = float(site_density)
+        if (kin is None) != (coupling is None):
+            raise ValueError('get_rate_control: kin and coupling come together')
+        host = csurf is not None or phi_surface is not None
+        if lanes is not None:
+            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        elif host and phiM is not None:
+            idx = None
+        else:
+            idx = np.arange(self.B, dtype=np.int64)
+        if phiM is None:
+            if o['phiM'] is None:
+                raise ValueError('get_rate_control: no batch was set')
+            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+                raise ValueError('get_rate_control: lane index outside [0, %d)' % self.B)
+            phiM = np.asarray(o['phiM'], float)[idx]
+        common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
+                      phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma)
+        if theta is None:
+            theta = self.get_kinetics(tables, phiM=phiM, lanes=lanes, csurf=csurf, phi_surface=phi_surface, fields=('theta',), max_waves=max_waves,
+                                      **common)['theta']
+        names = list(_drc.DEFAULT_FIELDS) if fields is None else list(fields)
+        ask = list(names)
+        if kin is not None:
+            ask += [k for k in ('dflux_drc', 'dflux_dG', 'flux') if k not in ask]
+        if getattr(self, '_rate_control', None) is None:
+            self._rate_control = _drc.RateControl(o['device'])
+        res = self._rate_control.solve(None if host else self.device_view(), tables, phiM, theta, lanes=None if host else idx, csurf=csurf,
+                                       phi_surface=phi_surface, residual_tol=residual_tol, fields=ask, max_waves=max_waves, **common)
+        if kin is not None:
+            for raw, norm in (('dflux_drc', 'drc'), ('dflux_dG', 'tdrc')):
+                res[raw + '_apparent'] = _drc.apparent(res[raw], kin, coupling, rf=rf)
+                res[norm + '_apparent'] = _drc.normalised(res[raw + '_apparent'], rf * res['flux'], tables['nu'])
+        for k in ask:
+            if k not in names:
+                del res[k]
+        return res
 
     def get_coupling(self, flux, kin, rf=1.0, lanes=None, dphi_max=0.05, fields=None, max_waves=0):
         """One Newton step of the self-consistency between kinetics and transport (include/catint_couple.h), formed on the device

@@ -77,6 +77,14 @@ SENS_LIB = os.path.join(LIB_DIR, 'libcatint_sens.so')
 SENS_SOURCES = ['catsens.hip']
 SENS_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_sens.h')]
 
+# tenth library (include/catint_drc.h): the degree of rate control of a microkinetic steady state -- the derivatives of the wall fluxes
+# with respect to every rate constant, transition state and adsorbate energy from one factorisation per operating point.  A library of
+# its own as the eight before it
+DRC_DIR = os.path.join(CSRC, 'drc')
+DRC_LIB = os.path.join(LIB_DIR, 'libcatint_drc.so')
+DRC_SOURCES = ['catdrc.hip']
+DRC_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_drc.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -225,6 +233,15 @@ def sens_needs_build():
 def build_sens_library(force=False, verbose=False):
     """catint_amd/csrc/sens into catint_amd/lib/libcatint_sens.so"""
     return _build_unit(SENS_DIR, SENS_SOURCES, SENS_HEADERS, SENS_LIB, force, verbose)
+
+
+def drc_needs_build():
+    return _unit_needs_build(DRC_DIR, DRC_SOURCES, DRC_HEADERS, DRC_LIB)
+
+
+def build_drc_library(force=False, verbose=False):
+    """catint_amd/csrc/drc into catint_amd/lib/libcatint_drc.so"""
+    return _build_unit(DRC_DIR, DRC_SOURCES, DRC_HEADERS, DRC_LIB, force, verbose)
 
 
 def unittest_needs_build():

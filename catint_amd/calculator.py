@@ -323,7 +323,7 @@ class Calculator(object):
             raise CalculatorError('set_surface_kinetics and set_microkinetics exclude each other: one kinetic model per calculator')
         self.surface_kinetics = list(reactions)
 
-    def set_microkinetics(self, model, site_density=None, potential_drop='stern', gamma=None, scf='mixing'):
+    def set_microkinetics(self, model, site_density=None, potential_drop='stern', gamma=None, scf='mixing', rate_control=False):
         """Mean-field surface microkinetics as the kinetic half of run_scf_cycle (physical mode only): model is a
         catint_amd.microkinetics.MeanFieldModel over this transport's species (or the dict of its tables()).  With it set,
         run_scf_cycle() without a callback runs its host loop with the device kinetics (include/catint_kinetics.h) as the callback: the
@@ -335,7 +335,12 @@ class Calculator(object):
         'coverage', 'flux_scale' and 'kinetic_status'.  model=None removes it.
         scf='newton' (default 'mixing': the loop above, unchanged): run_scf_cycle() runs a Newton iteration on the wall fluxes instead
         of the mixing loop -- see _run_newton_scf.  It needs the derivatives of both halves, so it excludes a host flux_callback, a
-        transport_fn and set_surface_kinetics."""
+        transport_fn and set_surface_kinetics.
+        rate_control=True (default False: no key is added and no call is made): after run_scf_cycle() one call of the degree of rate
+        control (include/catint_drc.h) at the final surface state of every lane; result['rate_control'] and
+        tp.alldata[i]['system']['rate_control'] hold 'drc' [R][N], 'tdrc' [S][N], 'status', 'residual' -- the intrinsic coefficients, at
+        a fixed surface state -- and under scf='newton' also 'drc_apparent', 'tdrc_apparent', those of the coupled electrode
+        (PnpSolver.get_rate_control)."""
         if model is None:
             self.microkinetics = None
             return
@@ -358,6 +363,43 @@ class Calculator(object):
         self.microkinetics = {'tables': tables, 'potential_drop': potential_drop, 'gamma': None if gamma is None else np.asarray(gamma, float)}
         if scf == 'newton':
             self.microkinetics['scf'] = 'newton'
+        if rate_control:
+            self.microkinetics['rate_control'] = True
+
+    def _rate_control_solver(self):
+        """The device context of the rate-control analysis (tests replace it)"""
+        from . import _drc
+        return _drc.RateControl(self.device)
+
+    def _final_rate_control(self, kin_solver, phiM, view=None, csurf=None, phi_surface=None, theta_guess=None, coupling_of=None, rf=1.0):
+        """set_microkinetics(rate_control=True): the kinetics once more at the final surface state (the view's, or csurf and
+        phi_surface), warm-started, and the degree of rate control at its coverages.  coupling_of(kin) -> the dict of get_coupling
+        for all lanes (scf='newton'): adds the apparent coefficients.  Returns the dict stored as result['rate_control']."""
+        from . import _drc
+        tp, micro = self.tp, self.microkinetics
+        tables = micro['tables']
+        B = len(phiM)
+        common = dict(potential_drop=micro['potential_drop'], stern_capacitance=float(tp.system.get('Stern capacitance', 0.0)) * 1e-2,
+                      phi_pzc=float(tp.system.get('phiPZC', 0.0)), gamma=micro['gamma'])
+        where = dict(lanes=np.arange(B, dtype=np.int64)) if view is not None else dict(csurf=csurf, phi_surface=phi_surface)
+        if theta_guess is not None:
+            ok = np.isfinite(theta_guess).all(axis=1)
+            theta_guess = np.where(ok[:, None], theta_guess, 1.0 / float(np.sum(tables['site_count']))) if ok.any() else None
+        want = ('theta', 'flux', 'flux_scale') + (('dflux_dc', 'dflux_dphi') if coupling_of is not None else ())
+        kin = kin_solver.solve(view, tables, phiM, theta_guess=theta_guess, fields=want, **where, **common)
+        rc = self._rate_control_solver()
+        try:
+            raw = rc.solve(view, tables, phiM, kin['theta'], fields=('drc', 'tdrc', 'dflux_drc', 'dflux_dG', 'flux'), **where, **common)
+        finally:
+            rc.close()
+        out = {k: np.asarray(raw[k]) for k in ('drc', 'tdrc', 'status', 'residual')}
+        out['kinetic_status'] = np.asarray(kin['status']).copy()
+        if coupling_of is not None:
+            cp = coupling_of(kin)
+            for name, norm in (('dflux_drc', 'drc'), ('dflux_dG', 'tdrc')):
+                out[norm + '_apparent'] = _drc.normalised(_drc.apparent(raw[name], kin, cp, rf=rf), rf * np.asarray(raw['flux']), tables['nu'])
+            out['coupling_status'] = np.asarray(cp['status']).copy()
+        return out
 
     def _kinetics_solver(self):
         """The device context of the microkinetic solves (tests replace it)"""
@@ -1220,6 +1262,9 @@ class Calculator(object):
                     active = st['active'] != 0
                     failed = st['failed'] != 0
                     break
+            rate_control = None
+            if kin_solver is not None and micro.get('rate_control'):
+                rate_control = self._final_rate_control(kin_solver, phiM, csurf=sc, phi_surface=vsurf, theta_guess=coverage.get('theta'))
         finally:
             if device_loop:
                 self.surface_kinetics = kinetics
@@ -1233,6 +1278,8 @@ class Calculator(object):
             if kin_solver is not None and 'theta' in coverage:
                 d['system']['coverage'] = coverage['theta'][i].copy()
                 d['system']['kinetic_status'] = int(coverage['status'][i])
+            if rate_control is not None:
+                d['system']['rate_control'] = {k: np.array(v[i]) for k, v in rate_control.items()}
             for k, sp in enumerate(names):
                 d['species'].setdefault(sp, {})
                 d['species'][sp]['surface_concentration'] = float(sc[i, k])
@@ -1250,6 +1297,8 @@ class Calculator(object):
             result['coverage'] = coverage['theta']
             result['flux_scale'] = coverage['flux_scale']
             result['kinetic_status'] = coverage['status']          # of each lane's last active iteration; non-zero: the lane is 'failed'
+        if rate_control is not None:
+            result['rate_control'] = rate_control
         return result
 
     def _run_newton_scf(self, nel=None, nprod=None, max_iter=1000):
@@ -1371,6 +1420,13 @@ class Calculator(object):
                         active[todo] = False
                         break
                     lam[np.searchsorted(idx, todo)] *= 0.5
+            rate_control = None
+            if micro.get('rate_control'):
+                # at the final state the handle holds, before it is closed: the intrinsic coefficients and, through the transport
+                # tangent of the same state, the apparent ones of the coupled electrode
+                rate_control = self._final_rate_control(
+                    kin_solver, phiM, view=solver.device_view(), theta_guess=theta, rf=rf,
+                    coupling_of=lambda kin: solver.get_coupling(g, kin, rf=rf, dphi_max=dphi_max, fields=('T_c', 'T_phi')))
         finally:
             solver.close()
             kin_solver.close()
@@ -1389,6 +1445,8 @@ class Calculator(object):
             d['system']['coverage'] = theta[i].copy()
             d['system']['kinetic_status'] = int(kin_status[i])
             d['system']['coupling_status'] = int(cpl_status[i])
+            if rate_control is not None:
+                d['system']['rate_control'] = {k: np.array(v[i]) for k, v in rate_control.items()}
             for k, sp in enumerate(names):
                 d['species'].setdefault(sp, {})
                 d['species'][sp]['surface_concentration'] = float(sc[i, k])
@@ -1397,7 +1455,8 @@ class Calculator(object):
             d['system'].update({'surface_pH': float(surface_pH[i]), 'surface_potential': float(vsurf[i]),
                                 'surface_efield': float(esurf[i]), 'phiM': float(phiM[i])})
         hist = np.array(res_hist).reshape(len(res_hist), B)
-        return {'surface_concentration': sc, 'flux': flux, 'current_density': flux * nel * unit_F / nprod / 10., 'surface_pH': surface_pH,
+        extra = {} if rate_control is None else {'rate_control': rate_control}
+        return {**extra, 'surface_concentration': sc, 'flux': flux, 'current_density': flux * nel * unit_F / nprod / 10., 'surface_pH': surface_pH,
                 'accuracy': acc, 'converged': ~active & ~failed, 'failed': failed, 'iterations': steps, 'history': hist,
                 'newton_residual_history': hist, 'damping': np.array(damp_hist).reshape(len(damp_hist), B), 'coverage': theta,
                 'flux_scale': flux_scale, 'kinetic_status': kin_status, 'coupling_status': cpl_status, 'transport_solves': solves}

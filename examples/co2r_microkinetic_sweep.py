@@ -21,6 +21,12 @@ as the surface CO2 concentration drops from 5.7 to 0.14 mol/m^3 and CO* gives wa
 --newton: the same fixed point by a Newton iteration on the wall fluxes (Calculator.set_microkinetics(..., scf='newton'),
 include/catint_couple.h) in the place of the mixing loop: a handful of transport solves instead of one per mixing iteration.  The
 figures of both are in profiles/couple_probe.md.
+
+--rate-control: after the loop, the degree of rate control of the CO flux at the final surface state of every voltage
+(include/catint_drc.h, Calculator.set_microkinetics(..., rate_control=True)): per potential the step whose transition state and the
+intermediate whose free energy control the flux most, with Campbell's coefficient -- intrinsic (fixed surface state) and, with --newton,
+apparent (the coupled electrode: mass transport of CO2 takes its share of the control, so the apparent coefficients lie below the
+intrinsic ones; on an MI355X with --lanes 16 --newton: step 2 0.50 intrinsic, 0.43 apparent, CO2* 1.00 and 0.86).
 """
 import argparse
 import os
@@ -58,12 +64,13 @@ def main():
     ap.add_argument('--site-fraction', type=float, default=1e-3, help='fraction of the active site density that takes part')
     ap.add_argument('--max-iter', type=int, default=2000)
     ap.add_argument('--newton', action='store_true', help='Newton iteration on the wall fluxes instead of the mixing loop')
+    ap.add_argument('--rate-control', action='store_true', help='degree of rate control of the CO flux at the final state of every lane')
     a = ap.parse_args()
     tp, phis = co2r_physical_sweep.build(a.lanes, a.nx, a.phimin, a.phimax)
     tp.newton = {'tol': 1e-8, 'maxit': 80}
     calc = Calculator(transport=tp, calc='comsol', tau_scf=1e-4, mix_scf=0.1)
     calc.set_microkinetics(model(tp), site_density=a.site_fraction * float(tp.system['active site density']), potential_drop='stern',
-                          scf='newton' if a.newton else 'mixing')
+                          scf='newton' if a.newton else 'mixing', rate_control=a.rate_control)
     names = list(tp.species.keys())
     t0 = time.time()
     out = calc.run_scf_cycle(nel=[2.0 if sp == 'CO' else 1.0 for sp in names], max_iter=a.max_iter)
@@ -79,6 +86,17 @@ def main():
             digits = 16.0 + np.log10(abs(out['flux'][i, iCO]) / out['flux_scale'][i, iCO])
         print('%7.3f   %12.5e   %6.1f   %8.4f   %s' % (phis[i], out['flux'][i, iCO] * 2 * unit_F / 10.0, digits, out['surface_concentration'][i, iCO2],
                                                      '   '.join('%9.3e' % v for v in out['coverage'][i])))
+    if a.rate_control:
+        rc = out['rate_control']
+        ads = list(ADSORBATES)
+        kinds = [('intrinsic', 'drc', 'tdrc')] + ([('apparent', 'drc_apparent', 'tdrc_apparent')] if a.newton else [])
+        print('degree of rate control of the CO flux: controlling step (X_rc) and intermediate (X_trc)')
+        for i in range(a.lanes):
+            parts = []
+            for label, x, xt in kinds:
+                r, s = int(np.argmax(np.nan_to_num(np.abs(rc[x][i][:, iCO])))), int(np.argmax(np.nan_to_num(np.abs(rc[xt][i][:, iCO]))))
+                parts.append('%s: step %d %+.3f, %s* %+.3f' % (label, r + 1, rc[x][i][r, iCO], ads[s], rc[xt][i][s, iCO]))
+            print('%7.3f   status %d   %s' % (phis[i], rc['status'][i], '   '.join(parts)))
 
 
 if __name__ == '__main__':
