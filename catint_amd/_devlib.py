@@ -55,7 +55,8 @@ class Handle(object):
         return getattr(self._lib, self._prefix + name)
 
     def _call(self, entry, view, params, outputs):
-        rc = self._sym(entry)(self._h, C.byref(view), C.byref(params), C.byref(outputs))
+        """view: None where the library takes its state from the parameters instead"""
+        rc = self._sym(entry)(self._h, None if view is None else C.byref(view), C.byref(params), C.byref(outputs))
         if rc != 0:
             raise self._error(rc, self._sym('last_error')(self._h).decode())
 

@@ -6,8 +6,9 @@ import os
 
 import numpy as np
 
-from . import _devlib
+from . import _devlib, _microkin
 from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
+from ._microkin import DROP, MAX_ADSORBATES, MAX_ORDER, MAX_SITES, MAX_SPECIES, MAX_STEPS, MIN_LOG, _PD, _PI, _PL, _iptr  # noqa: F401  (the same)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CATINT_KINETICS_LIB') or os.path.join(_HERE, 'lib', 'libcatint_kinetics.so')
@@ -15,9 +16,6 @@ LIB_PATH = os.environ.get('CATINT_KINETICS_LIB') or os.path.join(_HERE, 'lib', '
 # every symbol include/catint_kinetics.h declares (tests/test_kinetics_abi.py)
 SYMBOLS = _devlib.symbols('catkin_', 'solve')
 
-MAX_SPECIES, MAX_ADSORBATES, MAX_STEPS, MAX_ORDER, MAX_SITES = 8, 8, 16, 3, 3
-MIN_LOG = -700.0
-DROP = {'full': 0, 'stern': 1}
 CONVERGED, MAXIT, INPUT, PIVOT = 0, 1, 2, 3
 DEFAULT_TOL, DEFAULT_MAXIT = 1e-12, 200
 # output rows: name -> shape of one operating point from (N, S, R)
@@ -30,9 +28,6 @@ class KineticsError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__('catint_kinetics error %d: %s' % (code, msg))
         self.code = code
-
-
-_PD, _PI, _PL = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 
 
 class CatkinParams(C.Structure):
@@ -59,18 +54,6 @@ def load_library():
     return _lib
 
 
-def _iptr(a):
-    return a.ctypes.data_as(_PI) if a is not None else None
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-
-
 class KineticsSolver(_devlib.Handle):
     """One ``catkin_ctx``.  No device call is made before the first ``solve`` that passes validation with at least one point."""
     _prefix, _error, _load = 'catkin_', KineticsError, staticmethod(load_library)
@@ -85,48 +68,15 @@ class KineticsSolver(_devlib.Handle):
         sigma [n] C/m^2 or None: stern_capacitance (phiM - phi_pzc - phi(0)); off [n][R][2], gamma [n][N], theta_guess [n][S+1] optional.
         fields: names out of FIELDS (None: DEFAULT_FIELDS).  Returns a dict of the requested arrays and 'status', 'iterations' [n]
         (int32).  The number of digits of 'flux' is what flux / flux_scale leaves of 16.  out: arrays to write into (tests)."""
-        site_count = _f64(tables['site_count']).reshape(-1)
-        of, ob = _i32(tables['order_f']), _i32(tables['order_b'])
-        T = len(site_count)
-        S = T - 1
-        R = of.shape[0] if of.ndim == 2 else 0
-        N = (of.shape[1] - T) if of.ndim == 2 else 0
-        names = list(DEFAULT_FIELDS) if fields is None else list(fields)
-        for nm in names:
-            if nm not in FIELDS:
-                raise ValueError('unknown field %r (known: %s)' % (nm, ', '.join(FIELDS)))
-        pm = _f64(np.atleast_1d(np.asarray(phiM, float))).reshape(-1)
-        n = len(pm)
-        idx = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        if idx is not None and len(idx) != n:
-            raise ValueError('lanes has %d entries, phiM %d' % (len(idx), n))
-        nu, cref, dG, Ea, lnA = (_f64(tables[k]) for k in ('nu', 'cref', 'dG', 'Ea', 'lnA'))
-        per_point = {'sigma': (_f64(sigma), n), 'off': (_f64(off), n * R * 2), 'gamma': (_f64(gamma), n * max(N, 0)),
-                     'theta_guess': (_f64(theta_guess), n * T), 'csurf': (_f64(csurf), n * max(N, 0)), 'phi_surface': (_f64(phi_surface), n)}
-        for name, (a, size) in per_point.items():
-            if a is not None and a.size != size:
-                raise ValueError('%s has %d values, the call needs %d' % (name, a.size, size))
-        for name, a, size in (('order_b', ob, R * (N + T)), ('nu', nu, R * max(N, 0)), ('cref', cref, max(N, 0)), ('dG', dG, R * 4), ('Ea', Ea, R * 4),
-                              ('lnA', lnA, R)):
-            if a.size != size:
-                raise ValueError('%s has %d values, the tables need %d' % (name, a.size, size))
-        pp = {k: v[0] for k, v in per_point.items()}
-        p = CatkinParams(C.sizeof(CatkinParams) if struct_size is None else int(struct_size), int(max_waves), N, S, R, int(maxit),
-                         potential_drop if isinstance(potential_drop, int) else DROP[potential_drop], 0, n,
-                         None if idx is None else idx.ctypes.data_as(_PL), _iptr(of), _iptr(ob), _dptr(nu), _dptr(cref), _dptr(site_count),
-                         _dptr(dG), _dptr(Ea), _dptr(lnA), float(tables['site_density']), float(tol), float(stern_capacitance), float(phi_pzc),
-                         _dptr(pm), _dptr(pp['sigma']), _dptr(pp['off']), _dptr(pp['gamma']), _dptr(pp['theta_guess']), _dptr(pp['csurf']),
-                         _dptr(pp['phi_surface']))
-        res = {} if out is None else out
-        Ns, Ss, Rs = max(N, 0), max(S, 0), max(R, 0)
-        for name in names:
-            res.setdefault(name, np.empty((n,) + FIELDS[name](Ns, Ss, Rs)))
-        res.setdefault('status', np.zeros(n, np.int32))
-        res.setdefault('iterations', np.zeros(n, np.int32))
+        per_point = {'sigma': sigma, 'off': off, 'gamma': gamma, 'theta_guess': theta_guess, 'csurf': csurf, 'phi_surface': phi_surface}
+        call = _microkin.Call(tables, phiM, lanes, per_point, fields, FIELDS, DEFAULT_FIELDS, potential_drop, stern_capacitance, phi_pzc, max_waves)
+        p = CatkinParams(struct_size=C.sizeof(CatkinParams) if struct_size is None else int(struct_size), maxit=int(maxit), tol=float(tol),
+                         **call.members)
+        res = call.results(FIELDS, out)
+        res.setdefault('status', np.zeros(call.n, np.int32))
+        res.setdefault('iterations', np.zeros(call.n, np.int32))
         o = CatkinOutputs(struct_size=C.sizeof(CatkinOutputs) if out_struct_size is None else int(out_struct_size),
                           status=_iptr(res['status']), iterations=_iptr(res['iterations']),
                           **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
-        rc = self._sym('solve')(self._h, None if view is None else C.byref(view), C.byref(p), C.byref(o))
-        if rc != 0:
-            raise self._error(rc, self._sym('last_error')(self._h).decode())
+        self._call('solve', view, p, o)
         return res

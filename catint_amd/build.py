@@ -18,6 +18,8 @@ _INCLUDE = os.path.join(_HERE, '..', 'include')
 _POST_HEADERS = [os.path.join(CSRC, h) for h in ('pnp_post.h', 'pnp_wave.h', 'pnp_math.h', 'pnp_internal.h')] + [os.path.join(_INCLUDE, 'catint_pnp.h')]
 # what the two libraries that eliminate the stationary Jacobian with a team of lanes per system include on top (csrc/pnp_team.h)
 _TEAM_HEADERS = _POST_HEADERS + [os.path.join(CSRC, 'pnp_team.h')]
+# what the two libraries that work on a microkinetic model with one operating point per lane include on top (csrc/pnp_kin.h)
+_KIN_HEADERS = _POST_HEADERS + [os.path.join(CSRC, 'pnp_kin.h')]
 
 # second library (include/catint_observe.h): observables derived from a device-resident state.  Its kernels stay out of SOURCES:
 # the solver library holds the solver's kernels and nothing else (tests/test_kernel_census.py)
@@ -59,7 +61,7 @@ RESPONSE_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_response.h')]
 KINETICS_DIR = os.path.join(CSRC, 'kinetics')
 KINETICS_LIB = os.path.join(LIB_DIR, 'libcatint_kinetics.so')
 KINETICS_SOURCES = ['catkin.hip']
-KINETICS_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h')]
+KINETICS_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h')]
 
 # eighth library (include/catint_couple.h): one Newton step of the self-consistency between kinetics and transport per operating
 # point -- the transport tangent from one block elimination, the Newton matrix and the damped step at the wall.  A library of its
@@ -83,14 +85,14 @@ SENS_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_sens.h')]
 DRC_DIR = os.path.join(CSRC, 'drc')
 DRC_LIB = os.path.join(LIB_DIR, 'libcatint_drc.so')
 DRC_SOURCES = ['catdrc.hip']
-DRC_HEADERS = _POST_HEADERS + [os.path.join(_INCLUDE, 'catint_drc.h')]
+DRC_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_drc.h')]
 
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
 UNITTEST_LIB = os.path.join(LIB_DIR, 'libcatint_unittest.so')
 UNITTEST_SOURCES = ['primitives_harness.hip']
-UNITTEST_HEADERS = _POST_HEADERS + [os.path.join(CSRC, 'pnp_lane_common.h'), os.path.join(CSRC, 'pnp_lane_cols.h')]
+UNITTEST_HEADERS = _KIN_HEADERS + [os.path.join(CSRC, 'pnp_lane_common.h'), os.path.join(CSRC, 'pnp_lane_cols.h')]
 
 PARTIAL = os.path.join(LIB_DIR, '.partial')      # left by tools/devbuild.sh: the library holds only one block size
 

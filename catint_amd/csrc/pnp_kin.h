@@ -1,0 +1,512 @@
+// What the two libraries that work on a mean-field surface microkinetic model with ONE OPERATING POINT PER LANE have in common
+// (kinetics/catkin.hip, drc/catdrc.hip): the tables of a call, the rate constants and rates, the scaled rows of the steady state, the
+// per-lane LU, and the host code around a launch.  Each library is one translation unit and compiles its own copy: nothing here is
+// exported.  The frame of an entry point (context, rows, reserve) is that of pnp_post.h.  gfx950 / MI355X only.
+//
+// Mapping: one operating point per lane, one wave per workgroup, persistent waves walking groups of 64 points.  No lane ever reads what
+// another lane wrote, so there is no barrier and no cross-lane exchange; the only per-lane control is the row a lane chooses as its
+// pivot, which is an address, and the branch of Ga, which is a select.
+// Working set: everything that is indexed by a run-time step, column or row number lives in LDS as [slot][lane], the lane fastest (a
+// wave's 8-byte accesses are conflict-free, and a per-lane row number is only an address): the matrix J[T][T] (T = S + 1), y[T], the
+// right-hand side [T], the row scales D[T], the activities a[N] and what else the kernel keeps, sized per call (dynamic LDS).  The
+// functions here take the lane's pointer to the first slot of an array (lds + lane + 64 slot): element e is p[64 e].  Registers hold
+// scalars only, so nothing goes to scratch.  The pivot rows of the factorisation are kept as 4-bit fields of one 64-bit register.
+// Tables (orders, stoichiometry, polynomial coefficients) are the same for every lane and are read at wave-uniform addresses through a
+// read-only pointer: every loop over steps and columns has a uniform trip count.
+// Arithmetic: IEEE divisions and the compiler's exp / log (pnp_math.h has exp(u) - 1 away from 0 and log(1 + x) on (-1, 0] only);
+// implicit contraction is off, so a point's numbers do not depend on where in the batch it stands.  Every device function here switches
+// it off in its own body: whatever the including source sets, and wherever it sets it, governs that source's code alone.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "pnp_post.h"
+
+namespace pnp {
+namespace kin {
+
+using namespace pnp::post;
+
+// the CATKIN_* / CATDRC_* limits and values
+constexpr int MAXN = MAX_SPECIES, MAXS = 8, MAXT = MAXS + 1, MAXR = 16, MAXM = MAXN + MAXT, MAX_ORDER = 3;
+constexpr int DROP_FULL = 0, DROP_STERN = 1;
+constexpr double MINLOG = -700.0;
+static_assert(MAXT <= 15, "a pivot row is a 4-bit field");
+
+// the tables of one call, flattened on the host (everything validated there)
+struct Table {
+  int32_t of[MAXR][MAXM + 1], ob[MAXR][MAXM + 1];   // columns 0 .. N-1: species, N .. N+S: coverages
+  double nu[MAXR][MAXN];
+  double cref[MAXN];
+  double ns[MAXT + 1];
+  double dg[MAXR][4], ea[MAXR][4], lnA[MAXR];
+};
+static_assert(sizeof(Table) % 8 == 0, "the table is copied as doubles");
+
+// ---- device ------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool finite_(double a) { return fabs(a) < INFINITY; }
+
+// y = ln of a given coverage g, clamped to [MINLOG, 0]
+__device__ __forceinline__ double log_coverage(double g) {
+  double y = g >= 1.0 ? 0.0 : (g > 0.0 ? log(g) : MINLOG);
+  y = y < MINLOG ? MINLOG : y;
+  return y;
+}
+
+// what the head of the loop over groups leaves of a point's inputs
+struct Point {
+  bool ok;             // every input finite, and on the view path the solver's lane converged
+  double V, sg;        // potential and charge
+  const double* off;   // [R][2] of the point, or null
+};
+
+// The inputs of point i (lane b of the view).  The activities go to the N slots from `a`.  A: the kernel's arguments, read by name
+// (int32 N, R, w, use_sigma, from_view, ldx; c, phi, st of the view; cs, phis, phiM, sigma, off, gamma; CS, pzc)
+template <class KA>
+__device__ __forceinline__ Point point_inputs(const KA& A, const Table& tb, int64_t i, int64_t b, double* a) {
+#pragma clang fp contract(off)
+  const int N = A.N, R = A.R;
+  Point pt;
+  const double phiM = A.phiM[i];
+  const double phi0 = A.from_view ? A.phi[(size_t)b * A.ldx] : A.phis[i];
+  bool ok = finite_(phiM) && finite_(phi0);
+  if (A.from_view) ok = ok && A.st[b] == 0;
+  for (int j = 0; j < N; ++j) {
+    const double c = A.from_view ? A.c[((size_t)b * N + j) * A.ldx] : A.cs[i * N + j];
+    const double g = A.gamma ? A.gamma[i * N + j] : 1.0;
+    ok = ok && finite_(c) && finite_(g);
+    a[j * 64] = g * (c > 0.0 ? c : 0.0) / tb.cref[j];
+  }
+  pt.V = phiM - (A.w ? phi0 : 0.0);
+  pt.sg = A.use_sigma ? A.sigma[i] : A.CS * ((phiM - A.pzc) - phi0);
+  ok = ok && finite_(pt.sg);
+  pt.off = A.off ? A.off + (size_t)i * R * 2 : nullptr;
+  if (pt.off)
+    for (int r = 0; r < 2 * R; ++r) ok = ok && finite_(pt.off[r]);
+  pt.ok = ok;
+  return pt;
+}
+
+// ln kf, ln kb of step r and the branch of Ga (0: Ea, 1: dG, 2: zero)
+__device__ __forceinline__ void rate_constants(const Table& tb, double V, double sg, const double* off, int r, double& lf, double& lb, int& br) {
+#pragma clang fp contract(off)
+  const double s2 = sg * sg;
+  const double dG = ((tb.dg[r][0] + tb.dg[r][1] * V) + tb.dg[r][2] * sg) + tb.dg[r][3] * s2;
+  const double Ea = ((tb.ea[r][0] + tb.ea[r][1] * V) + tb.ea[r][2] * sg) + tb.ea[r][3] * s2;
+  const bool b0 = Ea >= dG && Ea >= 0.0, b1 = dG >= 0.0;
+  br = b0 ? 0 : (b1 ? 1 : 2);
+  const double Ga = b0 ? Ea : (b1 ? dG : 0.0);
+  const double o0 = off ? off[2 * r] : 0.0, o1 = off ? off[2 * r + 1] : 0.0;
+  lf = (tb.lnA[r] - Ga) + o0;
+  lb = (tb.lnA[r] - (Ga - dG)) + o1;
+}
+
+// d ln kf / dp and d ln kb / dp of step r for dV/dp = dV, dsigma/dp = ds
+__device__ __forceinline__ void rate_constant_slopes(const Table& tb, double sg, int r, int br, double dV, double ds, double& dlf, double& dlb) {
+#pragma clang fp contract(off)
+  const double ddG = tb.dg[r][1] * dV + (tb.dg[r][2] + 2.0 * tb.dg[r][3] * sg) * ds;
+  const double dEa = tb.ea[r][1] * dV + (tb.ea[r][2] + 2.0 * tb.ea[r][3] * sg) * ds;
+  const double dGa = br == 0 ? dEa : (br == 1 ? ddG : 0.0);
+  dlf = -dGa;
+  dlb = -(dGa - ddG);
+}
+
+// the two factors of rf and rb: exp(ln k + sum_t order y_t) and prod_j a_j^order, y in the T slots from `y`, the activities in the N
+// slots from `a`.  skip: a species whose order counts one less (the product with one factor left out), -1: none
+__device__ __forceinline__ void rate_factors(const Table& tb, int N, int T, const double* y, const double* a, int r, double lf, double lb, int skip,
+                                             double& ef, double& eb, double& pf, double& pb) {
+#pragma clang fp contract(off)
+  double sf = lf, sb = lb;
+  for (int t = 0; t < T; ++t) {
+    const int of = tb.of[r][N + t], ob = tb.ob[r][N + t];
+    if (of | ob) {
+      const double v = y[t * 64];
+      if (of) sf = sf + (double)of * v;
+      if (ob) sb = sb + (double)ob * v;
+    }
+  }
+  pf = 1.0;
+  pb = 1.0;
+  for (int j = 0; j < N; ++j) {
+    const int of = tb.of[r][j] - (j == skip ? 1 : 0), ob = tb.ob[r][j] - (j == skip ? 1 : 0);
+    if (of > 0 || ob > 0) {
+      const double v = a[j * 64];
+      for (int e = 0; e < of; ++e) pf = pf * v;
+      for (int e = 0; e < ob; ++e) pb = pb * v;
+    }
+  }
+  ef = exp(sf);
+  eb = exp(sb);
+}
+
+// step r at the rates rf, rb into the unscaled rows: its net rate into B, its gross rate into the row scales D, its derivative into J
+__device__ __forceinline__ void add_step_rows(const Table& tb, int N, int T, int r, double rf, double rb, double* J, double* B, double* D) {
+#pragma clang fp contract(off)
+  const double net = rf - rb, gross = rf + rb;
+  for (int s = 1; s < T; ++s) {
+    const int m = tb.ob[r][N + s] - tb.of[r][N + s];
+    if (m == 0) continue;
+    const double dm = (double)m;
+    B[s * 64] = B[s * 64] + dm * net;
+    D[s * 64] = D[s * 64] + fabs(dm) * gross;
+    for (int t = 0; t < T; ++t) {
+      const int of = tb.of[r][N + t], ob = tb.ob[r][N + t];
+      if (of | ob) {
+        double* e = &J[(s * T + t) * 64];
+        *e = *e + dm * (rf * (double)of - rb * (double)ob);
+      }
+    }
+  }
+}
+
+// Row s of J divided by its scale d.  An adsorbate that nothing produces or consumes (d == 0: a dead row) gets the identity row and is
+// set to MINLOG, where the row keeps it.  Returns whether the row is dead
+__device__ __forceinline__ bool scale_row(double* J, double* y, int T, int s, double d) {
+#pragma clang fp contract(off)
+  const bool dead = d == 0.0;
+  for (int t = 0; t < T; ++t) {
+    double* e = &J[(s * T + t) * 64];
+    *e = dead ? (t == s ? 1.0 : 0.0) : *e / d;
+  }
+  if (dead) y[s * 64] = MINLOG;
+  return dead;
+}
+
+// the site row: n_t theta_t into row 0 of J; their sum
+__device__ __forceinline__ double site_row(const Table& tb, double* J, const double* y, int T) {
+#pragma clang fp contract(off)
+  double f0 = 0.0;
+  for (int t = 0; t < T; ++t) {
+    const double th = tb.ns[t] * exp(y[t * 64]);
+    J[t * 64] = th;
+    f0 = f0 + th;
+  }
+  return f0;
+}
+
+// LU with partial row pivoting in place: rows exchanged whole, multipliers below the diagonal, the pivot row of step k in bits
+// 4k .. 4k+3 (the first of equal magnitudes wins).  Returns whether a pivot was zero or not finite
+__device__ __forceinline__ bool factor(double* J, int T, uint64_t& pivs) {
+#pragma clang fp contract(off)
+  bool bad = false;
+  pivs = 0;
+  for (int k = 0; k < T; ++k) {
+    int p = k;
+    double best = fabs(J[(k * T + k) * 64]);
+    for (int i = k + 1; i < T; ++i) {
+      const double v = fabs(J[(i * T + k) * 64]);
+      const bool up = v > best;
+      best = up ? v : best;
+      p = up ? i : p;
+    }
+    pivs |= (uint64_t)p << (4 * k);
+    for (int c = 0; c < T; ++c) {
+      const double a = J[(k * T + c) * 64], b = J[(p * T + c) * 64];
+      J[(p * T + c) * 64] = a;
+      J[(k * T + c) * 64] = b;
+    }
+    const double piv = J[(k * T + k) * 64];
+    bad = bad || !(piv != 0.0 && finite_(piv));
+    for (int i = k + 1; i < T; ++i) {
+      const double f = J[(i * T + k) * 64] / piv;
+      J[(i * T + k) * 64] = f;
+      for (int c = k + 1; c < T; ++c) J[(i * T + c) * 64] = J[(i * T + c) * 64] - f * J[(k * T + c) * 64];
+    }
+  }
+  return bad;
+}
+
+// the right-hand side in the T slots from `b` against the stored factors, in place
+__device__ __forceinline__ void substitute(const double* J, double* b, int T, uint64_t pivs) {
+#pragma clang fp contract(off)
+  // the rows were exchanged whole, multipliers included: every exchange is applied to the right-hand side before the first elimination
+  for (int k = 0; k < T; ++k) {
+    const int p = (int)((pivs >> (4 * k)) & 15);
+    const double u = b[k * 64], v = b[p * 64];
+    b[p * 64] = u;
+    b[k * 64] = v;
+  }
+  for (int k = 0; k < T; ++k) {
+    const double v = b[k * 64];
+    for (int i = k + 1; i < T; ++i) b[i * 64] = b[i * 64] - J[(i * T + k) * 64] * v;
+  }
+  for (int k = T - 1; k >= 0; --k) {
+    double s = b[k * 64];
+    for (int c = k + 1; c < T; ++c) s = s - J[(k * T + c) * 64] * b[c * 64];
+    b[k * 64] = s / J[(k * T + k) * 64];
+  }
+}
+
+// ---- host: the context ---------------------------------------------------------------------------------------------------------------
+struct Ctx : pnp::post::Ctx {
+  std::vector<double> stage;    // host: the inputs of the call in flight, one copy
+  std::vector<int32_t> flags;   // host: the int32 rows (status, iterations) as the kernel wrote them
+};
+
+// ---- host: what an entry point checks, in three parts; the library's own checks stand between them.  0 or the code.  Params:
+// ---- catkin_params / catdrc_params, read by the member names the two share; entry: the exported function, the head of every message --
+static bool posfin(double v) { return v > 0.0 && std::isfinite(v); }
+
+// the arguments themselves and the sizes of the model
+template <class Params, class Outputs>
+static int check_sizes(Ctx* ctx, const char* entry, const char* params_name, const char* outputs_name, const Params* p, const Outputs* out) {
+  if (!ctx) return ERR_INVAL;
+  const std::string e(entry);
+  char msg[256];
+  if (!p || !out) return fail(ctx, ERR_INVAL, e + ": null argument");
+  if (p->struct_size != (int32_t)sizeof(Params)) return fail(ctx, ERR_INVAL, e + ": " + params_name + ".struct_size does not match this library");
+  if (out->struct_size != (int32_t)sizeof(Outputs)) return fail(ctx, ERR_INVAL, e + ": " + outputs_name + ".struct_size does not match this library");
+  const int N = p->nspecies, S = p->nadsorbates, R = p->nsteps;
+  if (N < 0 || N > MAXN) {
+    snprintf(msg, sizeof msg, "%s: %d species outside [0, %d]", entry, N, MAXN);
+    return fail(ctx, ERR_INVAL, msg);
+  }
+  if (S < 1 || S > MAXS) {
+    snprintf(msg, sizeof msg, "%s: %d adsorbates outside [1, %d]", entry, S, MAXS);
+    return fail(ctx, ERR_INVAL, msg);
+  }
+  if (R < 1 || R > MAXR) {
+    snprintf(msg, sizeof msg, "%s: %d steps outside [1, %d]", entry, R, MAXR);
+    return fail(ctx, ERR_INVAL, msg);
+  }
+  if (p->max_waves < 0) return fail(ctx, ERR_INVAL, e + ": negative max_waves");
+  return OK;
+}
+
+template <class Params>
+static int check_drop(Ctx* ctx, const char* entry, const Params* p) {
+  if (p->potential_drop != DROP_FULL && p->potential_drop != DROP_STERN)
+    return fail(ctx, ERR_INVAL, std::string(entry) + ": potential_drop is 0 (full) or 1 (Stern)");
+  return OK;
+}
+
+// the tables
+template <class Params>
+static int check_tables(Ctx* ctx, const char* entry, const Params* p) {
+  const std::string e(entry);
+  char msg[256];
+  const int N = p->nspecies, R = p->nsteps, T = p->nadsorbates + 1, M = N + T;
+  if (!posfin(p->site_density)) return fail(ctx, ERR_INVAL, e + ": site_density must be positive and finite");
+  if (!p->order_f || !p->order_b || !p->site_count || !p->dG || !p->Ea || !p->lnA || (N > 0 && (!p->nu || !p->cref)))
+    return fail(ctx, ERR_INVAL, e + ": order_f, order_b, nu, cref, site_count, dG, Ea and lnA are required");
+  for (int j = 0; j < N; ++j)
+    if (!posfin(p->cref[j])) {
+      snprintf(msg, sizeof msg, "%s: cref[%d] must be positive and finite", entry, j);
+      return fail(ctx, ERR_INVAL, msg);
+    }
+  for (int t = 0; t < T; ++t) {
+    const double v = p->site_count[t];
+    if (!(t == 0 ? v == 1.0 : (v == 1.0 || v == 2.0 || v == 3.0))) {
+      snprintf(msg, sizeof msg, "%s: site count %d must be 1, 2 or 3 (1 for the free site)", entry, t);
+      return fail(ctx, ERR_INVAL, msg);
+    }
+  }
+  for (int r = 0; r < R; ++r) {
+    double sites = 0.0;
+    bool any_f = false, any_b = false, any_nu = false;
+    for (int c = 0; c < M; ++c) {
+      const int of = p->order_f[r * M + c], ob = p->order_b[r * M + c];
+      if (of < 0 || of > MAX_ORDER || ob < 0 || ob > MAX_ORDER) {
+        snprintf(msg, sizeof msg, "%s: step %d has an order outside [0, %d]", entry, r, MAX_ORDER);
+        return fail(ctx, ERR_INVAL, msg);
+      }
+      any_f = any_f || of;
+      any_b = any_b || ob;
+      if (c >= N) sites += p->site_count[c - N] * (ob - of);
+    }
+    if (sites != 0.0) {
+      snprintf(msg, sizeof msg, "%s: step %d does not conserve sites", entry, r);
+      return fail(ctx, ERR_INVAL, msg);
+    }
+    for (int k = 0; k < N; ++k) {
+      if (!std::isfinite(p->nu[r * N + k])) {
+        snprintf(msg, sizeof msg, "%s: nu of step %d is not finite", entry, r);
+        return fail(ctx, ERR_INVAL, msg);
+      }
+      any_nu = any_nu || p->nu[r * N + k] != 0.0;
+    }
+    if ((!any_f || !any_b) && !any_nu) {
+      snprintf(msg, sizeof msg, "%s: step %d is an empty step (no orders on a side and no stoichiometry)", entry, r);
+      return fail(ctx, ERR_INVAL, msg);
+    }
+    bool fin = std::isfinite(p->lnA[r]);
+    for (int q = 0; q < 4; ++q) {
+      fin = fin && std::isfinite(p->dG[r * 4 + q]);
+      const double v = p->Ea[r * 4 + q];
+      fin = fin && (std::isfinite(v) || (q == 0 && v == -INFINITY));
+    }
+    if (!fin) {
+      snprintf(msg, sizeof msg, "%s: step %d has a non-finite table entry (only e0 may be -INFINITY)", entry, r);
+      return fail(ctx, ERR_INVAL, msg);
+    }
+  }
+  if (!p->phiM) return fail(ctx, ERR_INVAL, e + ": phiM is required");
+  return OK;
+}
+
+// the surface charge, the points and where their surface state comes from (*from_view: the view)
+template <class Params>
+static int check_points(Ctx* ctx, const char* entry, const pnp_device_view* view, const Params* p, bool* from_view) {
+  const std::string e(entry);
+  char msg[256];
+  if (!p->sigma && !(std::isfinite(p->stern_capacitance) && std::isfinite(p->phi_pzc)))
+    return fail(ctx, ERR_INVAL, e + ": the surface charge needs sigma or a finite stern_capacitance and phi_pzc");
+  if (p->n < 0) return fail(ctx, ERR_INVAL, e + ": n < 0");
+  const int64_t n = p->n;
+  if ((p->csurf == nullptr) != (p->phi_surface == nullptr))
+    return fail(ctx, ERR_INVAL, e + ": csurf and phi_surface come together (or both NULL: the view)");
+  *from_view = !p->csurf;
+  if (*from_view) {
+    if (!view) return fail(ctx, ERR_INVAL, e + ": null view without csurf and phi_surface");
+    if (view->struct_size != (int32_t)sizeof(pnp_device_view)) return fail(ctx, ERR_INVAL, e + ": pnp_device_view.struct_size does not match this library");
+    if (!view->phi_dev || !view->c_dev)
+      return fail(ctx, ERR_INVAL, e + ": the view has no potential row (only the physical mode keeps the potential in its state)");
+    if (!view->status_dev) return fail(ctx, ERR_INVAL, e + ": the view has no status row");
+    if (view->nspecies != p->nspecies) {
+      snprintf(msg, sizeof msg, "%s: %d species, the view has %d", entry, p->nspecies, view->nspecies);
+      return fail(ctx, ERR_INVAL, msg);
+    }
+    if (view->batch < 1 || view->nx < 1 || view->row_pitch < view->nx) return fail(ctx, ERR_INVAL, e + ": empty batch or a row pitch below nx");
+    if (!p->lanes && n > view->batch) return fail(ctx, ERR_INVAL, e + ": n above the batch (lanes is NULL)");
+    if (p->lanes)
+      for (int64_t i = 0; i < n; ++i)
+        if (p->lanes[i] < 0 || p->lanes[i] >= view->batch) {
+          snprintf(msg, sizeof msg, "%s: lane index %lld outside [0, %lld)", entry, (long long)p->lanes[i], (long long)view->batch);
+          return fail(ctx, ERR_INVAL, msg);
+        }
+  } else if (view && view->struct_size != (int32_t)sizeof(pnp_device_view)) {
+    return fail(ctx, ERR_INVAL, e + ": pnp_device_view.struct_size does not match this library");
+  }
+  return OK;
+}
+
+// ---- host: the inputs of a call, staged for one copy -----------------------------------------------------------------------------------
+// offsets in doubles into the staging vector and, after the copy, into the context's device buffer
+struct Stage {
+  bool from_view;      // the surface state comes from the view, not from csurf and phi_surface
+  size_t o_pm, o_cs, o_ps, o_sg, o_off, o_gm, o_th, o_l, o_t, n_in;   // phiM, csurf, phi_surface, sigma, off, gamma, coverages, lanes, Table; all
+};
+
+template <class Params>
+static void fill_table(Table* tb, const Params* p) {
+  const int N = p->nspecies, R = p->nsteps, T = p->nadsorbates + 1, M = N + T;
+  for (int r = 0; r < R; ++r) {
+    for (int c = 0; c < M; ++c) tb->of[r][c] = p->order_f[r * M + c], tb->ob[r][c] = p->order_b[r * M + c];
+    for (int k = 0; k < N; ++k) tb->nu[r][k] = p->nu[r * N + k];
+    for (int q = 0; q < 4; ++q) tb->dg[r][q] = p->dG[r * 4 + q], tb->ea[r][q] = p->Ea[r * 4 + q];
+    tb->lnA[r] = p->lnA[r];
+  }
+  for (int j = 0; j < N; ++j) tb->cref[j] = p->cref[j];
+  for (int t = 0; t < T; ++t) tb->ns[t] = p->site_count[t];
+}
+
+// Lays out and fills ctx->stage, the Table included, and sizes ctx->flags to `flag_rows` int32 rows of n.  theta: the coverages
+// [n][T] the library takes (catkin's optional guess, catdrc's state), or null
+template <class Params>
+static int stage_inputs(Ctx* ctx, const char* entry, const Params* p, const double* theta, bool from_view, int flag_rows, Stage* s) {
+  const int N = p->nspecies, R = p->nsteps, T = p->nadsorbates + 1;
+  const int64_t n = p->n;
+  const size_t sn = (size_t)n;
+  s->from_view = from_view;
+  s->o_pm = 0;
+  s->o_cs = s->o_pm + even(sn);
+  s->o_ps = s->o_cs + (from_view ? 0 : even(sn * N));
+  s->o_sg = s->o_ps + (from_view ? 0 : even(sn));
+  s->o_off = s->o_sg + (p->sigma ? even(sn) : 0);
+  s->o_gm = s->o_off + (p->off ? sn * R * 2 : 0);
+  s->o_th = s->o_gm + (p->gamma ? even(sn * N) : 0);
+  s->o_l = s->o_th + (theta ? even(sn * T) : 0);
+  s->o_t = s->o_l + sn;
+  s->n_in = s->o_t + sizeof(Table) / 8;
+  try {
+    ctx->stage.assign(s->n_in, 0.0);
+    ctx->flags.assign(flag_rows * sn, 0);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, ERR_NOMEM, std::string(entry) + ": out of host memory");
+  }
+  double* sg = ctx->stage.data();
+  memcpy(sg + s->o_pm, p->phiM, sn * 8);
+  if (!from_view) {
+    if (N) memcpy(sg + s->o_cs, p->csurf, sn * N * 8);
+    memcpy(sg + s->o_ps, p->phi_surface, sn * 8);
+  }
+  if (p->sigma) memcpy(sg + s->o_sg, p->sigma, sn * 8);
+  if (p->off) memcpy(sg + s->o_off, p->off, sn * R * 2 * 8);
+  if (p->gamma && N) memcpy(sg + s->o_gm, p->gamma, sn * N * 8);
+  if (theta) memcpy(sg + s->o_th, theta, sn * T * 8);
+  int64_t* l = reinterpret_cast<int64_t*>(sg + s->o_l);
+  for (int64_t i = 0; i < n; ++i) l[i] = (from_view && p->lanes) ? p->lanes[i] : i;
+  fill_table(reinterpret_cast<Table*>(sg + s->o_t), p);
+  return OK;
+}
+
+// the members of the kernel's arguments that both kernels have, but for the device addresses (KA: see point_inputs; n, S, sd on top)
+template <class KA, class Params>
+static void set_args(KA& a, const pnp_device_view* view, const Params* p, bool from_view) {
+  memset(&a, 0, sizeof a);
+  a.N = p->nspecies; a.S = p->nadsorbates; a.R = p->nsteps; a.w = p->potential_drop; a.use_sigma = p->sigma != nullptr;
+  a.from_view = from_view; a.n = p->n;
+  a.sd = p->site_density; a.CS = p->stern_capacitance; a.pzc = p->phi_pzc;
+  if (from_view) {
+    a.ldx = view->row_pitch;
+    a.c = view->c_dev; a.phi = view->phi_dev; a.st = view->status_dev;
+  }
+}
+
+// The tail of an entry point.  One wave per block: max_waves of them, or (0) what the device holds at `lds` bytes each; the staged
+// inputs to the device buffer, the output rows and `flag_rows` int32 rows of n behind them; `kernel` between the context's two events
+// (last_kernel_ms) under the name `kernel_name`; the wanted rows back, the int32 rows back to ctx->flags when want_flags; the stream
+// drained.  own(const double* theta, int32_t* flags) puts the device addresses of the staged coverages (where there are any) and of
+// the int32 rows into the arguments `a` under the library's own names.
+template <class KA, class Params, size_t NR, class F>
+static int run(Ctx* ctx, const char* entry, const char* kernel_name, void (*kernel)(const KA, const Table*), const pnp_device_view* view, const Params* p,
+               const Stage& s, KA& a, const Row (&rows)[NR], size_t lds, int flag_rows, bool want_flags, F&& own) {
+  const bool from_view = s.from_view;
+  const int64_t n = p->n;
+  const size_t sn = (size_t)n;
+  const size_t need_out = rows_doubles(rows), n_flags = even(sn) * flag_rows / 2;
+  PNP_POST_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = from_view ? (hipStream_t)view->stream : (hipStream_t) nullptr;
+  if (lds > 48 * 1024) PNP_POST_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int64_t groups = (n + 63) / 64;
+  int64_t blocks = p->max_waves;
+  if (blocks == 0) {
+    int cus = 0, per_cu = 0;
+    PNP_POST_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    PNP_POST_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, lds));
+    blocks = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
+  }
+  blocks = std::min(std::max<int64_t>(blocks, 1), groups);
+  if (const int rc = reserve(ctx, entry, s.n_in + need_out + n_flags)) return rc;
+  a.phiM = ctx->buf + s.o_pm;
+  if (!from_view) a.cs = ctx->buf + s.o_cs, a.phis = ctx->buf + s.o_ps;
+  if (p->sigma) a.sigma = ctx->buf + s.o_sg;
+  if (p->off) a.off = ctx->buf + s.o_off;
+  if (p->gamma && p->nspecies) a.gamma = ctx->buf + s.o_gm;
+  a.lanes = reinterpret_cast<const int64_t*>(ctx->buf + s.o_l);
+  const Table* tab = reinterpret_cast<const Table*>(ctx->buf + s.o_t);   // a kernel argument of its own (read-only: scalar loads)
+  int32_t* flags_dev = reinterpret_cast<int32_t*>(place_rows(rows, ctx->buf + s.n_in));
+  own(ctx->buf + s.o_th, flags_dev);
+  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, ctx->stage.data(), s.n_in * sizeof(double), hipMemcpyHostToDevice, st));
+  if (!ctx->ev0) PNP_POST_HIP(hipEventCreate(&ctx->ev0));
+  if (!ctx->ev1) PNP_POST_HIP(hipEventCreate(&ctx->ev1));
+  ctx->kernel_ms = -1.0f;
+  PNP_POST_HIP(hipEventRecord(ctx->ev0, st));
+  hipLaunchKernelGGL(kernel, dim3((int)blocks), dim3(64), lds, st, a, tab);
+  PNP_POST_HIP(hipGetLastError());
+  PNP_POST_HIP(hipEventRecord(ctx->ev1, st));
+  for (const Row& r : rows)
+    if (r.wanted()) PNP_POST_HIP(hipMemcpyAsync(r.host, *r.dev, r.n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (want_flags) PNP_POST_HIP(hipMemcpyAsync(ctx->flags.data(), flags_dev, flag_rows * sn * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  PNP_POST_HIP(hipStreamSynchronize(st));
+  PNP_POST_HIP(hipEventElapsedTime(&ctx->kernel_ms, ctx->ev0, ctx->ev1));
+  ctx->last_kernel = kernel_name;
+  return OK;
+}
+
+}  // namespace kin
+}  // namespace pnp

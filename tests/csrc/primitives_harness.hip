@@ -1,4 +1,4 @@
-// Test-only harness (libcatint_unittest.so): every shared device primitive of the five libraries behind a kernel of its own, so that
+// Test-only harness (libcatint_unittest.so): every shared device primitive of the libraries behind a kernel of its own, so that
 // tests/test_gpu_primitives.py can hold each one to its own accuracy claim instead of seeing it through solver output.  Nothing of the
 // product links against this library.  gfx950 / MI355X only.
 //
@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../catint_amd/csrc/pnp_kin.h"
 #include "../../catint_amd/csrc/pnp_lane_cols.h"
 #include "../../catint_amd/csrc/pnp_lane_common.h"
 #include "../../catint_amd/csrc/pnp_math.h"
@@ -284,6 +285,29 @@ __global__ __launch_bounds__(256) void newton_accept_kernel(const double* __rest
   accept[i] = newton_accept(lam[i], upd[i], prev, tol[i], estimate[i] != 0.0) ? 1.0 : 0.0;
   prev_out[i] = prev;
 }
+
+// ---- the per-lane LU of pnp_kin.h: one wave, one system of order T with two right-hand sides per lane ------------------------------------
+// A: [64][T][T], b: [64][2][T].  LDS as the libraries lay it out, [slot][lane]: J in slots 0 .. T T - 1, the right-hand sides in the 2 T slots
+// behind (dynamic, lu_lds_bytes(T)).  lu: [64][T][T] the factors; meta: [64][2] the packed pivot rows and the bad-pivot flag; x: [64][2][T].
+// This source sets no contraction pragma: the header's functions carry their own
+__global__ __launch_bounds__(64) void lu_kernel(const double* __restrict__ A, const double* __restrict__ b, int T, double* __restrict__ lu,
+                                                uint64_t* __restrict__ meta, double* __restrict__ x) {
+  extern __shared__ double lu_lds[];
+  const int lane = threadIdx.x;
+  double* J = lu_lds + lane;
+  double* rhs = J + T * T * 64;
+  for (int e = 0; e < T * T; ++e) J[e * 64] = A[lane * T * T + e];
+  for (int e = 0; e < 2 * T; ++e) rhs[e * 64] = b[lane * 2 * T + e];
+  uint64_t pivs = 0;
+  const bool bad = kin::factor(J, T, pivs);
+  kin::substitute(J, rhs, T, pivs);
+  kin::substitute(J, rhs + T * 64, T, pivs);
+  for (int e = 0; e < T * T; ++e) lu[lane * T * T + e] = J[e * 64];
+  for (int e = 0; e < 2 * T; ++e) x[lane * 2 * T + e] = rhs[e * 64];
+  meta[lane * 2] = pivs;
+  meta[lane * 2 + 1] = bad ? 1 : 0;
+}
+static size_t lu_lds_bytes(int T) { return (size_t)(T * T + 2 * T) * 64 * sizeof(double); }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------------
 struct Buf {
@@ -565,6 +589,26 @@ __attribute__((visibility("default"))) int catunit_newton_accept(int n, const do
   CATUNIT_TRY(finish());
   CATUNIT_TRY(dev_download(accept, da, n));
   return dev_download(prev_out, dpo, n);
+}
+
+// A: [64][T][T]; b, x: [64][2][T]; lu: [64][T][T]; meta: [64][2] (lu_kernel); T in 1 .. 9
+__attribute__((visibility("default"))) int catunit_lu(int T, const double* A, const double* b, double* lu, uint64_t* meta, double* x) {
+  if (!A || !b || !lu || !meta || !x || T < 1 || T > kin::MAXT) return EINVAL_;
+  static_assert(sizeof(uint64_t) == sizeof(double), "meta travels in a buffer of doubles");
+  Buf dA, db, dlu, dmeta, dx;
+  const size_t nA = (size_t)64 * T * T, nb = (size_t)64 * 2 * T;
+  CATUNIT_TRY(dev_upload(dA, A, nA));
+  CATUNIT_TRY(dev_upload(db, b, nb));
+  CATUNIT_TRY(dev_alloc(dlu, nA));
+  CATUNIT_TRY(dev_alloc(dmeta, 128));
+  CATUNIT_TRY(dev_alloc(dx, nb));
+  const size_t lds = lu_lds_bytes(T);
+  if (lds > 48 * 1024) CATUNIT_HIP(hipFuncSetAttribute((const void*)lu_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  lu_kernel<<<1, 64, lds>>>(dA.d(), db.d(), T, dlu.d(), (uint64_t*)dmeta.p, dx.d());
+  CATUNIT_TRY(finish());
+  CATUNIT_TRY(dev_download(lu, dlu, nA));
+  CATUNIT_HIP(hipMemcpy(meta, dmeta.p, 128 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return dev_download(x, dx, nb);
 }
 
 // doubles every row buffer (catunit_load_row, catunit_store_row) resp. window buffer (catunit_load_window, catunit_store_window) must hold

@@ -2,7 +2,7 @@
 
 Three parts:
   * the ctypes binding of libcatint_unittest.so (tests/csrc/primitives_harness.hip: every primitive of pnp_math.h, pnp_wave.h,
-    pnp_post.h, pnp_lane_common.h and pnp_lane_cols.h behind a kernel of its own),
+    pnp_post.h, pnp_lane_common.h and pnp_lane_cols.h, and the per-lane LU of pnp_kin.h, behind a kernel of its own),
   * multiprecision references (mpmath, 60 digits, rounded ONCE to fp64; where an error is measured in ulp the reference is the pair
     (hi, lo) with hi + lo the exact value to ~1e-32 relative, so that the error is taken against the exact value, not a rounded one),
   * the assertion helpers of tests/test_gpu_primitives.py -- pure functions of arrays -- and plain fp64 NumPy emulations of the
@@ -24,7 +24,8 @@ PS = (1, 2, 4, 8, 16)
 FN = {'fast_rcp': 0, 'fast_rcp2': 1, 'nrcp': 2, 'expm1_sc': 3, 'log1p_sc': 4, 'bernoulli': 5}
 SYMBOLS = ('catunit_scalar', 'catunit_edge_flux', 'catunit_wave_moves', 'catunit_read_lane', 'catunit_pick_blocked', 'catunit_wave_scan',
            'catunit_blocked_scan', 'catunit_blocked_scan_sum', 'catunit_tridiag', 'catunit_row_alloc', 'catunit_win_alloc', 'catunit_load_row',
-           'catunit_store_row', 'catunit_load_window', 'catunit_store_window', 'catunit_col_lanes', 'catunit_newton_rule', 'catunit_newton_accept')
+           'catunit_store_row', 'catunit_load_window', 'catunit_store_window', 'catunit_col_lanes', 'catunit_newton_rule', 'catunit_newton_accept',
+           'catunit_lu')
 
 # the bars (the header comments' own figures with the allowance of the design note, or its derivations)
 RCP1_BAR = 2 * 2.2e-15          # fast_rcp, relative
@@ -184,6 +185,15 @@ def store_window(P, mode, v, dst, nrec):
     v, dst = _in(v).reshape(64, P + 2), _in(dst).copy()
     _check(load_library().catunit_store_window(P, STORE_WINDOW[mode], _p(v), _p(dst), C.c_int(dst.size), C.c_int(nrec)), 'catunit_store_window')
     return dst
+
+
+def lu(T, A, b):
+    """pnp_kin.h's factor and substitute on one wave: A [64, T, T], b [64, 2, T] -> the factors [64, T, T], the packed pivot rows [64]
+    (uint64), the bad-pivot flags [64] (uint64: 0 / 1) and the solutions [64, 2, T]"""
+    A, b = _in(A).reshape(64, T, T), _in(b).reshape(64, 2, T)
+    f, meta, x = np.empty_like(A), np.empty((64, 2), np.uint64), np.empty_like(b)
+    _check(load_library().catunit_lu(T, _p(A), _p(b), _p(f), meta.ctypes.data_as(C.POINTER(C.c_uint64)), _p(x)), 'catunit_lu')
+    return f, meta[:, 0].copy(), meta[:, 1].copy(), x
 
 
 # ---- multiprecision references ------------------------------------------------------------------------------------------------------
@@ -954,3 +964,110 @@ def check_newton_accept(acc, prev_out, t, what=None):
     assert bad.size == 0, 'tuple %d %r (%s): accepted %r, the twin %r' % (bad[0], tuple(np.asarray(t)[bad[0]]), None if what is None else what[bad[0]], acc[bad[0]], want[bad[0]])
     bad = np.nonzero(np.asarray(prev_out) != wprev)[0]
     assert bad.size == 0, 'tuple %d (%s): upd_prev becomes %r, the twin %r' % (bad[0], None if what is None else what[bad[0]], prev_out[bad[0]], wprev[bad[0]])
+
+
+# ---- the per-lane LU of pnp_kin.h (factor, substitute): 64 systems of order T, one per lane ---------------------------------------------
+LU_TS = (1, 2, 5, 9)
+LU_SPECIAL = ('site row', 'tie', 'dead row', 'singular', 'infinite')          # lanes 0 .. 4; the other 59 are seeded random matrices
+LU_NONSINGULAR = np.array([k not in (3, 4) for k in range(64)])
+
+
+@functools.lru_cache(maxsize=None)
+def lu_cases(T):
+    """A [64, T, T], b [64, 2, T] (treat as read-only) and what the special lanes must show.  Entries of order 1 throughout.
+      lane 0  the steady state's matrix with its site row on top: A[0][0] = 5e-8 against a column of order 1 -- the rows must be exchanged
+      lane 1  column 0 holds its largest magnitude twice (rows i1 < i2, opposite signs): the comparison is strict, row i1 is the pivot row
+      lane 2  the identity row of a dead adsorbate as the last row
+      lane 3  exactly singular: upper triangular with a zero as its last diagonal entry -- the flag is set.  The entries above the diagonal
+              are negative and b is positive, so every solution entry is +inf and no stored word is a NaN (IEEE 754 leaves the sign and
+              payload of a generated NaN open, the equality of the test is bitwise)
+      lane 4  A[0][0] = +inf: the flag is set; the multipliers of step 0 are zeros, the first solution entry is a zero, no NaN either"""
+    rng = np.random.default_rng(9100 + T)
+    A = rng.uniform(-1.0, 1.0, (64, T, T))
+    b = rng.uniform(-1.0, 1.0, (64, 2, T))
+    A[0] = rng.uniform(0.5, 1.5, (T, T)) * rng.choice([-1.0, 1.0], (T, T))
+    A[0, 0, 0] = 5e-8
+    i1, i2 = (0, T - 1) if T < 3 else (1, T - 1)
+    A[1, :, 0] = rng.uniform(-0.5, 0.5, T)
+    A[1, i1, 0], A[1, i2, 0] = 1.25, (-1.25 if i2 != i1 else 1.25)
+    A[2, T - 1] = 0.0
+    A[2, T - 1, T - 1] = 1.0
+    A[3] = np.triu(-rng.uniform(0.5, 1.5, (T, T)), 1) + np.diag(rng.uniform(0.5, 1.5, T))
+    A[3, T - 1, T - 1] = 0.0
+    b[3] = rng.uniform(0.5, 1.5, (2, T))
+    A[4, 0, 0] = np.inf
+    return A, b, {'exchange': 0 if T == 1 else int(np.argmax(np.abs(A[0, :, 0]))), 'tie rows': (i1, i2)}
+
+
+def emul_lu(A, b, strict=True, contract=False):
+    """factor and substitute of pnp_kin.h replayed in fp64, lane by lane, in the header's operation order: every division and every
+    multiply-subtract as separately rounded IEEE operations.  Returns what lu() returns.  Mutants: strict=False takes the LAST of equal
+    magnitudes as the pivot; contract=True forms the multiply-subtracts of the elimination with one rounding"""
+    A, b = np.array(A, float), np.array(b, float)
+    T = A.shape[1]
+    pivs, bad = np.zeros(64, np.uint64), np.zeros(64, np.uint64)
+
+    def mulsub(c, f, v):
+        return np.float64(_FP.fma(-float(f), float(v), float(c))) if contract else c - f * v
+    with np.errstate(all='ignore'):
+        for lane in range(64):
+            J = A[lane]
+            word, flag = 0, False
+            for k in range(T):
+                p, best = k, abs(J[k, k])
+                for i in range(k + 1, T):
+                    v = abs(J[i, k])
+                    if v > best or (not strict and v == best):
+                        p, best = i, v
+                word |= p << (4 * k)
+                J[[k, p]] = J[[p, k]]
+                piv = J[k, k]
+                flag = flag or not (piv != 0.0 and np.isfinite(piv))
+                for i in range(k + 1, T):
+                    f = J[i, k] / piv
+                    J[i, k] = f
+                    for c in range(k + 1, T):
+                        J[i, c] = mulsub(J[i, c], f, J[k, c])
+            pivs[lane], bad[lane] = word, int(flag)
+            for x in b[lane]:
+                for k in range(T):
+                    p = (word >> (4 * k)) & 15
+                    x[k], x[p] = x[p], x[k]
+                for k in range(T):
+                    for i in range(k + 1, T):
+                        x[i] = x[i] - J[i, k] * x[k]
+                for k in range(T - 1, -1, -1):
+                    s = x[k]
+                    for c in range(k + 1, T):
+                        s = s - J[k, c] * x[c]
+                    x[k] = s / J[k, k]
+    return A, pivs, bad, b
+
+
+def lu_backward_error(A, x, b):
+    """the normwise backward error ||A x - b||_inf / (||A||_inf ||x||_inf + ||b||_inf) per lane and right-hand side [64, 2], the
+    residual formed in extended precision"""
+    L = np.longdouble
+    with np.errstate(all='ignore'):          # (the singular and the infinite lane come out as inf or NaN)
+        r = np.abs(np.einsum('lij,lqj->lqi', A.astype(L), x.astype(L)) - b.astype(L)).max(axis=2)
+        return (r / (np.abs(A).sum(axis=2).max(axis=1)[:, None] * np.abs(x).max(axis=2) + np.abs(b).max(axis=2))).astype(float)
+
+
+def lu_backward_bar(T):
+    """8 T 2^(T-1) 2^-53: the textbook bound of Gaussian elimination with partial pivoting at its worst-case growth 2^(T-1)"""
+    return 8.0 * T * 2.0 ** (T - 1) * 2.0 ** -53
+
+
+def check_lu(got, want):
+    """every stored word of the factors, the pivot words, the flags and the solutions, bit for bit.  Returns the number of words"""
+    words = 0
+    for name, g, w in zip(('factors', 'pivot rows', 'bad-pivot flag', 'solutions'), got, want):
+        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+        assert g.dtype == w.dtype and g.shape == w.shape, name
+        gb, wb = g.view(np.uint64), w.view(np.uint64)
+        bad = np.argwhere(gb != wb)
+        assert bad.size == 0, '%s: lane %d%s holds %r (0x%016x), the replay %r (0x%016x); %d words differ' % (
+            name, bad[0][0], '' if g.ndim == 1 else ' element %s' % (tuple(bad[0][1:]),), g[tuple(bad[0])], gb[tuple(bad[0])], w[tuple(bad[0])],
+            wb[tuple(bad[0])], len(bad))
+        words += g.size
+    return words

@@ -303,3 +303,20 @@ def test_newton_accept():
     acc, prev = U.newton_accept(t)
     report('newton_accept: %d tuples, %d accepted' % (len(what), acc.sum()))
     U.check_newton_accept(acc, prev, t, what)
+
+
+# ---- the per-lane LU of pnp_kin.h (factor, substitute): every stored word against the fp64 replay of the same operation order ---------
+@pytest.mark.parametrize('T', U.LU_TS)
+def test_lu_factor_and_substitute_bit_for_bit(T):
+    """One launch, one wave, 64 systems (U.lu_cases: the site row with 5e-8 on the diagonal, the tie, the dead row, the singular and the
+    infinite matrix, 59 random ones), two right-hand sides each.  No contraction in the header's functions, divisions and multiply-subtracts
+    single IEEE operations: the factors, the packed pivot rows, the bad-pivot flags and the solutions equal the replay's bit for bit."""
+    A, b, want = U.lu_cases(T)
+    got = U.lu(T, A, b)
+    ref = U.emul_lu(A, b)
+    diff = sum(int((np.ascontiguousarray(g).view(np.uint64) != np.ascontiguousarray(r).view(np.uint64)).sum()) for g, r in zip(got, ref))
+    report('lu, T = %d: %d of %d words differ from the replay; flags set in lanes %s; pivot row of step 0 in the site-row lane %d, in the tie lane %d' % (
+        T, diff, 64 * (T * T + 2 + 2 * T), np.nonzero(got[2])[0].tolist(), int(got[1][0]) & 15, int(got[1][1]) & 15))
+    assert U.check_lu(got, ref) == 64 * (T * T + 2 + 2 * T)
+    assert np.nonzero(got[2])[0].tolist() == [3, 4]
+    assert (int(got[1][0]) & 15) == want['exchange'] and (int(got[1][1]) & 15) == want['tie rows'][0]

@@ -57,13 +57,13 @@ def test_the_harness_builds_for_gfx950(libpath):
 def test_the_harness_includes_only_the_shared_headers():
     src = open(os.path.join(ROOT, 'tests', 'csrc', 'primitives_harness.hip')).read()
     quoted = sorted(os.path.basename(n) for n in re.findall(r'^\s*#\s*include\s+"([^"]+)"', src, flags=re.M))
-    assert quoted == ['pnp_lane_cols.h', 'pnp_lane_common.h', 'pnp_math.h', 'pnp_post.h', 'pnp_wave.h']
+    assert quoted == ['pnp_kin.h', 'pnp_lane_cols.h', 'pnp_lane_common.h', 'pnp_math.h', 'pnp_post.h', 'pnp_wave.h']
 
 
 def test_the_library_exports_exactly_the_declared_symbols(libpath):
     src = open(os.path.join(ROOT, 'tests', 'csrc', 'primitives_harness.hip')).read()
     declared = sorted(set(re.findall(r'\bint\s+(catunit_[a-z0-9_]+)\s*\(', src)))
-    assert declared == sorted(U.SYMBOLS) and len(declared) == 18
+    assert declared == sorted(U.SYMBOLS) and len(declared) == 19
     lib = C.CDLL(libpath)
     for s in declared:
         assert hasattr(lib, s), s
@@ -81,7 +81,7 @@ def test_every_kernel_is_in_namespace_catunit_and_every_tridiag_instance_is_ther
     assert len(tri) == 30 and tri <= compiled, sorted(tri - compiled)
     for fam, count in (('scalar_kernel', 6), ('newton_rule_kernel', 4), ('newton_accept_kernel', 1), ('col_lanes_kernel', 2), ('pick_blocked_kernel', 5), ('wave_scan_kernel', 2), ('blocked_scan_kernel', 10),
                        ('blocked_scan_sum_kernel', 5), ('load_row_kernel', 5), ('store_row_kernel', 10), ('load_window_kernel', 13),
-                       ('store_window_kernel', 14)):
+                       ('store_window_kernel', 14), ('lu_kernel', 1)):
         assert sum(K.family(n) == 'catunit::' + fam for n in compiled) == count, fam
 
 
@@ -119,6 +119,7 @@ def test_invalid_arguments_are_refused_before_any_device_call(libpath):
     assert lib.catunit_pick_blocked(5, p, p) == 1 and lib.catunit_blocked_scan(3, 0, p, p, p, p, 1) == 1
     assert lib.catunit_newton_rule(3, 1, *([p] * 11)) == 1 and lib.catunit_newton_rule(2, 0, *([p] * 11)) == 1      # N is 1, 2, 7 or 8
     assert lib.catunit_newton_accept(0, *([p] * 7)) == 1
+    assert lib.catunit_lu(0, *([p] * 5)) == 1 and lib.catunit_lu(10, *([p] * 5)) == 1                                # T is 1 .. 9
 
 
 # ---- the references --------------------------------------------------------------------------------------------------------------------
@@ -432,3 +433,34 @@ def test_newton_accept_twin_is_the_oracle_s_rule_and_every_mutant_fails():
         moved = t.copy()
         moved[:, 1:4] *= 1.0 + 1e-12 * rng.choice([-1.0, 1.0], (t.shape[0], 3))
         assert np.array_equal(U.newton_accept_twin(moved)[0], acc) and np.array_equal(U.newton_accept_twin(moved)[2], fired)
+
+
+# ---- the per-lane LU of pnp_kin.h: the replay itself ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize('T', U.LU_TS)
+def test_lu_replay_solves_its_systems_and_the_special_lanes_show_what_they_are_there_for(T):
+    """The fp64 replay of factor / substitute that the GPU test compares bit for bit: on the 62 non-singular lanes the normwise backward
+    error ||A x - b||_inf / (||A||_inf ||x||_inf + ||b||_inf) stays within 8 T 2^(T-1) 2^-53 (partial pivoting at its worst-case growth: a
+    loose bound, there to catch a wrong replay); the special lanes make the decisions they were built for; check_lu passes the replay
+    against itself and fails the replay with a non-strict pivot comparison and (T > 1) the one with contracted multiply-subtracts."""
+    A, b, want = U.lu_cases(T)
+    f, pivs, bad, x = U.emul_lu(A, b)
+    err = U.lu_backward_error(A, x, b)[U.LU_NONSINGULAR]
+    print('T = %d: worst backward error %.2e, bound %.2e' % (T, err.max(), U.lu_backward_bar(T)))
+    assert err.shape == (62, 2) and np.isfinite(x[U.LU_NONSINGULAR]).all() and err.max() <= U.lu_backward_bar(T)
+    assert np.array_equal(bad != 0, ~U.LU_NONSINGULAR)                        # the flag in the singular and the infinite lane, nowhere else
+    assert not np.isnan(f).any() and not np.isnan(x).any()                    # no stored word is a NaN: bitwise equality is defined
+    assert np.isposinf(x[3]).all() and (x[4, :, 0] == 0.0).all()
+    step0 = (pivs & np.uint64(15)).astype(int)
+    assert step0[0] == want['exchange'] and (T == 1 or step0[0] != 0)          # 5e-8 is not the pivot
+    i1, i2 = want['tie rows']
+    assert step0[1] == i1 and abs(A[1, i1, 0]) == abs(A[1, i2, 0]) == np.abs(A[1, :, 0]).max()
+    assert T == 1 or (A[2, T - 1] == np.eye(T)[T - 1]).all()
+    for k in range(T, 16):                                                    # nothing above the T fields of four bits
+        assert not (pivs >> np.uint64(4 * k)).any()
+    assert U.check_lu((f, pivs, bad, x), U.emul_lu(A, b)) == 64 * (T * T + 2 + 2 * T)
+    if T > 1:
+        assert fails(U.check_lu, U.emul_lu(A, b, strict=False), (f, pivs, bad, x))
+        assert fails(U.check_lu, U.emul_lu(A, b, contract=True), (f, pivs, bad, x))
+    # a lane's result is its own: the random lanes alone, in other lanes, give the same words
+    A2, b2 = np.roll(A, 7, axis=0), np.roll(b, 7, axis=0)
+    U.check_lu(tuple(np.roll(v, 7, axis=0) for v in (f, pivs, bad, x)), U.emul_lu(A2, b2))
