@@ -999,6 +999,76 @@ class PnpSolver(object):
         out['elasticity'] = el
         return out
 
+    def get_relaxation(self, nmodes=3, subspace=8, iterations=12, lanes=None, rtol=1e-8, profiles=False, start=None, seed=0, max_waves=0):
+        """The slowest relaxation modes of the stationary state this handle holds (include/catint_modes.h): perturbations of the state
+        decay as exp(-lambda t) with J v = lambda S v, J the Jacobian of the stationary residual and S the storage matrix of
+        get_response.  For every lane of `lanes` (None: all, in order; repeats allowed) the device runs `iterations` passes of subspace
+        iteration on J^-1 S with `subspace` columns (1 .. 8, at most N (nx - 1)) from `start` [subspace][N+1][nx] (None: standard normal
+        numbers of RandomState(seed), the same for every lane); the small eigenproblem is solved here.  Returns a dict: 'rates'
+        [n][nmodes] complex, 1/s, ascending in |lambda| (complex pairs are legitimate: J is not symmetric); 'time_constants' = 1 / Re
+        lambda (inf where Re lambda = 0); 'residual' [n][nmodes], the relative residual of each Ritz pair; 'converged' = residual <=
+        rtol; 'stable' [n] (object): True when every converged rate has Re lambda > 0, False when one has not, None where none
+        converged; 'status' [n] (0; 1: failed pivot check or non-finite number; 2: the lane's solver status was not 0 or an input is not
+        finite, outputs NaN; 3: Gram-Schmidt breakdown, e.g. linearly dependent start vectors); 'ritz', 'gram' [n][subspace][subspace],
+        the device's B = Q^T W and G = (W - Q B)^T (W - Q B) of the last pass; with profiles 'dc' [n][nmodes][N][nx] and 'dphi'
+        [n][nmodes][nx], the mode shapes Q s_j (complex, each scaled to unit Euclidean norm).  nmodes is cut to subspace.  Lanes whose
+        status is not 0 have NaN rates and residuals and converged False.  Medium, tables and potentials are the ones this solver was
+        given, with the rules of get_response: after scf_cycle the wall table is left out; after a set_batch with another batch size
+        the wall table must be set again (ValueError)."""
+        from . import _modes
+        o = self._obs
+        wall = None if o['explicit_kinetics'] else o['wall']
+        if wall is not None and o['wall_stale']:
+            raise ValueError('get_relaxation: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall table '
+                             'whose rate constants were not recorded for this batch: call set_wall_kinetics again')
+        if o['phiM'] is None:
+            raise ValueError('get_relaxation: no batch was set')
+        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+            raise ValueError('get_relaxation: lane index outside [0, %d)' % self.B)
+        m, N, nx = int(subspace), self.N, self.nx
+        if not 1 <= m <= min(_modes.MAX_SUBSPACE, N * (nx - 1)):
+            raise ValueError('get_relaxation: subspace = %d outside [1, %d]' % (m, min(_modes.MAX_SUBSPACE, N * (nx - 1))))
+        if not 1 <= int(iterations) <= _modes.MAX_ITERATIONS:
+            raise ValueError('get_relaxation: iterations = %d outside [1, %d]' % (iterations, _modes.MAX_ITERATIONS))
+        if int(nmodes) < 1:
+            raise ValueError('get_relaxation: nmodes < 1')
+        q0 = _modes.default_start(m, N, nx, seed) if start is None else np.asarray(start, float)
+        if q0.shape != (m, N + 1, nx):
+            raise ValueError('get_relaxation: start has shape %r, the call needs %r' % (q0.shape, (m, N + 1, nx)))
+        if getattr(self, '_mode_solver', None) is None:
+            self._mode_solver = _modes.ModeSolver(o['device'])
+        raw = self._mode_solver.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], q0, subspace=m,
+                                      iterations=iterations, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
+                                      stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], wall=wall,
+                                      fields=['ritz', 'gram'] + (['basis'] if profiles else []), max_waves=max_waves)
+        n, k = len(idx), min(int(nmodes), m)
+        rates, res = np.full((n, k), np.nan + 0j), np.full((n, k), np.nan)
+        stable = np.full(n, None, dtype=object)
+        if profiles:
+            dc, dphi = np.full((n, k, N, nx), np.nan + 0j), np.full((n, k, nx), np.nan + 0j)
+        for i in range(n):
+            if raw['status'][i] != 0:
+                continue
+            theta, s, r = _modes.ritz_pairs(raw['ritz'][i], raw['gram'][i])
+            with np.errstate(divide='ignore', invalid='ignore'):
+                rates[i] = 1.0 / theta[:k]
+            res[i] = r[:k]
+            ok = np.isfinite(res[i]) & (res[i] <= rtol)
+            if ok.any():
+                stable[i] = bool((rates[i][ok].real > 0).all())
+            if profiles:
+                v = np.einsum('jke,jm->mke', raw['basis'][i], s[:, :k])
+                v = v / np.sqrt((np.abs(v) ** 2).sum(axis=(1, 2)))[:, None, None]
+                dc[i], dphi[i] = v[:, :N], v[:, N]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            tau = np.where(rates.real == 0, np.inf, 1.0 / np.where(rates.real == 0, 1.0, rates.real))
+        out = {'rates': rates, 'time_constants': tau, 'residual': res, 'converged': np.isfinite(res) & (res <= rtol), 'stable': stable,
+               'status': raw['status'], 'ritz': raw['ritz'], 'gram': raw['gram']}
+        if profiles:
+            out['dc'], out['dphi'] = dc, dphi
+        return out
+
     def get_status(self):
         st = np.zeros(self.B, np.int32)
         self._check(self._lib.pnp_get_status(self._h, _iptr(st)))

@@ -87,6 +87,14 @@ DRC_LIB = os.path.join(LIB_DIR, 'libcatint_drc.so')
 DRC_SOURCES = ['catdrc.hip']
 DRC_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_drc.h')]
 
+# eleventh library (include/catint_modes.h): the relaxation modes of a stationary state -- a subspace iteration on J^-1 S per operating
+# point, every pass one team block elimination with the subspace as carried right-hand sides, records and a substitution to the bulk, all
+# passes inside one launch.  A library of its own as the nine before it
+MODES_DIR = os.path.join(CSRC, 'modes')
+MODES_LIB = os.path.join(LIB_DIR, 'libcatint_modes.so')
+MODES_SOURCES = ['catmodes.hip']
+MODES_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_modes.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -244,6 +252,15 @@ def drc_needs_build():
 def build_drc_library(force=False, verbose=False):
     """catint_amd/csrc/drc into catint_amd/lib/libcatint_drc.so"""
     return _build_unit(DRC_DIR, DRC_SOURCES, DRC_HEADERS, DRC_LIB, force, verbose)
+
+
+def modes_needs_build():
+    return _unit_needs_build(MODES_DIR, MODES_SOURCES, MODES_HEADERS, MODES_LIB)
+
+
+def build_modes_library(force=False, verbose=False):
+    """catint_amd/csrc/modes into catint_amd/lib/libcatint_modes.so"""
+    return _build_unit(MODES_DIR, MODES_SOURCES, MODES_HEADERS, MODES_LIB, force, verbose)
 
 
 def unittest_needs_build():

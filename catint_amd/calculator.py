@@ -101,6 +101,12 @@ class Calculator(object):
         self.sensitivities = None         # the dict of get_sensitivities of the last such run()
         if self._sensitivity_option() is not None and not self.physical:
             raise CalculatorError("tp.newton['sensitivities'] is part of the physical mode (calc=\"comsol\")")
+        # physical mode, opt-in: tp.newton['relaxation'] = True | {arguments of PnpSolver.get_relaxation} -- after the sweep's solve, run()
+        # takes the slowest relaxation modes of every lane on the device (include/catint_modes.h) and adds them to
+        # tp.alldata[i]['system']['relaxation'].  Off by default: nothing else changes.
+        self.relaxation = None            # the dict of get_relaxation of the last such run()
+        if self._relaxation_option() is not None and not self.physical:
+            raise CalculatorError("tp.newton['relaxation'] is part of the physical mode (calc=\"comsol\")")
         # roughness factor: every wall flux the COMSOL model prescribes is j_i = RF*flux_factor*flux_i (comsol_model.py:1000, :1134)
         self.RF = float(self.tp.system.get('RF', 1.0)) if self.physical else 1.0
         # the reference hands system['flow rate'] (a number or a COMSOL expression) to the convection velocity tds.cdm1 "u"
@@ -735,6 +741,8 @@ class Calculator(object):
             raise CalculatorError("tp.newton['response'] is part of the physical mode (calc=\"comsol\")")
         if self._sensitivity_option() is not None and not self.physical:
             raise CalculatorError("tp.newton['sensitivities'] is part of the physical mode (calc=\"comsol\")")
+        if self._relaxation_option() is not None and not self.physical:
+            raise CalculatorError("tp.newton['relaxation'] is part of the physical mode (calc=\"comsol\")")
         keys = list(tp.descriptors.keys())
         lanes = tp.alldata_names
         B = len(lanes)
@@ -777,6 +785,8 @@ class Calculator(object):
                     self.response = s.get_response(omega=self._response_option())
                 if self._sensitivity_option() is not None:
                     self.sensitivities = s.get_sensitivities(self._sensitivity_option())
+                if self._relaxation_option() is not None:
+                    self.relaxation = s.get_relaxation(**self._relaxation_option())
             cout = cfin.reshape(1, B, tp.nspecies * tp.nx)
             if derived is not None:
                 self.status = status
@@ -785,6 +795,7 @@ class Calculator(object):
                 self._alldata_balance()
                 self._alldata_response()
                 self._alldata_sensitivities()
+                self._alldata_relaxation()
                 return cout
         else:
             cout, status, (v, g, l) = self.integrate_pnp_batch(c0, pb, vz, flux)
@@ -795,6 +806,7 @@ class Calculator(object):
             self._alldata_balance()
             self._alldata_response()
             self._alldata_sensitivities()
+            self._alldata_relaxation()
         return cout
 
     def _response_option(self):
@@ -862,6 +874,35 @@ class Calculator(object):
                 'dsurface_potential': res['dphi_surface'][b] * chain,
                 'dsurface_charge': res['dsigma'][b] * chain,
                 'elasticity': {k: v[b].copy() for k, v in res['elasticity'].items()}}
+
+    RELAXATION_ARGUMENTS = ('nmodes', 'subspace', 'iterations', 'rtol', 'profiles', 'start', 'seed', 'max_waves')
+
+    def _relaxation_option(self):
+        """tp.newton['relaxation']: None when the option is off, otherwise the keyword arguments of PnpSolver.get_relaxation ({} for True)"""
+        opt = (getattr(self.tp, 'newton', None) or {}).get('relaxation')
+        if opt is None or opt is False:
+            return None
+        if opt is True:
+            return {}
+        if not isinstance(opt, dict):
+            raise CalculatorError("tp.newton['relaxation'] is True or a dict of the arguments of get_relaxation")
+        unknown = sorted(set(opt) - set(self.RELAXATION_ARGUMENTS))
+        if unknown:
+            raise CalculatorError("tp.newton['relaxation']: unknown argument %s (known: %s)" % (', '.join(unknown), ', '.join(self.RELAXATION_ARGUMENTS)))
+        return dict(opt)
+
+    def _alldata_relaxation(self):
+        """tp.newton['relaxation']: self.relaxation into tp.alldata[i]['system']['relaxation'] -- 'rates' [nmodes] (complex, 1/s, the slowest
+        first), 'time_constants' [nmodes] (s), 'residual' [nmodes], 'converged' [nmodes], 'stable' (True, False, or None where no mode
+        converged) and 'status'; with profiles 'dc' [nmodes][N][nx] and 'dphi' [nmodes][nx].  Like the keys of _alldata_balance these are
+        an extension: the reference's field contract has no counterpart for them."""
+        if self._relaxation_option() is None or self.relaxation is None:
+            return
+        res = self.relaxation
+        for b in range(len(res['status'])):
+            d = {k: res[k][b].copy() for k in ('rates', 'time_constants', 'residual', 'converged') + tuple(k for k in ('dc', 'dphi') if k in res)}
+            d['stable'], d['status'] = res['stable'][b], int(res['status'][b])
+            self.tp.alldata[b]['system']['relaxation'] = d
 
     def _alldata_balance(self):
         """balance_on_device: the per-species picture of self.balance into tp.alldata -- per species 'flux' [nx-1], 'reaction_source' [nx],
