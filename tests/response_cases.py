@@ -113,6 +113,104 @@ def case_E(nx):
                 reactions=[([3, 5], [4], 1e3, 1.5e4)], wall=([3], nu, [1e-6], [-0.1 * F * BETA], [0.0]))
 
 
+def case_G(nx):
+    """N = 4, every term of the physics and every shape of a table entry: a dimerisation (a repeated reactant), an empty side with a
+    rate, a catalyst with a repeat and a dead backward side, four entries on both sides with a fourfold repeat; at the wall two
+    reactions driven by the same species, a zeroth-order one that still depends on the potential, and alpha = 0"""
+    q, cb = np.array([1.0, -1.0, 1.0, -1.0]) * F, [60.0, 50.0, 10.0, 20.0]
+    lam = debye(q, cb)
+    reactions = [([0, 0], [2], 2e4, 5e5), ([], [0, 1], 2e5, 1e2), ([1, 3, 3], [2, 1], 5.0, 0.0), ([0, 1, 2, 3], [3, 3, 3, 3], 1e-2, 1e-3)]
+    wall = ([1, -1, 1], [[0.0, -1.0, 0.5, 0.0], [1.0, 0.0, 0.0, -2.0], [0.0, 0.0, -1.0, 1.0]], [2e-6, 1e-5, 1e-6],
+            np.array([-0.15, 0.1, 0.0]) * F * BETA, [0.002, 0.0, 0.0])
+    return Case('G nx=%d' % nx, E_D[:4], q, cb, graded_mesh(20.0 * lam, lam / 6.0, nx), -0.3, CS=0.2, radii=[4e-10, 3e-10, 3.5e-10, 3e-10],
+                velocity=-1e-3, reactions=reactions, wall=wall)
+
+
+def case_G8(nx):
+    """N = 8 with both tables full: 16 reactions of 0 .. 4 entries per side (every fifth without a backward rate, reactions 3 and 10
+    without a forward one; reaction 3 is ([0, 5, 5], [], 0, 2e5), a constant source), 8 wall reactions (the first of zeroth order, the
+    second and third driven by the same species), drawn from a seeded generator in this order; the zeroth-order wall reaction takes
+    alpha = 0.1 F beta and no saturation, whatever was drawn"""
+    q = E_Z * F
+    lam = debye(q, E_CB)
+    rng = np.random.RandomState(8)
+    reactions = []
+    for r in range(16):
+        nl, nr = r % 5, (3 * r + 1) % 5
+        lhs = [int(v) for v in rng.randint(0, 8, nl)]
+        rhs = [int(v) for v in rng.randint(0, 8, nr)]
+        kf, kr = 1e5 / 30.0 ** nl, 2e5 / 30.0 ** nr
+        if r % 5 == 2:
+            kr = 0.0
+        if r % 7 == 3:
+            kf = 0.0
+        reactions.append((lhs, rhs, kf, kr))
+    sp = [int(v) for v in rng.randint(-1, 8, 8)]
+    sp[0] = -1
+    sp[1] = sp[2] = 3
+    nu = rng.choice([-2., -1., 0., 1., 2.], (8, 8))
+    al = rng.choice([-0.15, 0.0, 0.1], 8) * F * BETA
+    al[0] = 0.1 * F * BETA
+    sat = rng.choice([0.0, 0.002, 0.05], 8)
+    sat[0] = 0.0          # (drawn 0.002: pnp_set_wall_rate_law refuses a saturation on a zeroth-order reaction)
+    k = rng.uniform(2e-7, 2e-6, 8)
+    return Case('G8 nx=%d' % nx, E_D, q, E_CB, graded_mesh(40.0 * lam, lam / 6.0, nx), -0.3, CS=0.2, radii=[3.5e-10] * 8, velocity=-1e-3,
+                reactions=reactions, wall=(sp, nu, k, al, sat))
+
+
+# Entries that leave every row of case G as it is: a reaction without rates, a reaction whose species stands on both sides alone (net is
+# identically 0), and a wall reaction (species, nu, alpha, saturation) whose rate constant is 0 on every lane
+NULL_REACTIONS = [([0, 1], [3, 3], 0.0, 0.0), ([2], [2], 3e3, 7e2)]
+NULL_WALL = (0, [1.0, -1.0, 0.0, 2.0], -0.1 * F * BETA, 0.01)
+
+
+def table_properties(s, case, outputs, moves, wall=True):
+    """The exact properties of the reaction and wall tables in one of the team-elimination libraries.  s: a solver that holds converged
+    states of `case` (case G); outputs(): a dict of the library's output arrays at the handle's present tables.  The tables are
+    replaced after the state is fixed, and the exact state is put back before every call.  Appending an entry of NULL_REACTIONS or
+    (wall=True) NULL_WALL changes no bit of any output; dropping the case's first reaction changes every output named in `moves`
+    (a table that is silently ignored would pass the first half).  The handle is left as it was."""
+    n = s.B
+    c, phi = s.get_state(derived=False)
+
+    def run():
+        s.set_lanes(list(range(n)), c, phi)
+        return outputs()
+
+    def differing(a, b):
+        assert sorted(a) == sorted(b)
+        return sorted(k for k in a if not np.array_equal(a[k], b[k], equal_nan=True))
+
+    def set_wall(extra):
+        sp, nu, k, al, sat = case.wall
+        kk = np.tile(np.asarray(k, float), (n, 1))
+        if extra:
+            s.set_wall_kinetics(list(sp) + [NULL_WALL[0]], [list(row) for row in nu] + [NULL_WALL[1]], np.hstack([kk, np.zeros((n, 1))]),
+                                list(al) + [NULL_WALL[2]], list(sat) + [NULL_WALL[3]])
+        else:
+            s.set_wall_kinetics(sp, nu, kk, al, sat)
+    want = run()
+    assert all(np.isfinite(want[k]).all() for k in moves)
+    try:
+        for extra in NULL_REACTIONS:
+            s.set_reactions(case.reactions + [extra])
+            assert not differing(run(), want), extra
+        s.set_reactions(case.reactions)
+        if wall:
+            set_wall(True)
+            assert not differing(run(), want), 'wall'
+            set_wall(False)
+        s.set_reactions(case.reactions[1:])
+        moved = differing(run(), want)
+        assert set(moves) <= set(moved), (moves, moved)
+    finally:
+        s.set_reactions(case.reactions)
+        if wall:
+            set_wall(False)
+        s.set_lanes(list(range(n)), c, phi)
+    assert not differing(run(), want)
+
+
 def small(N, nx, stern=False, steric=False):
     """The first N species of case E's lists (N = 1: a single cation against a Dirichlet wall), a short graded grid"""
     q, cb = E_Z[:N] * F, E_CB[:N]

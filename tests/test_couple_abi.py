@@ -8,7 +8,7 @@ transport and tests/kinetics_ref.py as the kinetics (convergence in the stated n
 mixing loop), and with fakes (freezing, the retry ladder, failed lanes, result keys, the excluded combinations).
 
 Measured (CPU): the tangent against central differences at the relative flux step 0.1: 5.5e-8 (bound 5e-7); against
-response_ref's flux response: 8e-13; the Newton loop: 2 steps at the eight potentials of the end-to-end case (residuals 1, 5e-6 ..
+response_ref's flux response: 8e-13 (case G with its general reaction table, nx = 21: 1.2e-7 and 9e-13); the Newton loop: 2 steps at the eight potentials of the end-to-end case (residuals 1, 5e-6 ..
 7e-4, <= 1.1e-9), 3 / 6 / 6 steps at -0.5 / -0.7 / -0.9 V; its fluxes against the mixing loop's (23 iterations): 8e-9."""
 import ctypes as C
 import os
@@ -43,10 +43,27 @@ def state_F():
     return (case,) + case.solve()
 
 
+@pytest.fixture(scope='module')
+def state_G():
+    """case G (tests/response_cases.py: general reaction tables) without its wall table, about the prescribed fluxes of the sensitivity
+    tests"""
+    case = RC.case_G(21)
+    case.wall, case.flux = None, np.array([0.0, -1e-6, 1e-6, 0.0])
+    return (case,) + case.solve()
+
+
 def test_the_tangent_is_the_derivative_of_the_oracle_s_solutions(state_F):
     """Central differences of stationary solves at the relative flux step 0.1 tests/test_response_abi.py found usable (smaller steps
     measure the rounding of the solves), with the bound measured there: 5e-7."""
-    case, p, c, phi = state_F
+    tangent_against_differences(state_F)
+
+
+def test_the_tangent_of_case_G_is_the_derivative_of_the_oracle_s_solutions(state_G):
+    tangent_against_differences(state_G)
+
+
+def tangent_against_differences(state):
+    case, p, c, phi = state
     T = CR.tangent_banded(p, c, phi)
     fd = np.zeros_like(T)
     h = 0.1 * 1e-6
@@ -58,12 +75,20 @@ def test_the_tangent_is_the_derivative_of_the_oracle_s_solutions(state_F):
         fd[:case.N, j] = (ca[:, 0] - cb[:, 0]) / (2.0 * h)
         fd[case.N, j] = (pa[0] - pb[0]) / (2.0 * h)
     err = max(CR.rel(fd[:, j], T[:, j]) for j in range(case.N))
-    print('central differences against the tangent, relative flux step 0.1: %.2e' % err)
+    print('%s: central differences against the tangent, relative flux step 0.1: %.2e' % (case.name, err))
     assert err <= 5e-7
 
 
 def test_every_column_is_the_flux_response_of_the_response_reference(state_F):
-    case, p, c, phi = state_F
+    columns_against_the_response_reference(state_F)
+
+
+def test_every_column_of_case_G_is_the_flux_response_of_the_response_reference(state_G):
+    columns_against_the_response_reference(state_G)
+
+
+def columns_against_the_response_reference(state):
+    case, p, c, phi = state
     for method in CR.METHODS:
         T = CR.METHODS[method](p, c, phi)
         worst = 0.0

@@ -11,7 +11,8 @@ Tolerance: per output and system, 10 x the disagreement of the reference's two m
 Schur recursion) on that system, not below 1e-11 -- the project's rule from tests/test_gpu_response.py.  That disagreement must itself
 stay below 1e-8 (asserted).  The worst ratios device error / tolerance are printed by every test.  Measured on the MI355X (also in
 DESIGN.md section 7i): 0.90 at N = 2, nx = 19 (dc_surface: 1.0e-11 against 1.15e-11), every other small case at most 0.36, case F 0.28,
-case E 0.17, with reference disagreements up to 1.6e-11; the tangent equals the flux response of libcatint_response bit for bit (asserted); the
+case E 0.17, with reference disagreements up to 1.6e-11; the general reaction tables of cases G and G8 (without their wall tables):
+G 0.05 / 0.11 at nx = 5 / 21, G8 0.09 / 0.10 at nx = 7 / 34, reference disagreements up to 4.1e-12 (its two tangents agree to 1.6e-12); the tangent equals the flux response of libcatint_response bit for bit (asserted); the
 end-to-end case takes 2 Newton steps and 3 transport solves where the mixing loop takes 23 iterations, the fluxes equal to 8.1e-9.
 Everything that can be exact is asserted bit for bit."""
 import numpy as np
@@ -173,6 +174,25 @@ def test_case_F_every_term_of_the_physics():
 
 def test_case_E_block_size_nine():
     check(without_wall(RC.case_E(34)))
+
+
+G_CASES = {'G nx=5': lambda: RC.case_G(5), 'G nx=21': lambda: RC.case_G(21), 'G8 nx=7': lambda: RC.case_G8(7), 'G8 nx=34': lambda: RC.case_G8(34)}
+
+
+@pytest.mark.parametrize('name', sorted(G_CASES))
+def test_general_reaction_tables(name):
+    """Cases G and G8 (tests/response_cases.py) without their wall tables: every shape of an entry of the reaction table in the rows of
+    the Jacobian the tangent is eliminated from"""
+    check(without_wall(G_CASES[name]()), rf=1.5)
+
+
+def test_table_entries_without_effect_change_no_bit_and_a_dropped_reaction_does():
+    """tests/response_cases.py: table_properties (the library takes no wall table)"""
+    case = without_wall(RC.case_G(21))
+    s, phis, lin = prepared(case)
+    flux = np.zeros((B, case.N))
+    kin = kin_of(lin, flux)
+    RC.table_properties(s, case, lambda: call(s, flux, kin), ['T_c', 'T_phi', 'dflux', 'flux_new', 'dc_surface', 'dphi_surface'], wall=False)
 
 
 def test_the_cases_reach_every_instance():

@@ -14,6 +14,8 @@ Measured on the MI355X, worst device error / tolerance: Ritz values 0.19 (N = 1,
 (N = 1, nx = 19 and N = 5, nx = 3), every other case <= 0.10; projector 0.81 (N = 2, nx = 3; disagreement 8.9e-10), 0.79 (N = 5, nx = 3),
 0.71 (N = 6, nx = 3), every nx = 19 case <= 0.07, case F 0.015, case E 0.008.  The disagreement of the methods is up to 8.8e-9 on the
 three- and four-point grids, where the rates are decades apart (cond(W) up to 5e7), and at most 5e-12 from nx = 19 on.
+The general reaction and wall tables of cases G and G8: Ritz values 0.021 / 0.040 (G, nx = 5 / 21: 7 and 3 converged pairs per point)
+and 0.005 / 0.002 (G8, nx = 7 / 34: 6 pairs), projector 0.099 / 0.100 and 0.021 / 0.002, no breakdown, disagreements up to 3.2e-12.
 Everything that can be exact is asserted bit for bit."""
 import numpy as np
 import pytest
@@ -174,6 +176,26 @@ def test_case_F_every_term_of_the_physics_with_its_wall_table():
 
 def test_case_E_block_size_nine():
     check(RC.case_E(34), None)
+
+
+FLUX_G = np.array([0.0, -1e-6, 1e-6, 0.0])
+G_CASES = {'G nx=5': lambda: (RC.case_G(5), FLUX_G), 'G nx=21': lambda: (RC.case_G(21), FLUX_G),
+           'G8 nx=7': lambda: (RC.case_G8(7), None), 'G8 nx=34': lambda: (RC.case_G8(34), None)}
+
+
+@pytest.mark.parametrize('name', sorted(G_CASES))
+def test_general_reaction_and_wall_tables(name):
+    """Cases G and G8 (tests/response_cases.py): every shape of an entry of the reaction and wall tables in the rows of the Jacobian the
+    iteration solves with"""
+    check(*G_CASES[name]())
+
+
+def test_table_entries_without_effect_change_no_bit_and_a_dropped_reaction_does():
+    """tests/response_cases.py: table_properties, on the Ritz matrices and the basis of five passes"""
+    case = RC.case_G(21)
+    s, phis, lin = prepared(case, FLUX_G)
+    start = _modes.default_start(subspace(case), case.N, case.nx, 0)
+    RC.table_properties(s, case, lambda: raw(s, start, iterations=5), ALL)
 
 
 def test_the_cases_reach_every_instance():

@@ -12,7 +12,9 @@ unknown's profile, and every scalar, scaled by its own maximum).  The factor 10 
 matrix in another order.  That disagreement must itself stay below 1e-8, or the case tests nothing (asserted).  The worst ratios
 device error / tolerance are printed by every test.  Measured on the MI355X (also in DESIGN.md section 7g): case F 0.59 (phiM) and 0.65
 (flux), case E 0.32 / 0.36 / 0.67 at nx = 34 / 130 / 514 with reference disagreements up to 3.8e-10 (F) and 3.1e-9 (E), the small cases
-of every block size at most 0.37, Debye-Hueckel at most 0.005.
+of every block size at most 0.37, Debye-Hueckel at most 0.005; the general reaction and wall tables of cases G and G8: G 0.24 / 0.11
+at nx = 5 / 21, G8 0.40 / 0.76 at nx = 7 / 34 (point 2, omega = 8.1e5 / s: 7.95e-12 against 1.05e-11), with reference disagreements
+up to 4.9e-11 (G) and 2.2e-10 (G8).
 Everything that can be exact is asserted bit for bit."""
 import os
 
@@ -138,6 +140,24 @@ def test_case_E_block_size_nine(nx):
         check(RC.case_E(nx), ('flux', 3), profiles=False)
 
 
+G_CASES = {'G nx=5': lambda: RC.case_G(5), 'G nx=21': lambda: RC.case_G(21), 'G8 nx=7': lambda: RC.case_G8(7), 'G8 nx=34': lambda: RC.case_G8(34)}
+
+
+@pytest.mark.parametrize('name', sorted(G_CASES))
+def test_general_reaction_and_wall_tables(name):
+    """Cases G and G8 (tests/response_cases.py): repeated reactants, up to four entries per side, empty sides, sides without a rate,
+    a catalyst, several reactions into one dR[j], both tables full; wall reactions that share a driving species, of zeroth order, without
+    a potential dependence, with a saturation.  nx = 5: the first grid on which every step of the row walk runs with reactions; nx = 7:
+    the smallest that gives G8 several interior block rows.  Real and complex instances, with and without profiles, both perturbations.
+    tests/test_response_abi.py shows that every entry of the tables moves these results by at least 1e6 tolerances."""
+    case = G_CASES[name]()
+    for perturbation in ('phiM', ('flux', 1)):
+        for omega in ([0.0], case.omegas()):
+            full = check(case, perturbation, omega=omega, profiles=True)
+            scal = check(case, perturbation, omega=omega, profiles=False)
+            assert same(scal, full, list(RR.SCALARS) + ['status'])
+
+
 @pytest.mark.parametrize('N, nx, stern, steric', [(1, 3, False, False), (2, 4, True, False), (2, 66, False, True), (3, 9, True, True),
                                                   (4, 12, False, False), (5, 11, True, True), (6, 10, False, True), (7, 13, True, False),
                                                   (8, 7, False, False)])
@@ -186,6 +206,24 @@ def test_any_number_of_waves_gives_the_same_bits(name):
     want = call(s, omega=[0.0], profiles=False)
     for waves in (1, 2):
         assert same(call(s, omega=[0.0], profiles=False, max_waves=waves), want), waves
+
+
+def test_table_entries_without_effect_change_no_bit_and_a_dropped_reaction_does():
+    """tests/response_cases.py: table_properties, in the complex instance with profiles and the real one without, for both perturbations"""
+    case = RC.case_G(21)
+    s, _, _ = prepared(case)
+
+    def outputs():
+        out = {}
+        for pert in ('phiM', ('flux', 1)):
+            cx = call(s, omega=case.omegas(), perturbation=pert, profiles=True)
+            re = call(s, omega=[0.0], perturbation=pert)
+            out.update({'%s complex %s' % (pert, k): v for k, v in cx.items()})
+            out.update({'%s real %s' % (pert, k): v for k, v in re.items()})
+        return out
+    moves = ['%s %s %s' % (pert, inst, k) for pert in ('phiM', ('flux', 1)) for inst in ('complex', 'real') for k in RR.SCALARS]
+    moves += ['%s complex %s' % (pert, k) for pert in ('phiM', ('flux', 1)) for k in ('dc', 'dphi')]
+    RC.table_properties(s, case, outputs, moves)
 
 
 def test_lane_subsets_permutations_and_permuted_frequencies():

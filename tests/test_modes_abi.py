@@ -22,12 +22,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAIRS = {'catmodes_params': 'CatmodesParams', 'catmodes_outputs': 'CatmodesOutputs'}
 INSTANCES = {'catmodes::modes_kernel<%d, 8>' % nb for nb in range(2, 10)}
 FLUX_F = np.array([0.0, -1e-6, 1e-6])
+FLUX_G = np.array([0.0, -1e-6, 1e-6, 0.0])          # case G: general reaction and wall tables
 SUBSPACE, ITERATIONS = 8, 12          # the defaults of PnpSolver.get_relaxation
 
 
 def cpu_cases():
     return {'N=2 nx=33 stern': (RC.small(2, 33, stern=True), None), 'N=3 nx=48 stern steric': (RC.small(3, 48, stern=True, steric=True), None),
-            'F': (RC.case_F(), FLUX_F), 'E': (RC.case_E(34), None)}
+            'F': (RC.case_F(), FLUX_F), 'E': (RC.case_E(34), None), 'G': (RC.case_G(21), FLUX_G)}
 
 
 _states = {}

@@ -1,7 +1,8 @@
 """libcatint_response without a GPU (the method of tests/test_equil_abi.py).  The NumPy restatement of include/catint_response.h
 (tests/response_ref.py, which tests/test_gpu_response.py compares the device with) is checked against known answers: the Debye-Hueckel
 capacitance to second order in the grid, Kornyshev's bell-shaped capacitance of the steric double layer, the derivative of the oracle's
-own stationary solutions, and its omega -> 0 limit.  The library builds for gfx950 and exports what the header declares, the ctypes
+own stationary solutions (also with the general reaction and wall tables of case G), and its omega -> 0 limit; and the cases of the
+device tests are shown to see every entry of their tables.  The library builds for gfx950 and exports what the header declares, the ctypes
 mirrors have the compiler's layouts, every validation error is returned before any device call, the kernels compiled into it are exactly
 the thirty-two instances listed here and none of the other five libraries gained one.  The calculator's opt-in path is driven with fake
 solvers."""
@@ -82,17 +83,33 @@ def stacked(r):
     return np.concatenate([r['dc'], r['dphi'][None]])
 
 
-def test_the_tangent_is_the_derivative_of_the_oracle_s_solutions(state_F):
-    case, p, c, phi = state_F
+@pytest.fixture(scope='module')
+def state_G():
+    """case G (tests/response_cases.py): general reaction and wall tables"""
+    case = RC.case_G(21)
+    return (case,) + case.solve()
+
+
+def tangent_against_differences(state):
+    case, p, c, phi = state
     prof = stacked(RR.response(p, c, phi))
     errs = []
     for h in (1e-3, 1e-4):
         _, ca, pa = case.solve(case.phiM + h, start=(c, phi))
         _, cb, pb = case.solve(case.phiM - h, start=(c, phi))
         errs.append(RR.rel_rows(np.concatenate([ca - cb, (pa - pb)[None]]) / (2.0 * h), prof))
-    print('central differences against the tangent at h = 1e-3, 1e-4: %.2e %.2e' % tuple(errs))
+    print('%s: central differences against the tangent at h = 1e-3, 1e-4: %.2e %.2e' % ((case.name,) + tuple(errs)))
     assert 50.0 <= errs[0] / errs[1] <= 200.0      # the h^2 law
     assert errs[1] <= 5e-7
+
+
+def test_the_tangent_is_the_derivative_of_the_oracle_s_solutions(state_F):
+    tangent_against_differences(state_F)
+
+
+def test_the_tangent_of_case_G_is_the_derivative_of_the_oracle_s_solutions(state_G):
+    """... through a repeated reactant, an empty side, a catalyst, four entries per side and three wall reactions"""
+    tangent_against_differences(state_G)
 
 
 def test_the_flux_tangent_is_the_derivative_of_the_oracle_s_solutions():
@@ -102,22 +119,43 @@ def test_the_flux_tangent_is_the_derivative_of_the_oracle_s_solutions():
     close to linear in the flux, so the bound of the phiM check, 5e-7, is asserted at the relative step 0.1, where the rounding share is
     5e-8; the figures of the smaller steps are printed."""
     case = RC.case_F(flux=[0.0, 1e-6, 0.0])
+    flux_tangent_against_differences(case)
+
+
+def flux_tangent_against_differences(case):
+    base = case.flux.copy()
     p, c, phi = case.solve()
     prof = stacked(RR.response(p, c, phi, perturbation=('flux', 1)))
     errs = []
     for rel in (1e-1, 1e-3, 1e-4):
-        h = rel * 1e-6
-        _, ca, pa = case.solve(start=(c, phi), flux=[0.0, 1e-6 + h, 0.0])
-        _, cb, pb = case.solve(start=(c, phi), flux=[0.0, 1e-6 - h, 0.0])
-        errs.append(RR.rel_rows(np.concatenate([ca - cb, (pa - pb)[None]]) / (2.0 * h), prof))
-    print('flux: central differences against the tangent at relative steps 1e-1, 1e-3, 1e-4: %.2e %.2e %.2e' % tuple(errs))
+        e = np.zeros(case.N)
+        e[1] = rel * 1e-6
+        _, ca, pa = case.solve(start=(c, phi), flux=base + e)
+        _, cb, pb = case.solve(start=(c, phi), flux=base - e)
+        errs.append(RR.rel_rows(np.concatenate([ca - cb, (pa - pb)[None]]) / (2.0 * e[1]), prof))
+    print('%s, flux: central differences against the tangent at relative steps 1e-1, 1e-3, 1e-4: %.2e %.2e %.2e' % ((case.name,) + tuple(errs)))
     assert errs[0] <= 5e-7
+
+
+def test_the_flux_tangent_of_case_G_is_the_derivative_of_the_oracle_s_solutions():
+    """The same check and bound about the prescribed flux [0, 1e-6, 0, 0] of case G"""
+    case = RC.case_G(21)
+    case.flux = np.array([0.0, 1e-6, 0.0, 0.0])
+    flux_tangent_against_differences(case)
 
 
 def test_the_complex_solve_tends_to_the_real_one(state_F):
     """At omega = 1e-6 / tau_D the real part is the static response to 1e-9 (its correction is second order in omega tau), and the
     imaginary part is first order: below omega tau_D, as no relaxation time of the diffusion problem exceeds L^2 / D_min"""
-    case, p, c, phi = state_F
+    complex_against_real(state_F)
+
+
+def test_the_complex_solve_of_case_G_tends_to_the_real_one(state_G):
+    complex_against_real(state_G)
+
+
+def complex_against_real(state):
+    case, p, c, phi = state
     real = RR.response(p, c, phi)
     for method in RR.METHODS:
         cx = RR.response(p, c, phi, 1e-6 / case.tau_D, method=method)
@@ -131,11 +169,66 @@ def test_the_complex_solve_tends_to_the_real_one(state_F):
 
 def test_the_two_solution_methods_agree(state_F):
     """... to the rounding of the case: what tests/test_gpu_response.py builds its tolerance from must itself stay below 1e-8"""
-    case, p, c, phi = state_F
+    methods_agree(state_F)
+
+
+def test_the_two_solution_methods_agree_on_case_G(state_G):
+    methods_agree(state_G)
+
+
+def methods_agree(state):
+    case, p, c, phi = state
     for w in case.omegas():
         for pert in ('phiM', ('flux', 1)):
             d = RR.disagreement(RR.response(p, c, phi, w, pert, 'banded'), RR.response(p, c, phi, w, pert, 'elimination'))
             assert d < 1e-8, (w, pert, d)
+
+
+# ---- the power of the general-table cases ------------------------------------------------------------------------------------------
+G_CASES = {'G nx=5': lambda: RC.case_G(5), 'G nx=21': lambda: RC.case_G(21), 'G8 nx=7': lambda: RC.case_G8(7), 'G8 nx=34': lambda: RC.case_G8(34)}
+POWER = 1000.0
+
+
+def only_live_side_is_empty(reaction):
+    """a reaction none of whose sides with a rate holds a species: a constant source, whose part of the Jacobian is zero by construction"""
+    lhs, rhs, kf, kr = reaction
+    return not ((kf != 0.0 and len(lhs)) or (kr != 0.0 and len(rhs)))
+
+
+@pytest.mark.parametrize('name', sorted(G_CASES))
+def test_the_device_cases_can_see_every_entry_of_their_tables(name):
+    """What tests/test_gpu_response.py (and its siblings, which eliminate the same rows) can notice: at the case's largest potential and
+    omega = 0, with the state held fixed, the phiM response without one reaction, or without one wall reaction, differs from the full one
+    by at least POWER = 1000 times the tolerance the device test uses there (10 x the disagreement of the two methods, not below 1e-11).
+    A reaction whose only live side is empty (reaction 3 of G8) is exempt, its Jacobian part being zero; its 'kr' column of
+    tests/sens_ref.py must not vanish instead.  Measured (tolerances 1.0e-11 .. 1.8e-10): the weakest entries are those of G8 at nx = 34, wall
+    reaction 0 (1.5e5 tolerances) and, among the reactions, 3.1e5; at nx = 7 every entry of G8 moves the result by at least 2.3e6
+    tolerances, and every entry of G by at least 7.9e6."""
+    import copy
+    from tests import sens_ref as SR
+    case = G_CASES[name]()
+    p, c, phi = case.solve()
+    full = RR.response(p, c, phi, 0.0, 'phiM', 'banded')
+    tol = max(10.0 * RR.disagreement(full, RR.response(p, c, phi, 0.0, 'phiM', 'elimination')), 1e-11)
+    moved = {}
+    for table in ('reactions', 'wall_kinetics'):
+        entries = getattr(p, table)
+        for r in range(len(entries)):
+            if table == 'reactions' and only_live_side_is_empty(case.reactions[r]):
+                col = SR.sensitivities(p, c, phi, [('kr', r)])
+                assert np.abs(col['dc_surface']).max() > 0.0 and np.abs(col['dcurrent']).max() > 0.0, (name, r)
+                continue
+            less = copy.copy(p)
+            setattr(less, table, entries[:r] + entries[r + 1:])
+            moved[(table, r)] = RR.disagreement(RR.response(less, c, phi, 0.0, 'phiM', 'banded'), full) / tol
+    exempt = [r for r in range(len(case.reactions)) if only_live_side_is_empty(case.reactions[r])]
+    assert exempt == ([3] if name.startswith('G8') else [])
+    assert len(moved) == len(p.reactions) - len(exempt) + len(p.wall_kinetics)
+    weakest = min(moved, key=moved.get)
+    print('%s: tolerance %.1e; the weakest entry, %s %d, moves the response by %.1e tolerances; reactions at least %.1e, wall reactions %.1e'
+          % (name, tol, weakest[0], weakest[1], moved[weakest], min(v for k, v in moved.items() if k[0] == 'reactions'),
+             min(v for k, v in moved.items() if k[0] == 'wall_kinetics')))
+    assert moved[weakest] >= POWER, (weakest, moved[weakest])
 
 
 # ---- the library -------------------------------------------------------------------------------------------------------------------

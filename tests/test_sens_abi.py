@@ -26,13 +26,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAIRS = {'catsens_params': 'CatsensParams', 'catsens_outputs': 'CatsensOutputs'}
 INSTANCES = {'catsens::sens_kernel<%d, 8>' % nb for nb in range(2, 10)}
 FLUX_F = np.array([0.0, -1e-6, 1e-6])
+FLUX_G = np.array([0.0, -1e-6, 1e-6, 0.0])
 # the size of a step where the parameter itself is 0 (case E has no convection, and most of its prescribed fluxes are 0): the values
-# case F carries
-ZERO_SCALE = {'velocity': 1e-3, 'flux': 1e-6}
+# case F carries (reaction 2 of case G has no backward rate)
+ZERO_SCALE = {'velocity': 1e-3, 'flux': 1e-6, 'kr': 1.2e5}
 
 
 def every_kind(p):
-    return (['phiM', 'stern_capacitance', 'velocity', ('wall_k', 0), ('kf', 0), ('kr', 0)]
+    """... with the rate constants of every reaction and of every wall reaction"""
+    return (['phiM', 'stern_capacitance', 'velocity'] + [('wall_k', r) for r in range(len(p.wall_kinetics))]
+            + [(kind, r) for r in range(len(p.reactions)) for kind in ('kf', 'kr')]
             + [(kind, j) for kind in ('flux', 'c_bulk', 'D') for j in range(p.N)])
 
 
@@ -86,22 +89,37 @@ def state_E():
     return case, p, c, phi
 
 
-@pytest.mark.parametrize('name', ['F', 'E'])
-def test_the_right_hand_sides_are_the_derivatives_of_the_oracle_s_residual(name, state_F, state_E):
+@pytest.fixture(scope='module')
+def state_G():
+    """case G (tests/response_cases.py): general reaction and wall tables"""
+    case = RC.case_G(21)
+    p, c, phi = case.solve(flux=FLUX_G)
+    return case, p, c, phi
+
+
+@pytest.mark.parametrize('name', ['F', 'E', 'G'])
+def test_the_right_hand_sides_are_the_derivatives_of_the_oracle_s_residual(name, state_F, state_E, state_G):
     """(a) Central differences at relative step 1e-6 (of ZERO_SCALE where the parameter is 0), max-norm relative to the largest entry of
     the column.  Measured: at most 1.4e-10 for every kind whose derivative does not go through the edge fluxes' convection term
     (the prescribed fluxes, whose step is 1e-12: 4.8e-9); the three 'D' columns of case F (velocity -1e-3 m/s) 1.4e-6, 3.8e-6, 1.4e-6
     (case E, without convection: 1.1e-10) and the 'velocity' column 2.2e-6 in both cases.
     Those are the difference quotient's own rounding, not the formula's: the quotient divides differences of edge fluxes whose
     two terms are 1e2 .. 1e3 and cancel, by a step of 1e-6 D = 2e-15 (eps 1e3 / 2e-15 = 1e2 against entries of 4e7).  (b) below
-    confirms the same columns to 1e-8 through re-solved states.  Bound: 5 x the worst value measured, 3.8e-6."""
-    case, p, c, phi = state_F if name == 'F' else state_E
+    confirms the same columns to 1e-8 through re-solved states.  Bound: 5 x the worst value measured, 3.8e-6.
+    Case G (every rate constant of its four reactions and three wall reactions): the residual's rows hold reaction terms of 0.2 that
+    cancel, and a relative step of 1e-6 in a prescribed flux, a 'kr' or a 'wall_k' moves them by 1e-13 .. 1e-12, so at that step the
+    quotient measures its own rounding: flux 6.5e-5, kr 8.1e-6, wall_k 6.3e-6, kf 4.2e-7, falling as 1 / step to 2.5e-12, 1.8e-11,
+    1.2e-12, 3.2e-13 at the relative step 1.  The residual is linear in these four kinds, so the quotient has no truncation error at
+    any step: case G takes them at the relative step 1e-2 and then meets the bounds of F and E unchanged (measured: flux 5.1e-9,
+    kr 3.0e-9, wall_k 3.8e-10, kf 3.0e-11; D 3.0e-6, velocity 1.1e-6, every other kind at most 1.8e-10)."""
+    case, p, c, phi = {'F': state_F, 'E': state_E, 'G': state_G}[name]
     worst = {}
     for spec in every_kind(p):
         kind, index = SR.split(spec)
         r = SR.rhs(p, c, phi, p.flux, kind, index)
         v = value(p, kind, index)
-        d = 1e-6 * (abs(v) if v != 0 else ZERO_SCALE[kind])
+        rel = 1e-2 if name == 'G' and kind in ('flux', 'kf', 'kr', 'wall_k') else 1e-6
+        d = rel * (abs(v) if v != 0 else ZERO_SCALE[kind])
         fd = -(PH.residual(moved(case, p.flux, kind, index, d), c, phi, c, np.inf)
                - PH.residual(moved(case, p.flux, kind, index, -d), c, phi, c, np.inf)) / (2 * d)
         scale = np.abs(r).max()
@@ -119,7 +137,17 @@ def test_the_reference_is_the_derivative_of_the_oracle_s_solutions(state_F):
     """(b) Case F with flux = [0, -1e-6, 1e-6]: du_0 against central differences of re-solved stationary states, per parameter the
     smallest error over relative steps 1e-2, 1e-3, 1e-4.  Measured: flux columns 4.3e-7, 3.9e-7, 5.2e-7; D 1e-8; every other
     parameter at most 2.3e-9.  Bound 2e-6."""
-    case, p, c, phi = state_F
+    reference_against_resolved_states(state_F)
+
+
+def test_the_reference_of_case_G_is_the_derivative_of_the_oracle_s_solutions(state_G):
+    """(b) Case G with flux = [0, -1e-6, 1e-6, 0], every rate constant of its tables among the parameters: the same steps and bound.
+    Measured: flux columns up to 9.7e-7, ('kr', 3) 1.0e-7, the wall rate constants up to 5.6e-8, every other rate constant at most 5.2e-9"""
+    reference_against_resolved_states(state_G)
+
+
+def reference_against_resolved_states(state):
+    case, p, c, phi = state
     specs = every_kind(p)
     ref = SR.sensitivities(p, c, phi, specs, p.flux)
     worst = {}
@@ -137,14 +165,14 @@ def test_the_reference_is_the_derivative_of_the_oracle_s_solutions(state_F):
                 ends.append(np.concatenate([c2[:, 0], [phi2[0]]]))
             best = min(best, np.abs((ends[0] - ends[1]) / (2 * d) - mine).max() / np.abs(mine).max())
         worst[spec] = best
-    print('case F: du_0 against differences of re-solved states: %s' % {str(k): '%.1e' % v for k, v in worst.items()})
+    print('case %s: du_0 against differences of re-solved states: %s' % (case.name, {str(k): '%.1e' % v for k, v in worst.items()}))
     assert max(worst.values()) <= 2e-6, worst
 
 
-@pytest.mark.parametrize('name', ['F', 'E'])
-def test_the_control_columns_are_those_of_the_response_and_coupling_references(name, state_F, state_E):
+@pytest.mark.parametrize('name', ['F', 'E', 'G'])
+def test_the_control_columns_are_those_of_the_response_and_coupling_references(name, state_F, state_E, state_G):
     """(c)"""
-    case, p, c, phi = state_F if name == 'F' else state_E
+    case, p, c, phi = {'F': state_F, 'E': state_E, 'G': state_G}[name]
     specs = ['phiM'] + [('flux', j) for j in range(p.N)]
     for method in SR.METHODS:
         ref = SR.sensitivities(p, c, phi, specs, p.flux, method)
@@ -179,8 +207,8 @@ def test_a_direction_in_bulk_composition_is_the_weighted_sum_of_its_columns(stat
     assert np.abs(fd - r).max() <= 1e-9
 
 
-def test_the_two_methods_agree_far_inside_the_condition_of_the_device_tests(state_F, state_E):
-    for case, p, c, phi in (state_F, state_E):
+def test_the_two_methods_agree_far_inside_the_condition_of_the_device_tests(state_F, state_E, state_G):
+    for case, p, c, phi in (state_F, state_E, state_G):
         specs = every_kind(p)
         dis = SR.disagreement(SR.sensitivities(p, c, phi, specs, p.flux, 'banded'), SR.sensitivities(p, c, phi, specs, p.flux, 'schur'))
         assert max(v.max() for v in dis.values()) < 1e-9, dis
