@@ -57,8 +57,8 @@ struct pnp_handle {
   int32_t* bdf_acc = nullptr;               // ... and per-lane iteration counts / status summed over the launches of one pnp_step call
   double* phi_old2 = nullptr;               // predictor: the potential of the time level before the current one
   double* vol_dev = nullptr;                // ... and the ion volumes for its crowding guard
-  std::vector<uint8_t> lane_hist;           // per lane: c_old2 (phi_old2) holds the level before its current state (cleared by an upload
-                                            // and a change of time_order / predictor for every lane, by a stationary solve or patch for
+  std::vector<uint8_t> lane_hist;           // per lane: c_old2 (phi_old2) holds the level before its current state (cleared by an upload,
+                                            // pnp_set_potential and a change of time_order / predictor for every lane, by a stationary solve or patch for
                                             // the lanes it touched: their next step is backward Euler)
   ReactionSides* rs_dev = nullptr;          // the table flattened per reaction side (lane kernels)
   int rs_max_exponent = 0;
@@ -1463,6 +1463,9 @@ int pnp_set_potential(pnp_handle* h, const double* phi) {
   if (!h->newton) return fail(h, PNP_EINVAL, "pnp_set_potential: the handle was not created with PNP_METHOD_NEWTON");
   if (!h->have_batch) return fail(h, PNP_ESTATE, "pnp_set_potential: call pnp_set_batch first");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
+  // (the rows replaced are no continuation of the level phi_old2 holds: every lane's next BDF2 / predictor step starts over, as after
+  // pnp_set_lanes -- the predictor would otherwise extrapolate through a potential the caller has just replaced)
+  std::fill(h->lane_hist.begin(), h->lane_hist.end(), (uint8_t)0);
   const size_t w = (size_t)h->a.nx * sizeof(double), dp = (size_t)h->a.ldx * sizeof(double);
   HIP_TRY(h, hipMemcpy2DAsync(h->v, dp, phi, w, w, (size_t)h->B, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));

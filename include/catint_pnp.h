@@ -305,7 +305,9 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel /* [
 /* Newton iterations each lane spent in the most recent pnp_step / pnp_solve_stationary call, summed over its
  * timesteps; a solve that hit maxit counts maxit+1. */
 int pnp_get_newton_iterations(pnp_handle* h, int32_t* iters /* [B] */);
-/* Overwrite the potential rows (initial guess of the physical mode), phi[B][nx]. */
+/* Overwrite the potential rows (initial guess of the physical mode), phi[B][nx].  The call overwrites every lane, so it ends every
+ * lane's BDF2 / predictor history, as pnp_set_lanes does for the lanes it patches: the next pnp_step starts with a backward-Euler step
+ * from the state and the rows given here, exactly as on a handle that was given them right after pnp_set_batch. */
 int pnp_set_potential(pnp_handle* h, const double* phi);
 /* Overwrite the state (concentrations c[n][N][nx], potential phi[n][nx]) of the n lanes lanes[0..n) and leave every other lane, the
  * iteration counters, the bulk values and the status flags alone: how a lane recovered elsewhere -- on a finer continuation ramp or
