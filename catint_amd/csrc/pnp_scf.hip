@@ -54,7 +54,8 @@ __global__ __launch_bounds__(256) void scf_pre_kernel(const ScfArgs A) {
   for (int r = 0; r < A.n_wk; ++r) {
     const double K = A.wk_k[b * PNP_MAX_WALL_REACTIONS + r];
     const int sp = A.wk_species[r];
-    const double cs = sp >= 0 ? fmax(s[sp], 0.0) : 1.0;
+    // max(c, 0) that keeps a NaN (fmax would turn it into 0 and the lane would go on with a zero flux instead of failing)
+    const double cs = sp >= 0 ? (s[sp] < 0.0 ? 0.0 : s[sp]) : 1.0;
     // rate law of pnp_set_wall_rate_law, evaluated explicitly: Langmuir saturation in the mixed surface concentration,
     // Butler-Volmer factor in the Stern-layer drop of the PREVIOUS transport solve (the state the reference hands CatMAP,
     // catmap_wrapper.py: surface potential of the last COMSOL run).  alpha = K_sat = 0: g = cs exactly.

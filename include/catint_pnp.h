@@ -272,7 +272,19 @@ int pnp_solve_surface(pnp_handle* h, const double* flux, int32_t nsteps, double*
  * round trip per iteration: the host reads one counter every `check_every` iterations.
  * The caller runs the first iteration(s) (first transport solve, with whatever continuation it needs) and hands over the
  * loop state together with a CONVERGED transport state on the device: a lane whose later solve fails is put back to the
- * state of its last converged solve.  All arrays of pnp_scf_state are host arrays, read at entry, written back at exit. */
+ * state of its last converged solve.  All arrays of pnp_scf_state are host arrays, read at entry, written back at exit.
+ * What the arrays hold at exit (tests/test_gpu_scf.py):
+ *  - a lane that left the loop: the values of its last iteration -- surface_concentration is the transport's answer,
+ *    surface_concentration_old the mixed iterate the kinetics saw, surface_pH taken from that iterate;
+ *  - a lane whose last solve did not converge: surface_concentration = -1.0 in every species, active = 1 (it never leaves: the
+ *    fallback hands the kinetics the same iterate again), surface_concentration_old / flux / current_density_old of that last
+ *    attempt, accuracy 0, surface_potential / surface_efield and the device state those of its last CONVERGED solve -- the state
+ *    it was handed over with if none converged;
+ *  - a lane with a non-finite input (rate constant, surface concentration of a reacting species) or a solve that ended in NaN:
+ *    failed = 1, active = 0, its other entries and its device state are not defined; no other lane is affected;
+ *  - a lane inactive at entry: every entry, its device state, status and Newton iteration counter unchanged;
+ *  - istep >= max_iter: nothing runs, nothing changes, *iterations = istep.
+ * *iterations is the last iteration number at whose start a lane was active, not max_iter, whatever check_every is. */
 typedef struct pnp_scf_params {
   int32_t struct_size;   /* = sizeof(pnp_scf_params) */
   int32_t istep;         /* iterations already done (>= 1) */
