@@ -33,7 +33,7 @@ SYMBOLS = [
     'pnp_set_batch', 'pnp_set_flux', 'pnp_set_pb', 'pnp_step', 'pnp_integrate', 'pnp_mol_rhs', 'pnp_integrate_dopri5', 'pnp_integrate_dop853', 'pnp_integrate_rkc', 'pnp_get_state',
     'pnp_get_surface', 'pnp_get_status', 'pnp_synchronize', 'pnp_timer_start', 'pnp_timer_stop',
     'pnp_device_bytes', 'pnp_row_pitch', 'pnp_step_row_chunks', 'pnp_set_newton', 'pnp_solve_stationary', 'pnp_get_newton_iterations',
-    'pnp_set_potential', 'pnp_set_convection', 'pnp_set_option', 'pnp_get_lane_order', 'pnp_autotune', 'pnp_autotune_name', 'pnp_autotune_default', 'pnp_tune_placement', 'pnp_set_lanes', 'pnp_set_lane_mask', 'pnp_set_wall_kinetics', 'pnp_set_wall_rate_law', 'pnp_set_grid', 'pnp_solve_surface', 'pnp_scf_cycle', 'pnp_get_device_view',
+    'pnp_set_potential', 'pnp_set_convection', 'pnp_set_option', 'pnp_get_lane_order', 'pnp_autotune', 'pnp_autotune_name', 'pnp_autotune_default', 'pnp_tune_placement', 'pnp_set_lanes', 'pnp_set_lane_mask', 'pnp_set_wall_kinetics', 'pnp_set_wall_rate_law', 'pnp_set_grid', 'pnp_solve_surface', 'pnp_scf_cycle', 'pnp_scf_cycle_fn', 'pnp_get_device_view',
     'pnp_set_lanes_device',
 ]
 
@@ -85,6 +85,19 @@ class PnpScfState(C.Structure):
         'surface_concentration', 'surface_concentration_old', 'flux', 'current_density_old', 'mix', 'accuracy',
         'surface_pH', 'surface_potential', 'surface_efield')] + [(n, C.POINTER(C.c_int32)) for n in (
             'step_to_check', 'active', 'failed')]
+
+
+class PnpScfDevice(C.Structure):
+    """pnp_scf_device: what the flux function of pnp_scf_cycle_fn is handed (device addresses)"""
+    _fields_ = [
+        ('struct_size', C.c_int32), ('nspecies', C.c_int32), ('istep', C.c_int32), ('reserved', C.c_int32), ('batch', C.c_int64),
+        ('surface_concentration', C.c_void_p), ('surface_potential', C.c_void_p), ('surface_efield', C.c_void_p),
+        ('surface_pH', C.c_void_p), ('active', C.c_void_p), ('flux', C.c_void_p), ('stream', C.c_void_p),
+    ]
+
+
+# pnp_scf_flux_fn
+PnpScfFluxFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(PnpScfDevice))
 
 
 _lib = None
@@ -169,6 +182,8 @@ def load_library():
     lib.pnp_solve_surface.restype = C.c_int
     lib.pnp_scf_cycle.argtypes = [vp, C.POINTER(PnpScfParams), dp, dp, C.POINTER(PnpScfState), ip]
     lib.pnp_scf_cycle.restype = C.c_int
+    lib.pnp_scf_cycle_fn.argtypes = [vp, C.POINTER(PnpScfParams), dp, dp, C.POINTER(PnpScfState), C.c_void_p, C.c_void_p, ip]
+    lib.pnp_scf_cycle_fn.restype = C.c_int
     for name in ('pnp_set_newton', 'pnp_solve_stationary', 'pnp_get_newton_iterations', 'pnp_set_potential'):
         getattr(lib, name).restype = C.c_int
     for name in ('pnp_set_species', 'pnp_set_reactions', 'pnp_set_batch', 'pnp_set_flux', 'pnp_set_pb', 'pnp_step',
@@ -443,11 +458,13 @@ class PnpSolver(object):
         return cs, vs, es, st
 
     def scf_cycle(self, state, istep, max_iter, tau_scf, faraday, nel=None, nprod=None, species_H=-1, species_OH=-1,
-                  check_every=8):
+                  check_every=8, flux_fn=None, user=None):
         """Device SCF loop (pnp_scf_cycle) from iteration istep+1 on.  `state`: dict of the loop arrays
         ('surface_concentration', 'surface_concentration_old', 'flux', 'current_density_old' [B][N]; 'mix', 'accuracy',
         'surface_pH', 'surface_potential', 'surface_efield' [B]; 'step_to_check', 'active', 'failed' [B] int) -- updated in
-        place (fresh contiguous arrays are put back into the dict).  Returns the last iteration number that had active lanes."""
+        place (fresh contiguous arrays are put back into the dict).  Returns the last iteration number that had active lanes.
+        flux_fn, user: the addresses (two integers) of a pnp_scf_flux_fn and of its argument; with flux_fn the wall fluxes come from that
+        function (pnp_scf_cycle_fn) and the wall table is not consulted."""
         B, N = self.B, self.N
         st = PnpScfState()
         for name, ctype in PnpScfState._fields_:
@@ -464,7 +481,11 @@ class PnpSolver(object):
         nel = None if nel is None else _f64(nel, (N,))
         nprod = None if nprod is None else _f64(nprod, (N,))
         it = C.c_int32(0)
-        self._check(self._lib.pnp_scf_cycle(self._h, C.byref(p), _dptr(nel), _dptr(nprod), C.byref(st), C.byref(it)))
+        if flux_fn is None:
+            self._check(self._lib.pnp_scf_cycle(self._h, C.byref(p), _dptr(nel), _dptr(nprod), C.byref(st), C.byref(it)))
+        else:
+            self._check(self._lib.pnp_scf_cycle_fn(self._h, C.byref(p), _dptr(nel), _dptr(nprod), C.byref(st), C.c_void_p(int(flux_fn)),
+                                                   C.c_void_p(None if user is None else int(user)), C.byref(it)))
         # the loop updated the wall fluxes on the device: the recorded table is no longer theirs.  And its solves took the wall reactions
         # through those fluxes (explicitly, from the mixed surface state), not through the wall table: the state it leaves conserves
         # state['flux'] alone

@@ -95,6 +95,14 @@ MODES_LIB = os.path.join(LIB_DIR, 'libcatint_modes.so')
 MODES_SOURCES = ['catmodes.hip']
 MODES_HEADERS = _TEAM_HEADERS + [os.path.join(_INCLUDE, 'catint_modes.h')]
 
+# twelfth library (include/catint_scfkin.h): the wall fluxes of the microkinetic model inside the device SCF loop -- the function
+# pnp_scf_cycle_fn calls once per iteration, one launch, the coverages of every lane kept on the device as the next start.  A library of
+# its own as the ten before it: the kinetics library is pinned to one kernel and six symbols (tests/test_kinetics_abi.py)
+SCFKIN_DIR = os.path.join(CSRC, 'scfkin')
+SCFKIN_LIB = os.path.join(LIB_DIR, 'libcatint_scfkin.so')
+SCFKIN_SOURCES = ['catscfkin.hip']
+SCFKIN_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_scfkin.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -261,6 +269,15 @@ def modes_needs_build():
 def build_modes_library(force=False, verbose=False):
     """catint_amd/csrc/modes into catint_amd/lib/libcatint_modes.so"""
     return _build_unit(MODES_DIR, MODES_SOURCES, MODES_HEADERS, MODES_LIB, force, verbose)
+
+
+def scfkin_needs_build():
+    return _unit_needs_build(SCFKIN_DIR, SCFKIN_SOURCES, SCFKIN_HEADERS, SCFKIN_LIB)
+
+
+def build_scfkin_library(force=False, verbose=False):
+    """catint_amd/csrc/scfkin into catint_amd/lib/libcatint_scfkin.so"""
+    return _build_unit(SCFKIN_DIR, SCFKIN_SOURCES, SCFKIN_HEADERS, SCFKIN_LIB, force, verbose)
 
 
 def unittest_needs_build():

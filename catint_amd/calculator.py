@@ -329,7 +329,7 @@ class Calculator(object):
             raise CalculatorError('set_surface_kinetics and set_microkinetics exclude each other: one kinetic model per calculator')
         self.surface_kinetics = list(reactions)
 
-    def set_microkinetics(self, model, site_density=None, potential_drop='stern', gamma=None, scf='mixing', rate_control=False):
+    def set_microkinetics(self, model, site_density=None, potential_drop='stern', gamma=None, scf='mixing', rate_control=False, device_loop=False):
         """Mean-field surface microkinetics as the kinetic half of run_scf_cycle (physical mode only): model is a
         catint_amd.microkinetics.MeanFieldModel over this transport's species (or the dict of its tables()).  With it set,
         run_scf_cycle() without a callback runs its host loop with the device kinetics (include/catint_kinetics.h) as the callback: the
@@ -346,7 +346,15 @@ class Calculator(object):
         control (include/catint_drc.h) at the final surface state of every lane; result['rate_control'] and
         tp.alldata[i]['system']['rate_control'] hold 'drc' [R][N], 'tdrc' [S][N], 'status', 'residual' -- the intrinsic coefficients, at
         a fixed surface state -- and under scf='newton' also 'drc_apparent', 'tdrc_apparent', those of the coupled electrode
-        (PnpSolver.get_rate_control)."""
+        (PnpSolver.get_rate_control).
+        device_loop=True (default False: no call of the library is made and the result has no other key; needs scf='mixing'):
+        run_scf_cycle() runs its host loop until every transport solve of an iteration >= 2 converged and every active lane has its
+        coverages, then hands the loop to the device (pnp_scf_cycle_fn with the function of include/catint_scfkin.h): the kinetics of
+        the active lanes run between the loop's bookkeeping and its transport solve, warm-started from coverages that stay on the
+        device, with no host round trip per iteration; converged lanes leave the batch.  As with the wall table's device loop
+        'history' holds the host iterations only, and with a transport_fn or a roughness factor other than 1 the loop stays on the
+        host.  The result then also carries 'kinetic_iterations' [B] (Newton iterations of the kinetics on the device) and
+        'kinetic_calls' [B]."""
         if model is None:
             self.microkinetics = None
             return
@@ -358,6 +366,8 @@ class Calculator(object):
             raise CalculatorError('set_surface_kinetics and set_microkinetics exclude each other: one kinetic model per calculator')
         if potential_drop not in ('stern', 'full'):
             raise CalculatorError("potential_drop is 'stern' or 'full'")
+        if device_loop and scf != 'mixing':
+            raise CalculatorError("device_loop=True needs scf='mixing': the Newton iteration on the wall fluxes is driven from the host")
         tables = model.tables() if hasattr(model, 'tables') else dict(model)
         N = self.tp.nspecies
         nu, of = np.asarray(tables['nu']), np.asarray(tables['order_f'])
@@ -371,6 +381,8 @@ class Calculator(object):
             self.microkinetics['scf'] = 'newton'
         if rate_control:
             self.microkinetics['rate_control'] = True
+        if device_loop:
+            self.microkinetics['device_loop'] = True
 
     def _rate_control_solver(self):
         """The device context of the rate-control analysis (tests replace it)"""
@@ -411,6 +423,11 @@ class Calculator(object):
         """The device context of the microkinetic solves (tests replace it)"""
         from . import _kinetics
         return _kinetics.KineticsSolver(self.device)
+
+    def _scf_kinetics(self):
+        """The device context of the kinetics inside the device SCF loop (tests replace it)"""
+        from . import _scfkin
+        return _scfkin.ScfKinetics(self.device)
 
     def _apply_surface_kinetics(self, solver, phiM, lanes=None):
         rx = getattr(self, 'surface_kinetics', None)
@@ -1283,6 +1300,44 @@ class Calculator(object):
                 active = active & ~bad & ((acc > self.tau_scf) | (sc < 0.0).any(axis=1))
                 if kin_solver is not None:
                     coverage['active'] = active.copy()
+                if (kin_solver is not None and micro.get('device_loop') and transport_fn is None and active.any() and istep < max_iter
+                        and istep >= 2 and not restart and self.RF == 1.0 and not (active & coverage['unsolved']).any()):
+                    # the rest of the loop on the device: the kinetics between the loop's bookkeeping and its transport solve, the
+                    # coverages of this iteration as the first start
+                    sk = self._scf_kinetics()
+                    try:
+                        sk.begin(micro['tables'], phiM, potential_drop=micro['potential_drop'], stern_capacitance=stern_c,
+                                 phi_pzc=float(tp.system.get('phiPZC', 0.0)), gamma=micro['gamma'], theta_guess=coverage['theta'])
+                        handed = flux.copy()
+                        st = {'surface_concentration': sc, 'surface_concentration_old': sc_old, 'flux': flux,
+                              'current_density_old': cd_old, 'mix': mix, 'accuracy': acc, 'surface_pH': surface_pH,
+                              'surface_potential': vsurf, 'surface_efield': esurf, 'step_to_check': step_to_check,
+                              'active': active.astype(np.int32), 'failed': failed.astype(np.int32)}
+                        istep = solver.scf_cycle(st, istep, max_iter, self.tau_scf, unit_F, nel, nprod,
+                                                 species_H=-1 if iH is None else iH, species_OH=-1 if iOH is None else iOH,
+                                                 flux_fn=sk.flux_fn, user=sk.user)
+                        dev = sk.end()
+                    finally:
+                        sk.close()
+                    sc, sc_old, flux, cd_old = (st[k] for k in ('surface_concentration', 'surface_concentration_old', 'flux',
+                                                                'current_density_old'))
+                    mix, acc, surface_pH, vsurf, esurf = (st[k] for k in ('mix', 'accuracy', 'surface_pH', 'surface_potential',
+                                                                          'surface_efield'))
+                    step_to_check = st['step_to_check']
+                    active = st['active'] != 0
+                    failed = st['failed'] != 0
+                    ran = dev['calls'] > 0
+                    for k in ('theta', 'flux_scale', 'status'):
+                        coverage[k] = np.where(ran.reshape((-1,) + (1,) * (coverage[k].ndim - 1)), dev[k], coverage[k])
+                    # a lane whose coverages were not found was handed NaN fluxes and left as failed: it reports the fluxes of its last
+                    # good call (before the hand-over when the device made none)
+                    lost = ran & (dev['status'] != 0)
+                    kept = np.where((dev['calls'] > 1)[:, None], dev['flux_last'], handed)
+                    flux = np.where(lost[:, None], kept, flux)
+                    failed = failed | lost
+                    active = active & ~lost
+                    coverage['device'] = {'kinetic_iterations': dev['iterations_total'], 'kinetic_calls': dev['calls']}
+                    break
                 if device_loop and active.any() and istep < max_iter and istep >= 2 and not restart and self.RF == 1.0:
                     # (with a roughness factor the loop stays on the host: the device table would fold RF into the fluxes the
                     #  bookkeeping of the loop sees, the reference scales only what COMSOL is given)
@@ -1338,6 +1393,7 @@ class Calculator(object):
             result['coverage'] = coverage['theta']
             result['flux_scale'] = coverage['flux_scale']
             result['kinetic_status'] = coverage['status']          # of each lane's last active iteration; non-zero: the lane is 'failed'
+            result.update(coverage.get('device', {}))
         if rate_control is not None:
             result['rate_control'] = rate_control
         return result

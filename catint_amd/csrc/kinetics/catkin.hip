@@ -3,7 +3,7 @@
 // gfx950 / MI355X only.
 //
 // Mapping, working set, tables and arithmetic: ../pnp_kin.h, which also holds the rates, the rows, the LU and the host code this
-// library shares with drc/catdrc.hip.  Here the only divergence besides the pivot row is the iteration count (a finished lane idles:
+// library shares with drc/catdrc.hip, and the Newton iteration and the flux sums it shares with scfkin/catscfkin.hip.  Here the only divergence besides the pivot row is the iteration count (a finished lane idles:
 // its unknowns stop changing).  LDS slots: J[T][T] (or N slots, whichever is more), y[T], the right-hand side [T], the row scales D[T],
 // the activities a[N] and N accumulators.  At S = 8, N = 8: 124 slots x 512 B = 62 KB per wave.
 #include "../../../include/catint_kinetics.h"
@@ -29,43 +29,7 @@ struct KArgs {
   double sd, tol, CS, pzc;
 };
 
-// what one lane carries in registers
-struct Lane {
-  double* L;       // lds + lane: slot s at L[s * 64]
-  int oJ, oY, oB, oD, oA, oC;   // first slots of J, y, right-hand side, D, activities, accumulators
-  Point pt;        // potential, charge and off row of the point
-  __device__ __forceinline__ double* at(int slot) const { return L + slot * 64; }
-};
-
-// rf and rb of step r at the lane's y; skip: see rate_factors
-__device__ __forceinline__ void rates(const KArgs& A, const Table& tb, const Lane& ln, int r, int skip, int& br, double& ef, double& eb, double& pf,
-                                      double& pb) {
-  double lf, lb;
-  rate_constants(tb, ln.pt.V, ln.pt.sg, ln.pt.off, r, lf, lb, br);
-  rate_factors(tb, A.N, A.S + 1, ln.at(ln.oY), ln.at(ln.oA), r, lf, lb, skip, ef, eb, pf, pb);
-}
-
-// J (scaled rows), right-hand side -F and the row scales D at the lane's y
-__device__ __forceinline__ void assemble(const KArgs& A, const Table& tb, const Lane& ln) {
-  const int N = A.N, T = A.S + 1;
-  double* L = ln.L;
-  for (int s = 0; s < T * T; ++s) L[(ln.oJ + s) * 64] = 0.0;
-  for (int s = 0; s < T; ++s) L[(ln.oB + s) * 64] = 0.0, L[(ln.oD + s) * 64] = 0.0;
-  for (int r = 0; r < A.R; ++r) {
-    double ef, eb, pf, pb;
-    int br;
-    rates(A, tb, ln, r, -1, br, ef, eb, pf, pb);
-    add_step_rows(tb, N, T, r, ef * pf, eb * pb, ln.at(ln.oJ), ln.at(ln.oB), ln.at(ln.oD));
-  }
-  for (int s = 1; s < T; ++s) {
-    const double D = L[(ln.oD + s) * 64];
-    const bool dead = scale_row(ln.at(ln.oJ), ln.at(ln.oY), T, s, D);
-    const double g = L[(ln.oB + s) * 64];
-    L[(ln.oB + s) * 64] = dead ? 0.0 : -(g / D);
-  }
-  const double f0 = site_row(tb, ln.at(ln.oJ), ln.at(ln.oY), T);
-  L[ln.oB * 64] = -(f0 - 1.0);
-}
+using Lane = SteadyLane;
 
 __global__ __launch_bounds__(64) void steady_kernel(const KArgs A, const Table* __restrict__ tab) {
   extern __shared__ double lds[];
@@ -73,13 +37,7 @@ __global__ __launch_bounds__(64) void steady_kernel(const KArgs A, const Table* 
   const int N = A.N, T = A.S + 1, R = A.R;
   const Table& tb = *tab;   // its own read-only argument: the uniform reads become scalar loads
   Lane ln;
-  ln.L = lds + lane;
-  ln.oJ = 0;
-  ln.oY = T * T > N ? T * T : N;
-  ln.oB = ln.oY + T;
-  ln.oD = ln.oB + T;
-  ln.oA = ln.oD + T;
-  ln.oC = ln.oA + N;
+  steady_slots(ln, lds, lane, N, T);
   double* L = ln.L;
   const double bad_number = __builtin_nan("");
 
@@ -97,61 +55,19 @@ __global__ __launch_bounds__(64) void steady_kernel(const KArgs A, const Table* 
       for (int t = 0; t < T; ++t) ok = ok && finite_(A.guess[i * T + t]);
     for (int t = 0; t < T; ++t) L[(ln.oY + t) * 64] = A.guess && ok ? log_coverage(A.guess[i * T + t]) : y0;
     // ---- Newton ----
-    int status = ok ? CATKIN_MAXIT : CATKIN_INPUT, it = 0;
-    bool active = ok && live;
-    uint64_t pivs = 0;
-    for (int iter = 0; iter < A.maxit; ++iter) {
-      if (__ballot(active) == 0) break;
-      assemble(A, tb, ln);
-      const bool bad = factor(ln.at(ln.oJ), T, pivs);
-      substitute(ln.at(ln.oJ), ln.at(ln.oB), T, pivs);
-      double mx = 0.0;
-      for (int t = 0; t < T; ++t) {
-        const double d = fabs(L[(ln.oB + t) * 64]);
-        mx = d > mx || d != d ? d : mx;
-      }
-      const double sc = mx > 3.0 ? 3.0 / mx : 1.0;
-      const bool move = active && !bad;
-      for (int t = 0; t < T; ++t) {
-        const double y = L[(ln.oY + t) * 64];
-        const double v = y + sc * L[(ln.oB + t) * 64];
-        L[(ln.oY + t) * 64] = move ? (v < MINLOG ? MINLOG : v) : y;
-      }
-      if (active) {
-        if (bad) {
-          status = CATKIN_PIVOT;
-          active = false;
-        } else {
-          ++it;
-          if (mx < A.tol) {
-            status = CATKIN_CONVERGED;
-            active = false;
-          }
-        }
-      }
-    }
+    int it;
+    uint64_t pivs;
+    int status = steady_newton(A, tb, ln, ok ? CATKIN_MAXIT : CATKIN_INPUT, ok && live, it, pivs);
     const bool nan = status == CATKIN_INPUT;
 
     // ---- coverages, rates, fluxes at the lane's y (the J slots are free: N of them hold flux_scale) ----
     if (A.theta && live)
       for (int t = 0; t < T; ++t) A.theta[i * T + t] = nan ? bad_number : exp(L[(ln.oY + t) * 64]);
     if (A.rate || A.gross || A.flux || A.fscale) {
-      for (int k = 0; k < N; ++k) L[(ln.oC + k) * 64] = 0.0, L[(ln.oJ + k) * 64] = 0.0;
-      for (int r = 0; r < R; ++r) {
-        double ef, eb, pf, pb;
-        int br;
-        rates(A, tb, ln, r, -1, br, ef, eb, pf, pb);
-        const double rf = ef * pf, rb = eb * pb, net = rf - rb, gross = rf + rb;
+      steady_fluxes(A, tb, ln, [&](int r, double net, double gross) {
         if (A.rate && live) A.rate[i * R + r] = nan ? bad_number : net;
         if (A.gross && live) A.gross[i * R + r] = nan ? bad_number : gross;
-        for (int k = 0; k < N; ++k) {
-          const double nu = tb.nu[r][k];
-          if (nu != 0.0) {
-            L[(ln.oC + k) * 64] = L[(ln.oC + k) * 64] + nu * net;
-            L[(ln.oJ + k) * 64] = L[(ln.oJ + k) * 64] + fabs(nu) * gross;
-          }
-        }
-      }
+      });
       for (int k = 0; k < N; ++k) {
         if (A.flux && live) A.flux[i * N + k] = nan ? bad_number : A.sd * L[(ln.oC + k) * 64];
         if (A.fscale && live) A.fscale[i * N + k] = nan ? bad_number : A.sd * L[(ln.oJ + k) * 64];
@@ -160,7 +76,7 @@ __global__ __launch_bounds__(64) void steady_kernel(const KArgs A, const Table* 
 
     // ---- sensitivities: J at the lane's y factorised once, one right-hand side after another ----
     if (A.sens) {
-      assemble(A, tb, ln);
+      steady_assemble(A, tb, ln);
       const bool bad = factor(ln.at(ln.oJ), T, pivs);
       if (bad && status != CATKIN_INPUT) status = CATKIN_PIVOT;
       const int first = A.dfdc ? 0 : N, last = A.dfdphi ? N + 2 : N;
@@ -182,12 +98,12 @@ __global__ __launch_bounds__(64) void steady_kernel(const KArgs A, const Table* 
           if (p < N) {
             const int of = tb.of[r][p], ob = tb.ob[r][p];
             if (of == 0 && ob == 0) continue;
-            rates(A, tb, ln, r, p, br, ef, eb, pf, pb);
+            steady_rates(A, tb, ln, r, p, br, ef, eb, pf, pb);
             drf = of ? ef * ((double)of * pf * dadc) : 0.0;
             drb = ob ? eb * ((double)ob * pb * dadc) : 0.0;
           } else {
             double dlf, dlb;
-            rates(A, tb, ln, r, -1, br, ef, eb, pf, pb);
+            steady_rates(A, tb, ln, r, -1, br, ef, eb, pf, pb);
             rate_constant_slopes(tb, ln.pt.sg, r, br, dV, ds, dlf, dlb);
             drf = (ef * pf) * dlf;
             drb = (eb * pb) * dlb;
@@ -210,7 +126,7 @@ __global__ __launch_bounds__(64) void steady_kernel(const KArgs A, const Table* 
         for (int r = 0; r < R; ++r) {
           double ef, eb, pf, pb;
           int br;
-          rates(A, tb, ln, r, -1, br, ef, eb, pf, pb);
+          steady_rates(A, tb, ln, r, -1, br, ef, eb, pf, pb);
           const double rf = ef * pf, rb = eb * pb;
           double ws = 0.0;
           for (int t = 0; t < T; ++t) {
@@ -247,6 +163,9 @@ static size_t lds_bytes(int N, int S) {
 static_assert(CATKIN_OK == pnp::post::OK && CATKIN_EINVAL == pnp::post::ERR_INVAL && CATKIN_ENOMEM == pnp::post::ERR_NOMEM &&
                   CATKIN_EDEVICE == pnp::post::ERR_DEVICE && CATKIN_MAX_SPECIES == pnp::post::MAX_SPECIES,
               "catint_kinetics.h and pnp_post.h disagree");
+static_assert(CATKIN_CONVERGED == pnp::kin::STATUS_CONVERGED && CATKIN_MAXIT == pnp::kin::STATUS_MAXIT && CATKIN_INPUT == pnp::kin::STATUS_INPUT &&
+                  CATKIN_PIVOT == pnp::kin::STATUS_PIVOT,
+              "catint_kinetics.h and pnp_kin.h disagree");
 static_assert(CATKIN_MAX_SPECIES == pnp::kin::MAXN && CATKIN_MAX_ADSORBATES == pnp::kin::MAXS && CATKIN_MAX_STEPS == pnp::kin::MAXR &&
                   CATKIN_MAX_ORDER == pnp::kin::MAX_ORDER && CATKIN_MIN_LOG == pnp::kin::MINLOG && CATKIN_DROP_FULL == pnp::kin::DROP_FULL &&
                   CATKIN_DROP_STERN == pnp::kin::DROP_STERN,

@@ -1318,19 +1318,22 @@ int pnp_solve_surface(pnp_handle* h, const double* flux, int32_t nsteps, double*
   return PNP_OK;
 }
 
-int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, const double* nprod, pnp_scf_state* s,
-                  int32_t* iterations) {
-  if (!h || !p || !s) return fail(h, PNP_EINVAL, "pnp_scf_cycle: null argument");
-  if (!h->newton) return fail(h, PNP_EINVAL, "pnp_scf_cycle: the handle was not created with PNP_METHOD_NEWTON");
-  if (!h->have_batch) return fail(h, PNP_ESTATE, "pnp_scf_cycle: call pnp_set_batch first");
-  if (p->struct_size != (int32_t)sizeof(pnp_scf_params)) return fail(h, PNP_EINVAL, "pnp_scf_cycle: struct_size mismatch (ABI)");
-  if (h->n_wk < 1) return fail(h, PNP_ESTATE, "pnp_scf_cycle: no kinetic model (pnp_set_wall_kinetics)");
-  if (p->istep < 1) return fail(h, PNP_EINVAL, "pnp_scf_cycle: the first iteration (transport solve from the bulk state) is the caller's");
+// The device SCF loop behind pnp_scf_cycle (fn == NULL: the wall table gives the fluxes) and pnp_scf_cycle_fn (fn gives them).  `entry`
+// is the exported function, the head of every message.
+static int scf_cycle_impl(pnp_handle* h, const char* entry_name, const pnp_scf_params* p, const double* nel, const double* nprod, pnp_scf_state* s,
+                          pnp_scf_flux_fn fn, void* user, int32_t* iterations) {
+  const std::string entry(entry_name);
+  if (!h || !p || !s) return fail(h, PNP_EINVAL, entry + ": null argument");
+  if (!h->newton) return fail(h, PNP_EINVAL, entry + ": the handle was not created with PNP_METHOD_NEWTON");
+  if (!h->have_batch) return fail(h, PNP_ESTATE, entry + ": call pnp_set_batch first");
+  if (p->struct_size != (int32_t)sizeof(pnp_scf_params)) return fail(h, PNP_EINVAL, entry + ": struct_size mismatch (ABI)");
+  if (!fn && h->n_wk < 1) return fail(h, PNP_ESTATE, entry + ": no kinetic model (pnp_set_wall_kinetics)");
+  if (p->istep < 1) return fail(h, PNP_EINVAL, entry + ": the first iteration (transport solve from the bulk state) is the caller's");
   const int N = h->a.N;
-  if (p->species_H >= N || p->species_OH >= N) return fail(h, PNP_EINVAL, "pnp_scf_cycle: pH species index out of range");
+  if (p->species_H >= N || p->species_OH >= N) return fail(h, PNP_EINVAL, entry + ": pH species index out of range");
   if (!s->surface_concentration || !s->surface_concentration_old || !s->flux || !s->current_density_old || !s->mix ||
       !s->accuracy || !s->surface_pH || !s->surface_potential || !s->surface_efield || !s->step_to_check || !s->active || !s->failed)
-    return fail(h, PNP_EINVAL, "pnp_scf_cycle: null array in pnp_scf_state");
+    return fail(h, PNP_EINVAL, entry + ": null array in pnp_scf_state");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   const int64_t B = h->B, cap = h->cfg.batch_capacity;
   if (!h->scf_d) {
@@ -1341,7 +1344,7 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
   ScfArgs a;
   memset(&a, 0, sizeof(a));
   a.N = N;
-  a.n_wk = h->n_wk;
+  a.n_wk = fn ? 0 : h->n_wk;      // with fn the pre kernel writes zero fluxes and the callee fills them
   a.iH = p->species_H;
   a.iOH = p->species_OH;
   a.ldx = h->a.ldx;
@@ -1408,14 +1411,34 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
   solve.stationary = true;
   solve.mask = {a.active, nullptr, 0};
   solve.explicit_kinetics = true;
+  pnp_scf_device dv;
+  memset(&dv, 0, sizeof(dv));
+  dv.struct_size = (int32_t)sizeof(pnp_scf_device);
+  dv.nspecies = N;
+  dv.batch = B;
+  dv.surface_concentration = a.sc;
+  dv.surface_potential = a.vsurf;
+  dv.surface_efield = a.esurf;
+  dv.surface_pH = a.surface_pH;
+  dv.active = a.active;
+  dv.flux = a.flux;
+  dv.stream = (void*)st;
   for (int istep = p->istep + 1; istep <= p->max_iter && rc == PNP_OK; ++istep) {
     a.istep = istep;
     a.slot = istep & 63;
     hipError_t e = hipMemsetAsync(a.counters + a.slot, 0, sizeof(int32_t), st);
     if (e == hipSuccess) e = launch_scf_pre(a, st);
     if (e != hipSuccess) {
-      rc = fail(h, PNP_EDEVICE, std::string("pnp_scf_cycle: ") + hipGetErrorString(e));
+      rc = fail(h, PNP_EDEVICE, entry + ": " + hipGetErrorString(e));
       break;
+    }
+    if (fn) {
+      dv.istep = istep;
+      const int code = fn(user, &dv);
+      if (code != 0) {
+        rc = fail(h, PNP_EDEVICE, entry + ": the flux function returned " + std::to_string(code));
+        break;
+      }
     }
     rc = run_newton(h, solve);       // stationary, warm: the state of the previous iteration (restart=True, calculator.py:523)
     if (rc != PNP_OK) break;
@@ -1426,7 +1449,7 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
       if (e == hipSuccess) e = hipStreamSynchronize(st);
       if (e == hipSuccess && left == 0) break;
     }
-    if (e != hipSuccess) rc = fail(h, PNP_EDEVICE, std::string("pnp_scf_cycle: ") + hipGetErrorString(e));
+    if (e != hipSuccess) rc = fail(h, PNP_EDEVICE, entry + ": " + hipGetErrorString(e));
   }
   if (rc != PNP_OK) return rc;
   int32_t last = 0;
@@ -1446,6 +1469,17 @@ int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, con
   HIP_TRY(h, hipStreamSynchronize(st));
   if (iterations) *iterations = last > p->istep ? last : p->istep;
   return PNP_OK;
+}
+
+int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel, const double* nprod, pnp_scf_state* s,
+                  int32_t* iterations) {
+  return scf_cycle_impl(h, "pnp_scf_cycle", p, nel, nprod, s, nullptr, nullptr, iterations);
+}
+
+int pnp_scf_cycle_fn(pnp_handle* h, const pnp_scf_params* p, const double* nel, const double* nprod, pnp_scf_state* s,
+                     pnp_scf_flux_fn fn, void* user, int32_t* iterations) {
+  if (!fn) return fail(h, PNP_EINVAL, "pnp_scf_cycle_fn: null flux function");
+  return scf_cycle_impl(h, "pnp_scf_cycle_fn", p, nel, nprod, s, fn, user, iterations);
 }
 
 int pnp_get_newton_iterations(pnp_handle* h, int32_t* iters) {

@@ -241,6 +241,132 @@ __device__ __forceinline__ void substitute(const double* J, double* b, int T, ui
   }
 }
 
+// ---- device: the steady state of one lane (kinetics/catkin.hip and scfkin/catscfkin.hip compile it from this one text) -------------
+// what one lane of a steady-state kernel carries in registers
+struct SteadyLane {
+  double* L;       // lds + lane: slot s at L[s * 64]
+  int oJ, oY, oB, oD, oA, oC;   // first slots of J, y, right-hand side, D, activities, accumulators
+  Point pt;        // potential, charge and off row of the point
+  __device__ __forceinline__ double* at(int slot) const { return L + slot * 64; }
+};
+
+// the slots of a lane for N species and T = S + 1 coverages: (max(T T, N) + 3 T + 2 N) of them
+__device__ __forceinline__ void steady_slots(SteadyLane& ln, double* lds, int lane, int N, int T) {
+  ln.L = lds + lane;
+  ln.oJ = 0;
+  ln.oY = T * T > N ? T * T : N;
+  ln.oB = ln.oY + T;
+  ln.oD = ln.oB + T;
+  ln.oA = ln.oD + T;
+  ln.oC = ln.oA + N;
+}
+
+// rf and rb of step r at the lane's y; skip: see rate_factors.  A: the kernel's arguments, read by name (int32 N, S, R here; maxit and
+// tol in steady_newton)
+template <class KA>
+__device__ __forceinline__ void steady_rates(const KA& A, const Table& tb, const SteadyLane& ln, int r, int skip, int& br, double& ef, double& eb,
+                                             double& pf, double& pb) {
+#pragma clang fp contract(off)
+  double lf, lb;
+  rate_constants(tb, ln.pt.V, ln.pt.sg, ln.pt.off, r, lf, lb, br);
+  rate_factors(tb, A.N, A.S + 1, ln.at(ln.oY), ln.at(ln.oA), r, lf, lb, skip, ef, eb, pf, pb);
+}
+
+// J (scaled rows), right-hand side -F and the row scales D at the lane's y
+template <class KA>
+__device__ __forceinline__ void steady_assemble(const KA& A, const Table& tb, const SteadyLane& ln) {
+#pragma clang fp contract(off)
+  const int N = A.N, T = A.S + 1;
+  double* L = ln.L;
+  for (int s = 0; s < T * T; ++s) L[(ln.oJ + s) * 64] = 0.0;
+  for (int s = 0; s < T; ++s) L[(ln.oB + s) * 64] = 0.0, L[(ln.oD + s) * 64] = 0.0;
+  for (int r = 0; r < A.R; ++r) {
+    double ef, eb, pf, pb;
+    int br;
+    steady_rates(A, tb, ln, r, -1, br, ef, eb, pf, pb);
+    add_step_rows(tb, N, T, r, ef * pf, eb * pb, ln.at(ln.oJ), ln.at(ln.oB), ln.at(ln.oD));
+  }
+  for (int s = 1; s < T; ++s) {
+    const double D = L[(ln.oD + s) * 64];
+    const bool dead = scale_row(ln.at(ln.oJ), ln.at(ln.oY), T, s, D);
+    const double g = L[(ln.oB + s) * 64];
+    L[(ln.oB + s) * 64] = dead ? 0.0 : -(g / D);
+  }
+  const double f0 = site_row(tb, ln.at(ln.oJ), ln.at(ln.oY), T);
+  L[ln.oB * 64] = -(f0 - 1.0);
+}
+
+// The damped Newton iteration from the y in the lane's slots: the update scaled by min(1, 3 / max|dy|), y clamped to >= MINLOG, stopped
+// when max|dy| < A.tol (the update still applied) or after A.maxit iterations.  A finished lane idles: its unknowns stop changing.
+// start: what the status is before the first iteration (STATUS_MAXIT for a lane that iterates, STATUS_INPUT for one whose inputs are
+// bad); run: the lane iterates.  Returns the status; it: the iterations taken; pivs: the pivot rows of the last factorisation
+constexpr int STATUS_CONVERGED = 0, STATUS_MAXIT = 1, STATUS_INPUT = 2, STATUS_PIVOT = 3;   // the CATKIN_* values
+template <class KA>
+__device__ __forceinline__ int steady_newton(const KA& A, const Table& tb, const SteadyLane& ln, int start, bool run, int& it, uint64_t& pivs) {
+#pragma clang fp contract(off)
+  const int T = A.S + 1;
+  double* L = ln.L;
+  int status = start;
+  bool active = run;
+  it = 0;
+  pivs = 0;
+  for (int iter = 0; iter < A.maxit; ++iter) {
+    if (__ballot(active) == 0) break;
+    steady_assemble(A, tb, ln);
+    const bool bad = factor(ln.at(ln.oJ), T, pivs);
+    substitute(ln.at(ln.oJ), ln.at(ln.oB), T, pivs);
+    double mx = 0.0;
+    for (int t = 0; t < T; ++t) {
+      const double d = fabs(L[(ln.oB + t) * 64]);
+      mx = d > mx || d != d ? d : mx;
+    }
+    const double sc = mx > 3.0 ? 3.0 / mx : 1.0;
+    const bool move = active && !bad;
+    for (int t = 0; t < T; ++t) {
+      const double y = L[(ln.oY + t) * 64];
+      const double v = y + sc * L[(ln.oB + t) * 64];
+      L[(ln.oY + t) * 64] = move ? (v < MINLOG ? MINLOG : v) : y;
+    }
+    if (active) {
+      if (bad) {
+        status = STATUS_PIVOT;
+        active = false;
+      } else {
+        ++it;
+        if (mx < A.tol) {
+          status = STATUS_CONVERGED;
+          active = false;
+        }
+      }
+    }
+  }
+  return status;
+}
+
+// The rates at the lane's y summed into the fluxes: sum_r nu_rk (rf_r - rb_r) into the N accumulator slots, sum_r |nu_rk| (rf_r + rb_r)
+// (flux_scale without the site density) into the first N slots of J, which are free by now.  per_step(r, net, gross) sees every step
+template <class KA, class F>
+__device__ __forceinline__ void steady_fluxes(const KA& A, const Table& tb, const SteadyLane& ln, F&& per_step) {
+#pragma clang fp contract(off)
+  const int N = A.N, R = A.R;
+  double* L = ln.L;
+  for (int k = 0; k < N; ++k) L[(ln.oC + k) * 64] = 0.0, L[(ln.oJ + k) * 64] = 0.0;
+  for (int r = 0; r < R; ++r) {
+    double ef, eb, pf, pb;
+    int br;
+    steady_rates(A, tb, ln, r, -1, br, ef, eb, pf, pb);
+    const double rf = ef * pf, rb = eb * pb, net = rf - rb, gross = rf + rb;
+    per_step(r, net, gross);
+    for (int k = 0; k < N; ++k) {
+      const double nu = tb.nu[r][k];
+      if (nu != 0.0) {
+        L[(ln.oC + k) * 64] = L[(ln.oC + k) * 64] + nu * net;
+        L[(ln.oJ + k) * 64] = L[(ln.oJ + k) * 64] + fabs(nu) * gross;
+      }
+    }
+  }
+}
+
 // ---- host: the context ---------------------------------------------------------------------------------------------------------------
 struct Ctx : pnp::post::Ctx {
   std::vector<double> stage;    // host: the inputs of the call in flight, one copy

@@ -17,10 +17,15 @@ as the surface CO2 concentration drops from 5.7 to 0.14 mol/m^3 and CO* gives wa
 
     python examples/co2r_microkinetic_sweep.py --lanes 16
     python examples/co2r_microkinetic_sweep.py --lanes 16 --newton
+    python examples/co2r_microkinetic_sweep.py --lanes 16 --device-loop
 
 --newton: the same fixed point by a Newton iteration on the wall fluxes (Calculator.set_microkinetics(..., scf='newton'),
 include/catint_couple.h) in the place of the mixing loop: a handful of transport solves instead of one per mixing iteration.  The
 figures of both are in profiles/couple_probe.md.
+
+--device-loop: the mixing loop itself on the device (Calculator.set_microkinetics(..., device_loop=True), include/catint_scfkin.h):
+after the first host iterations the kinetics run between the loop's bookkeeping and its transport solve with no host round trip per
+iteration; the same iterates as the default.  The figures of both are in profiles/scfkin_probe.md.
 
 --rate-control: after the loop, the degree of rate control of the CO flux at the final surface state of every voltage
 (include/catint_drc.h, Calculator.set_microkinetics(..., rate_control=True)): per potential the step whose transition state and the
@@ -64,13 +69,16 @@ def main():
     ap.add_argument('--site-fraction', type=float, default=1e-3, help='fraction of the active site density that takes part')
     ap.add_argument('--max-iter', type=int, default=2000)
     ap.add_argument('--newton', action='store_true', help='Newton iteration on the wall fluxes instead of the mixing loop')
+    ap.add_argument('--device-loop', action='store_true', help='the mixing loop on the device, no host round trip per iteration')
     ap.add_argument('--rate-control', action='store_true', help='degree of rate control of the CO flux at the final state of every lane')
     a = ap.parse_args()
+    if a.newton and a.device_loop:
+        ap.error('--device-loop is the mixing loop on the device: it excludes --newton')
     tp, phis = co2r_physical_sweep.build(a.lanes, a.nx, a.phimin, a.phimax)
     tp.newton = {'tol': 1e-8, 'maxit': 80}
     calc = Calculator(transport=tp, calc='comsol', tau_scf=1e-4, mix_scf=0.1)
     calc.set_microkinetics(model(tp), site_density=a.site_fraction * float(tp.system['active site density']), potential_drop='stern',
-                          scf='newton' if a.newton else 'mixing', rate_control=a.rate_control)
+                          scf='newton' if a.newton else 'mixing', rate_control=a.rate_control, device_loop=a.device_loop)
     names = list(tp.species.keys())
     t0 = time.time()
     out = calc.run_scf_cycle(nel=[2.0 if sp == 'CO' else 1.0 for sp in names], max_iter=a.max_iter)

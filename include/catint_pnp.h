@@ -314,6 +314,30 @@ typedef struct pnp_scf_state {
 int pnp_scf_cycle(pnp_handle* h, const pnp_scf_params* p, const double* nel /* [N] or NULL */, const double* nprod /* [N] or NULL */,
                   pnp_scf_state* s, int32_t* iterations /* last iteration number that had active lanes, nullable */);
 
+/* The same loop with the wall fluxes supplied by the caller's function instead of the wall table: fn is called on the host once per
+ * iteration, after scf_pre_kernel (mixing, fallback, pH, sc_old; the flux rows of the active lanes zeroed) and before the transport
+ * solve, with device pointers into the loop's own arrays.  It enqueues its work on d->stream and returns without synchronising; the
+ * loop's solve follows on the same stream.  The wall table is not consulted (a handle without one is accepted); everything else --
+ * lane flags, snapshots, accuracy, check_every, exit arrays -- is pnp_scf_cycle.  A lane whose fluxes the callee cannot produce gets
+ * NaN in its flux row: its transport solve ends non-finite and the lane leaves with failed = 1, the others go on.
+ * fn == NULL: PNP_EINVAL.  A non-zero return of fn ends the call with PNP_EDEVICE (the code is in pnp_last_error); the arrays of
+ * pnp_scf_state are then not written back, and the handle remains usable. */
+typedef struct pnp_scf_device {
+  int32_t struct_size, nspecies, istep, reserved;
+  int64_t batch;
+  const double* surface_concentration; /* [B][N] device: the MIXED iterate of this iteration (scf_pre_kernel has run) */
+  const double* surface_potential;     /* [B] device: phi(x=0) of the previous transport solve */
+  const double* surface_efield;        /* [B] device */
+  const double* surface_pH;            /* [B] device */
+  const int32_t* active;               /* [B] device */
+  double* flux;                        /* [B][N] device: rows of active lanes are zero at entry and are the callee's to write;
+                                          rows of inactive lanes must not be touched */
+  void* stream;                        /* the handle's hipStream_t: the callee enqueues there and does not synchronise */
+} pnp_scf_device;
+typedef int (*pnp_scf_flux_fn)(void* user, const pnp_scf_device* d);   /* 0, or non-zero: the loop stops */
+int pnp_scf_cycle_fn(pnp_handle* h, const pnp_scf_params* p, const double* nel, const double* nprod, pnp_scf_state* s,
+                     pnp_scf_flux_fn fn, void* user, int32_t* iterations);
+
 /* Newton iterations each lane spent in the most recent pnp_step / pnp_solve_stationary call, summed over its
  * timesteps; a solve that hit maxit counts maxit+1. */
 int pnp_get_newton_iterations(pnp_handle* h, int32_t* iters /* [B] */);
