@@ -275,6 +275,7 @@ class PnpSolver(object):
         self._coupler = None
         self._sensitizer = None
         self._rate_control = None
+        self._transient = None
 
     def _check(self, rc):
         if rc != 0:
@@ -308,6 +309,9 @@ class PnpSolver(object):
         if getattr(self, '_rate_control', None) is not None:
             self._rate_control.close()
             self._rate_control = None
+        if getattr(self, '_transient', None) is not None:
+            self._transient.close()
+            self._transient = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -767,7 +771,7 @@ class PnpSolver(object):
 
     def get_kinetics(self, model_or_tables, phiM=None, lanes=None, csurf=None, phi_surface=None, theta_guess=None, fields=None,
                      potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None,
-                     tol=None, maxit=None, max_waves=0):
+                     tol=None, maxit=None, max_waves=0, rescue=False):
         """The steady state of a mean-field surface microkinetic model (include/catint_kinetics.h) solved on the device, one operating
         point per entry of `lanes` (None: all lanes, in order; repeats allowed): coverages, step rates, the wall fluxes into the
         electrolyte and, when asked for, their sensitivities to the surface concentrations and potentials.  model_or_tables: a
@@ -778,8 +782,15 @@ class PnpSolver(object):
         point.  fields: names out of catint_amd._kinetics.FIELDS (None: 'theta', 'rate', 'rate_gross', 'flux', 'flux_scale'; also
         'dflux_dc' [n][N][N], 'dflux_dphi' [n][N][2]).  Returns a dict of these arrays and 'status' [n] (0 converged; 1 stopped at
         maxit; 2 the lane's solver status is not 0 or an input is not finite: NaN; 3 a zero or non-finite pivot), 'iterations' [n].
-        The number of digits of 'flux' is what flux / flux_scale leaves of 16."""
+        The number of digits of 'flux' is what flux / flux_scale leaves of 16.
+        rescue=True (default False: the call above and nothing else; needs theta_guess None): the points that come back with status 1
+        or 3 are integrated in time from the uniform start until they are stationary (include/catint_kintrans.h: to 1e12 s with rtol
+        1e-2, stopped at a scaled residual of 1e-6) and the ones that get there are solved again from that state; the rows of those
+        that now converge replace the failed ones and the result gains 'rescued' [n] (bool).  A point whose second solve fails as
+        well keeps its first rows and status."""
         from . import _kinetics
+        if rescue and theta_guess is not None:
+            raise ValueError('get_kinetics: rescue=True starts from the uniform surface and excludes theta_guess')
         o = self._obs
         tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
         if site_density is not None:
@@ -799,12 +810,64 @@ class PnpSolver(object):
             phiM = np.asarray(o['phiM'], float)[idx]
         if self._kinetics is None:
             self._kinetics = _kinetics.KineticsSolver(o['device'])
-        return self._kinetics.solve(None if host else self.device_view(), tables, phiM, lanes=None if host else idx, csurf=csurf,
-                                    phi_surface=phi_surface, potential_drop=potential_drop,
-                                    stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
-                                    phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma,
-                                    theta_guess=theta_guess, tol=_kinetics.DEFAULT_TOL if tol is None else tol,
-                                    maxit=_kinetics.DEFAULT_MAXIT if maxit is None else maxit, fields=fields, max_waves=max_waves)
+        view = None if host else self.device_view()
+        common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
+                      phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, tol=_kinetics.DEFAULT_TOL if tol is None else tol,
+                      maxit=_kinetics.DEFAULT_MAXIT if maxit is None else maxit, fields=fields, max_waves=max_waves)
+        res = self._kinetics.solve(view, tables, phiM, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, sigma=sigma, off=off,
+                                   gamma=gamma, theta_guess=theta_guess, **common)
+        if rescue:
+            from . import _kintrans
+            _kintrans.rescue(self._kinetics, self._transient_kinetics(), view, tables, phiM, res, lanes=None if host else idx,
+                             per_point=dict(csurf=csurf, phi_surface=phi_surface, sigma=sigma, off=off, gamma=gamma), **common)
+        return res
+
+    def _transient_kinetics(self):
+        from . import _kintrans
+        if getattr(self, '_transient', None) is None:
+            self._transient = _kintrans.TransientKinetics(self._obs['device'])
+        return self._transient
+
+    def get_kinetics_transient(self, model_or_tables, t_out, phiM=None, lanes=None, csurf=None, phi_surface=None, theta0=None, rtol=1e-4,
+                               atol=1e-12, steady_tol=0.0, fields=None, potential_drop='stern', stern_capacitance=None, phi_pzc=None,
+                               sigma=None, off=None, gamma=None, site_density=None, h0=0.0, newton_tol=None, newton_maxit=None, max_steps=None,
+                               max_waves=0):
+        """The transient of the microkinetic model at a constant surface state (include/catint_kintrans.h) integrated on the device, one
+        operating point per entry of `lanes`, every point with its own step size: how the coverages relax after a step of the potential
+        or of the surface concentrations, and the kinetic time scale to set beside the transport's (get_modes).  The model, the surface
+        state (this handle's, or csurf and phi_surface) and phiM, stern_capacitance, phi_pzc, sigma, off, gamma are those of
+        get_kinetics.  t_out [n_out]: output times in s, positive and increasing, common to the points; theta0 [n][S+1]: the coverages
+        at t = 0, e.g. get_kinetics(...)['theta'] at the state before the step (the free-site entry is recomputed from the site
+        balance), None: the uniform surface.  rtol, atol: per step, on the coverages; steady_tol > 0 stops a point whose scaled
+        residual max |G_s| / D_s falls below it.  fields: names out of catint_amd._kintrans.FIELDS (None: all).  Returns a dict of
+        'theta' [n][n_out][S+1], 'flux', 'flux_scale' [n][n_out][N], 'drift' [n][n_out], 't_reached' [n], 'status' [n] (0 every output
+        time reached; 1 stopped stationary, the remaining rows hold that state; 2 unsolved lane or non-finite input: NaN; 3 max_steps
+        were not enough, the rows not reached are NaN) and 'steps' [n][3] (accepted, rejected, Newton iterations)."""
+        from . import _kintrans
+        o = self._obs
+        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
+        if site_density is not None:
+            tables['site_density'] = float(site_density)
+        host = csurf is not None or phi_surface is not None
+        if lanes is not None:
+            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        elif host and phiM is not None:
+            idx = None
+        else:
+            idx = np.arange(self.B, dtype=np.int64)
+        if phiM is None:
+            if o['phiM'] is None:
+                raise ValueError('get_kinetics_transient: no batch was set')
+            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+                raise ValueError('get_kinetics_transient: lane index outside [0, %d)' % self.B)
+            phiM = np.asarray(o['phiM'], float)[idx]
+        return self._transient_kinetics().solve(
+            None if host else self.device_view(), tables, phiM, t_out, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface,
+            potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
+            phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma, theta0=theta0, rtol=rtol, atol=atol,
+            steady_tol=steady_tol, h0=h0, newton_tol=_kintrans.DEFAULT_NEWTON_TOL if newton_tol is None else newton_tol,
+            newton_maxit=_kintrans.DEFAULT_NEWTON_MAXIT if newton_maxit is None else newton_maxit,
+            max_steps=_kintrans.DEFAULT_MAX_STEPS if max_steps is None else max_steps, fields=fields, max_waves=max_waves)
 
     def get_rate_control(self, model_or_tables, theta=None, phiM=None, lanes=None, csurf=None, phi_surface=None, fields=None,
                          potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None,

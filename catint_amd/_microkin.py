@@ -14,7 +14,7 @@ DROP = {'full': 0, 'stern': 1}
 _PD, _PI, _PL = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 # values per operating point from (N, T, R)
 _PER_POINT = {'sigma': lambda N, T, R: 1, 'off': lambda N, T, R: R * 2, 'gamma': lambda N, T, R: max(N, 0), 'theta_guess': lambda N, T, R: T,
-              'theta': lambda N, T, R: T, 'csurf': lambda N, T, R: max(N, 0), 'phi_surface': lambda N, T, R: 1}
+              'theta': lambda N, T, R: T, 'theta0': lambda N, T, R: T, 'csurf': lambda N, T, R: max(N, 0), 'phi_surface': lambda N, T, R: 1}
 
 
 def _iptr(a):

@@ -103,6 +103,13 @@ SCFKIN_LIB = os.path.join(LIB_DIR, 'libcatint_scfkin.so')
 SCFKIN_SOURCES = ['catscfkin.hip']
 SCFKIN_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_scfkin.h')]
 
+# thirteenth library (include/catint_kintrans.h): the transient of the microkinetic model -- implicit Euler with step doubling in the
+# log-coverages, every operating point with its own step size, all steps inside one launch.  A library of its own as the eleven before it
+KINTRANS_DIR = os.path.join(CSRC, 'kintrans')
+KINTRANS_LIB = os.path.join(LIB_DIR, 'libcatint_kintrans.so')
+KINTRANS_SOURCES = ['catkt.hip']
+KINTRANS_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h'), os.path.join(_INCLUDE, 'catint_kintrans.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -278,6 +285,15 @@ def scfkin_needs_build():
 def build_scfkin_library(force=False, verbose=False):
     """catint_amd/csrc/scfkin into catint_amd/lib/libcatint_scfkin.so"""
     return _build_unit(SCFKIN_DIR, SCFKIN_SOURCES, SCFKIN_HEADERS, SCFKIN_LIB, force, verbose)
+
+
+def kintrans_needs_build():
+    return _unit_needs_build(KINTRANS_DIR, KINTRANS_SOURCES, KINTRANS_HEADERS, KINTRANS_LIB)
+
+
+def build_kintrans_library(force=False, verbose=False):
+    """catint_amd/csrc/kintrans into catint_amd/lib/libcatint_kintrans.so"""
+    return _build_unit(KINTRANS_DIR, KINTRANS_SOURCES, KINTRANS_HEADERS, KINTRANS_LIB, force, verbose)
 
 
 def unittest_needs_build():

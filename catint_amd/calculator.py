@@ -329,7 +329,8 @@ class Calculator(object):
             raise CalculatorError('set_surface_kinetics and set_microkinetics exclude each other: one kinetic model per calculator')
         self.surface_kinetics = list(reactions)
 
-    def set_microkinetics(self, model, site_density=None, potential_drop='stern', gamma=None, scf='mixing', rate_control=False, device_loop=False):
+    def set_microkinetics(self, model, site_density=None, potential_drop='stern', gamma=None, scf='mixing', rate_control=False, device_loop=False,
+                          rescue=False):
         """Mean-field surface microkinetics as the kinetic half of run_scf_cycle (physical mode only): model is a
         catint_amd.microkinetics.MeanFieldModel over this transport's species (or the dict of its tables()).  With it set,
         run_scf_cycle() without a callback runs its host loop with the device kinetics (include/catint_kinetics.h) as the callback: the
@@ -354,7 +355,11 @@ class Calculator(object):
         device, with no host round trip per iteration; converged lanes leave the batch.  As with the wall table's device loop
         'history' holds the host iterations only, and with a transport_fn or a roughness factor other than 1 the loop stays on the
         host.  The result then also carries 'kinetic_iterations' [B] (Newton iterations of the kinetics on the device) and
-        'kinetic_calls' [B]."""
+        'kinetic_calls' [B].
+        rescue=True (default False: no call of the library is made): a lane whose kinetic solve ends with status 1 or 3 in an iteration
+        of the host loop (scf='mixing' or 'newton') is integrated in time from the uniform surface until it is stationary
+        (include/catint_kintrans.h) and solved again from there (catint_amd._kintrans.rescue) before it would leave the loop as
+        'failed'.  The device loop has no rescue yet: together with device_loop=True it is an error."""
         if model is None:
             self.microkinetics = None
             return
@@ -368,6 +373,8 @@ class Calculator(object):
             raise CalculatorError("potential_drop is 'stern' or 'full'")
         if device_loop and scf != 'mixing':
             raise CalculatorError("device_loop=True needs scf='mixing': the Newton iteration on the wall fluxes is driven from the host")
+        if device_loop and rescue:
+            raise CalculatorError('rescue=True is part of the host loops: the device loop (device_loop=True) has no rescue')
         tables = model.tables() if hasattr(model, 'tables') else dict(model)
         N = self.tp.nspecies
         nu, of = np.asarray(tables['nu']), np.asarray(tables['order_f'])
@@ -383,6 +390,8 @@ class Calculator(object):
             self.microkinetics['rate_control'] = True
         if device_loop:
             self.microkinetics['device_loop'] = True
+        if rescue:
+            self.microkinetics['rescue'] = True
 
     def _rate_control_solver(self):
         """The device context of the rate-control analysis (tests replace it)"""
@@ -423,6 +432,24 @@ class Calculator(object):
         """The device context of the microkinetic solves (tests replace it)"""
         from . import _kinetics
         return _kinetics.KineticsSolver(self.device)
+
+    def _transient_solver(self):
+        """The device context of the transient kinetics behind set_microkinetics(rescue=True) (tests replace it)"""
+        from . import _kintrans
+        return _kintrans.TransientKinetics(self.device)
+
+    def _rescue_kinetics(self, kin_solver, out, view, tables, phiM, lanes=None, per_point=None, **solve_kw):
+        """set_microkinetics(rescue=True): the points of the solve `out` that ended with status 1 or 3 once more, by way of the
+        transient (catint_amd._kintrans.rescue).  No context is created while every point converges."""
+        from . import _kintrans
+        status = np.asarray(out['status'])
+        if not ((status == 1) | (status == 3)).any():
+            return out
+        tr = self._transient_solver()
+        try:
+            return _kintrans.rescue(kin_solver, tr, view, tables, phiM, out, lanes=lanes, per_point=per_point, **solve_kw)
+        finally:
+            tr.close()
 
     def _scf_kinetics(self):
         """The device context of the kinetics inside the device SCF loop (tests replace it)"""
@@ -1183,6 +1210,12 @@ class Calculator(object):
                                        phi_surface=state['surface_potential'], potential_drop=micro['potential_drop'],
                                        stern_capacitance=stern_c, phi_pzc=float(tp.system.get('phiPZC', 0.0)), gamma=micro['gamma'],
                                        theta_guess=guess, fields=('theta', 'flux', 'flux_scale'))
+                if micro.get('rescue'):
+                    out = self._rescue_kinetics(kin_solver, out, None, micro['tables'], state['phiM'],
+                                                per_point=dict(csurf=state['surface_concentration'], phi_surface=state['surface_potential'],
+                                                               gamma=micro['gamma']),
+                                                potential_drop=micro['potential_drop'], stern_capacitance=stern_c,
+                                                phi_pzc=float(tp.system.get('phiPZC', 0.0)), fields=('theta', 'flux', 'flux_scale'))
                 live = coverage.get('active', np.ones(len(out['status']), bool))
                 for k in ('theta', 'flux_scale', 'status'):
                     coverage[k] = out[k] if k not in coverage else np.where(live.reshape((-1,) + (1,) * (out[k].ndim - 1)), out[k], coverage[k])
@@ -1459,6 +1492,11 @@ class Calculator(object):
                 kin = kin_solver.solve(solver.device_view(), tables, phiM[idx], lanes=idx, potential_drop=micro['potential_drop'],
                                        stern_capacitance=stern_c, phi_pzc=phi_pzc, gamma=None if micro['gamma'] is None else micro['gamma'][idx],
                                        theta_guess=guess, fields=('theta', 'flux', 'flux_scale', 'dflux_dc', 'dflux_dphi'))
+                if micro.get('rescue'):
+                    kin = self._rescue_kinetics(kin_solver, kin, solver.device_view(), tables, phiM[idx], lanes=idx,
+                                                per_point=dict(gamma=None if micro['gamma'] is None else micro['gamma'][idx]),
+                                                potential_drop=micro['potential_drop'], stern_capacitance=stern_c, phi_pzc=phi_pzc,
+                                                fields=('theta', 'flux', 'flux_scale', 'dflux_dc', 'dflux_dphi'))
                 theta[idx], flux_scale[idx], kflux[idx], kin_status[idx] = kin['theta'], kin['flux_scale'], kin['flux'], kin['status']
                 K = np.asarray(kin['flux'], float)
                 kbad = np.asarray(kin['status']) != 0
