@@ -276,6 +276,7 @@ class PnpSolver(object):
         self._sensitizer = None
         self._rate_control = None
         self._transient = None
+        self._impedance = None
 
     def _check(self, rc):
         if rc != 0:
@@ -312,6 +313,9 @@ class PnpSolver(object):
         if getattr(self, '_transient', None) is not None:
             self._transient.close()
             self._transient = None
+        if getattr(self, '_impedance', None) is not None:
+            self._impedance.close()
+            self._impedance = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -964,6 +968,119 @@ class PnpSolver(object):
                                    dphi_max=dphi_max, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
                                    stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], fields=fields,
                                    max_waves=max_waves)
+
+    def _eis_handle(self):
+        from . import _eis
+        if getattr(self, '_impedance', None) is None:
+            self._impedance = _eis.Impedance(self._obs['device'])
+        return self._impedance
+
+    def get_kinetic_admittance(self, model_or_tables, omega, theta=None, phiM=None, lanes=None, csurf=None, phi_surface=None, fields=None,
+                               potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None,
+                               site_density=None, residual_tol=1e-8, max_waves=0):
+        """The intrinsic kinetic admittance of the microkinetic model at a fixed surface state (include/catint_eis.h: cateis_kinetic),
+        on the device, one operating point per entry of `lanes` and one column per angular frequency of `omega` (rad/s, >= 0): how the
+        wall fluxes answer a small harmonic change of the surface concentrations and of the two potentials when the adsorbates store
+        charge-free matter, i omega theta.  The model, the surface state (this handle's, or csurf and phi_surface) and phiM,
+        stern_capacitance, phi_pzc, sigma, off, gamma are those of get_kinetics; theta [n][S+1]: the stationary coverages (None:
+        get_kinetics is called first).  fields: names out of catint_amd._eis.KINETIC_FIELDS and 'residual' (None: 'Kc', 'Kphi',
+        'residual').  Returns complex128 'Kc' [n][F][N][N] = dflux_k / dc_j, 'Kphi' [n][F][N][2] = d/dphiM, d/dphi_0, 'dy'
+        [n][F][S+1][N+2] = d ln theta, 'residual' [n] = max_s |G_s| / D_s, 'status' [n][F] (0; 2: unsolved lane or non-finite input,
+        NaN; 3: bad pivot; 4: residual above residual_tol) and 'omega' [F].  At omega = 0 Kc and Kphi are get_kinetics' dflux_dc and
+        dflux_dphi."""
+        o = self._obs
+        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
+        if site_density is not None:
+            tables['site_density'] = float(site_density)
+        host = csurf is not None or phi_surface is not None
+        if lanes is not None:
+            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        elif host and phiM is not None:
+            idx = None
+        else:
+            idx = np.arange(self.B, dtype=np.int64)
+        if phiM is None:
+            if o['phiM'] is None:
+                raise ValueError('get_kinetic_admittance: no batch was set')
+            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+                raise ValueError('get_kinetic_admittance: lane index outside [0, %d)' % self.B)
+            phiM = np.asarray(o['phiM'], float)[idx]
+        common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
+                      phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma)
+        if theta is None:
+            theta = self.get_kinetics(tables, phiM=phiM, lanes=lanes, csurf=csurf, phi_surface=phi_surface, fields=('theta',), max_waves=max_waves,
+                                      **common)['theta']
+        om = np.atleast_1d(np.asarray(omega, float)).reshape(-1)
+        out = self._eis_handle().kinetic(None if host else self.device_view(), tables, phiM, theta, om, lanes=None if host else idx, csurf=csurf,
+                                         phi_surface=phi_surface, residual_tol=residual_tol, fields=fields, max_waves=max_waves, **common)
+        out['omega'] = om.copy()
+        return out
+
+    def get_impedance(self, model_or_tables, omega, theta=None, rf=1.0, lanes=None, fields=None, phiM=None, potential_drop='stern', sigma=None,
+                      off=None, gamma=None, site_density=None, residual_tol=1e-8, max_waves=0):
+        """The impedance of the working electrode with the microkinetic model at its surface (include/catint_eis.h: cateis_solve), on
+        the device, about the stationary state this handle holds: for every lane of `lanes` (None: all, in order; repeats allowed) and
+        every angular frequency of `omega` (rad/s, >= 0) the linearised surface kinetics with adsorbate storage, the transport transfer
+        functions at the same frequency and the Stern layer are closed at the wall.  The model and phiM, sigma, off, gamma are those of
+        get_kinetics; theta [n][S+1]: the stationary coverages (None: get_kinetics is called first); rf: the roughness factor the SCF
+        loop used (0: the blocking electrode).  fields: names out of catint_amd._eis.FIELDS (None: 'admittance', 'faradaic',
+        'double_layer', 'dflux', 'dc_surface', 'dphi_surface', 'dsigma', 'residual').  Returns complex128 arrays: 'admittance' [n][F] in
+        A m^-2 V^-1 = 'double_layer' (i omega dsigma) + 'faradaic' (sum_k q_k dflux_k), 'dflux', 'dc_surface' [n][F][N],
+        'dphi_surface', 'dsigma' [n][F] per volt of phiM; on request the transfer functions 'Tc' [n][F][N][N], 'Tphi', 'tc' [n][F][N],
+        'tphi' [n][F], the kinetic 'Kc', 'Kphi', 'dy'; 'residual' [n]; 'status' [n][F] (0; 1: failed pivot check in the transport
+        elimination; 2: unsolved lane or non-finite input, NaN; 3: singular kinetic or coupled matrix; 4: the coverages are not
+        stationary, residual above residual_tol); 'omega' [F]; 'impedance' = 1 / admittance (inf where it is 0);
+        'polarization_resistance' [n] = 1 / Re admittance at the first omega = 0 of the list (absent without one): the slope of the
+        polarisation curve of the coupled electrode.  'dtheta' [n][F][S+1] = theta_t (sum_j dy_tj dc_j + dy_t,phiM + dy_t,phi0 dphi_0) is
+        the answer of the coverages per volt.  It is a field name of this method only (in the default list; otherwise name it in
+        `fields`): the library is asked for 'dy', 'dc_surface' and 'dphi_surface', the chain rule is formed on the host, and of those
+        three the result keeps the ones `fields` names (the default list names 'dc_surface' and 'dphi_surface', not 'dy').  The state
+        must be stationary and solved with prescribed wall fluxes (the SCF loop of the microkinetic model): with a wall table set
+        (set_wall_kinetics) the call raises ValueError.  Adsorbates carry no charge of their own and C_S is constant."""
+        o = self._obs
+        if o['wall'] is not None and not o['explicit_kinetics']:
+            raise ValueError('get_impedance: the handle applies a wall table (set_wall_kinetics); the impedance of the microkinetic electrode is '
+                             'defined for a state solved with prescribed wall fluxes only')
+        if o['phiM'] is None:
+            raise ValueError('get_impedance: no batch was set')
+        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
+        if site_density is not None:
+            tables['site_density'] = float(site_density)
+        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+            raise ValueError('get_impedance: lane index outside [0, %d)' % self.B)
+        if phiM is None:
+            phiM = np.asarray(o['phiM'], float)[idx]
+        common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'], phi_pzc=o['phi_pzc'], sigma=sigma, off=off,
+                      gamma=gamma)
+        if theta is None:
+            theta = self.get_kinetics(tables, phiM=phiM, lanes=idx, fields=('theta',), max_waves=max_waves, **common)['theta']
+        om = np.atleast_1d(np.asarray(omega, float)).reshape(-1)
+        from . import _eis
+        names = list(_eis.DEFAULT_FIELDS) + ['dtheta'] if fields is None else list(fields)
+        ask = [k for k in names if k != 'dtheta']
+        if 'dtheta' in names:
+            ask += [k for k in ('dy', 'dc_surface', 'dphi_surface') if k not in ask]
+        out = self._eis_handle().solve(self.device_view(), tables, phiM, theta, om, o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'],
+                                       rf=rf, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'], velocity=o['velocity'],
+                                       reactions=o['reactions'], residual_tol=residual_tol, fields=ask, max_waves=max_waves, **common)
+        out['omega'] = om.copy()
+        if 'admittance' in out:
+            with np.errstate(divide='ignore', invalid='ignore'):
+                y = out['admittance']
+                out['impedance'] = np.where(y == 0, np.inf, 1.0 / np.where(y == 0, 1.0, y))
+                zero = np.flatnonzero(om == 0.0)
+                if len(zero):
+                    out['polarization_resistance'] = 1.0 / y[:, zero[0]].real
+        if 'dtheta' in names:
+            N = self.N
+            dy = out['dy']
+            th = np.asarray(theta, float).reshape(len(idx), 1, -1)
+            out['dtheta'] = th * (np.einsum('nftj,nfj->nft', dy[..., :N], out['dc_surface']) + dy[..., N] + dy[..., N + 1] * out['dphi_surface'][..., None])
+        for k in ask:
+            if k not in names:
+                del out[k]
+        return out
 
     def get_sensitivities(self, parameters, lanes=None, fields=None, flux=None, max_waves=0):
         """The sensitivities of the stationary state this handle holds to its model parameters (include/catint_sens.h), solved on the

@@ -110,6 +110,14 @@ KINTRANS_LIB = os.path.join(LIB_DIR, 'libcatint_kintrans.so')
 KINTRANS_SOURCES = ['catkt.hip']
 KINTRANS_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h'), os.path.join(_INCLUDE, 'catint_kintrans.h')]
 
+# fourteenth library (include/catint_eis.h): the impedance of the microkinetic electrode -- the linearised surface kinetics with adsorbate
+# storage per (operating point, frequency) in one kernel, the transport transfer functions at the same frequency and the closure at the
+# wall in a second one that reads what the first wrote.  It includes both shared headers.  A library of its own as the twelve before it
+EIS_DIR = os.path.join(CSRC, 'eis')
+EIS_LIB = os.path.join(LIB_DIR, 'libcatint_eis.so')
+EIS_SOURCES = ['cateis.hip']
+EIS_HEADERS = _POST_HEADERS + [os.path.join(CSRC, 'pnp_team.h'), os.path.join(CSRC, 'pnp_kin.h'), os.path.join(_INCLUDE, 'catint_eis.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -294,6 +302,15 @@ def kintrans_needs_build():
 def build_kintrans_library(force=False, verbose=False):
     """catint_amd/csrc/kintrans into catint_amd/lib/libcatint_kintrans.so"""
     return _build_unit(KINTRANS_DIR, KINTRANS_SOURCES, KINTRANS_HEADERS, KINTRANS_LIB, force, verbose)
+
+
+def eis_needs_build():
+    return _unit_needs_build(EIS_DIR, EIS_SOURCES, EIS_HEADERS, EIS_LIB)
+
+
+def build_eis_library(force=False, verbose=False):
+    """catint_amd/csrc/eis into catint_amd/lib/libcatint_eis.so"""
+    return _build_unit(EIS_DIR, EIS_SOURCES, EIS_HEADERS, EIS_LIB, force, verbose)
 
 
 def unittest_needs_build():
