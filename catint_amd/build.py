@@ -15,7 +15,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-Wal
 _INCLUDE = os.path.join(_HERE, '..', 'include')
 # what every library that derives quantities from a device-resident state includes (csrc/pnp_post.h); tests/test_build_deps.py follows
 # the #include lines of the first three libraries and compares with the lists here (tests/test_regrid_abi.py: the fourth)
-_POST_HEADERS = [os.path.join(CSRC, h) for h in ('pnp_post.h', 'pnp_wave.h', 'pnp_math.h', 'pnp_internal.h')] + [os.path.join(_INCLUDE, 'catint_pnp.h')]
+_POST_HEADERS = [os.path.join(CSRC, h) for h in ('pnp_post.h', 'pnp_stage.h', 'pnp_wave.h', 'pnp_math.h', 'pnp_internal.h')] + [os.path.join(_INCLUDE, 'catint_pnp.h')]
 # what the two libraries that eliminate the stationary Jacobian with a team of lanes per system include on top (csrc/pnp_team.h)
 _TEAM_HEADERS = _POST_HEADERS + [os.path.join(CSRC, 'pnp_team.h')]
 # what the two libraries that work on a microkinetic model with one operating point per lane include on top (csrc/pnp_kin.h)

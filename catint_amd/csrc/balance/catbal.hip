@@ -307,9 +307,7 @@ static_assert(CATBAL_OK == pnp::post::OK && CATBAL_EINVAL == pnp::post::ERR_INVA
                   CATBAL_EDEVICE == pnp::post::ERR_DEVICE && CATBAL_MAX_NX == pnp::post::MAX_NX && CATBAL_MAX_SPECIES == pnp::post::MAX_SPECIES,
               "catint_balance.h and pnp_post.h disagree");
 
-struct catbal_ctx : pnp::post::Ctx {
-  std::vector<double> stage;   // host: the inputs of the call in flight, one copy
-};
+struct catbal_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -407,19 +405,20 @@ int catbal_species(catbal_ctx* ctx, const pnp_device_view* view, const catbal_pa
   while (blocks > 1 && (size_t)blocks * ws_block > ((size_t)16 << 20)) blocks /= 2;
 
   // the inputs, staged on the host for one copy: grid, prescribed flux, electrode potential, wall rate constants, tables
-  const size_t o_x = 0, o_j = o_x + even(nx), o_p = o_j + even((size_t)B * N), o_k = o_p + even(B), o_t = o_k + even((size_t)B * W),
-               n_in = o_t + sizeof(Table) / 8;
+  Inputs in;
+  const int i_x = in.add((size_t)nx, &a.x), i_j = in.add((size_t)B * N, &a.jpre), i_p = in.add((size_t)B, &a.phiM),
+            i_k = in.add((size_t)B * W, &a.kwall), i_t = in.add_unpadded(sizeof(Table) / 8, &a.tab);
+  const size_t n_in = in.total;
   try {
     ctx->stage.assign(n_in, 0.0);
   } catch (const std::bad_alloc&) {
     return fail(ctx, CATBAL_ENOMEM, "catbal_species: out of host memory");
   }
-  double* sg = ctx->stage.data();
-  memcpy(sg + o_x, p->x, (size_t)nx * 8);
-  memcpy(sg + o_j, p->flux, (size_t)B * N * 8);
-  memcpy(sg + o_p, p->phiM, (size_t)B * 8);
-  if (W) memcpy(sg + o_k, p->k, (size_t)B * W * 8);
-  Table* tb = reinterpret_cast<Table*>(sg + o_t);
+  memcpy(in.host(ctx->stage, i_x), p->x, (size_t)nx * 8);
+  memcpy(in.host(ctx->stage, i_j), p->flux, (size_t)B * N * 8);
+  memcpy(in.host(ctx->stage, i_p), p->phiM, (size_t)B * 8);
+  if (W) memcpy(in.host(ctx->stage, i_k), p->k, (size_t)B * W * 8);
+  Table* tb = reinterpret_cast<Table*>(in.host(ctx->stage, i_t));
   for (int r = 0; r < R; ++r) {
     tb->n_lhs[r] = p->n_lhs[r];
     tb->n_rhs[r] = p->n_rhs[r];
@@ -446,13 +445,9 @@ int catbal_species(catbal_ctx* ctx, const pnp_device_view* view, const catbal_pa
   PNP_POST_HIP(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)view->stream;
   if (const int rc = reserve(ctx, entry, n_in + need_out + even((size_t)blocks * ws_block))) return rc;
-  a.x = ctx->buf + o_x;
-  a.jpre = ctx->buf + o_j;
-  a.phiM = ctx->buf + o_p;
-  a.kwall = ctx->buf + o_k;
-  a.tab = reinterpret_cast<const Table*>(ctx->buf + o_t);
+  in.place(ctx->buf);
   a.ws = place_rows(rows, ctx->buf + n_in);
-  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, sg, n_in * sizeof(double), hipMemcpyHostToDevice, st));
+  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, ctx->stage.data(), n_in * sizeof(double), hipMemcpyHostToDevice, st));
   return run(ctx, entry, st, rows, "catbal::species_kernel", P, WY, steric, [&](auto p_, auto wy_, auto steric_) {
     hipLaunchKernelGGL((species_kernel<p_(), wy_(), steric_()>), dim3((int)blocks), dim3(64 * wy_()), 0, st, a);
   });

@@ -265,21 +265,6 @@ static hipError_t resident(int* per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, couple_kernel<NB>, 64, 0);
 }
 
-// the compiled instances: NB = 2 .. 9.  f(ic<NB>)
-template <class Fn>
-static void dispatch(int NB, Fn&& f) {
-  switch (NB) {
-    case 2: f(ic<2>()); break;
-    case 3: f(ic<3>()); break;
-    case 4: f(ic<4>()); break;
-    case 5: f(ic<5>()); break;
-    case 6: f(ic<6>()); break;
-    case 7: f(ic<7>()); break;
-    case 8: f(ic<8>()); break;
-    default: f(ic<9>()); break;
-  }
-}
-
 }  // namespace catcpl
 
 static_assert(CATCPL_OK == pnp::post::OK && CATCPL_EINVAL == pnp::post::ERR_INVAL && CATCPL_ENOMEM == pnp::post::ERR_NOMEM &&
@@ -289,7 +274,7 @@ static_assert(CATCPL_WALL_DIRICHLET == pnp::team::WALL_DIRICHLET && CATCPL_WALL_
                   CATCPL_PIVOT_GROWTH_LIMIT == pnp::team::PIVOT_GROWTH_LIMIT,
               "catint_couple.h and pnp_team.h disagree");
 
-struct catcpl_ctx : pnp::team::Ctx {};
+struct catcpl_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -332,23 +317,25 @@ int catcpl_solve(catcpl_ctx* ctx, const pnp_device_view* view, const catcpl_para
 
   // the inputs, staged on the host for one copy: edge weights, control volumes, row constants, the kinetic inputs, lanes (int64 in the
   // place of doubles), the flags of non-finite inputs (int32 pairs), the table
-  const size_t o_g = grid_doubles(nx), o_K = o_g + even(nn * N), o_Kc = o_K + even(nn * N), o_Kp = o_Kc + even(nn * N * N), o_l = o_Kp + even(nn * N),
-               o_b = o_l + nn, o_t = o_b + even((nn + 1) / 2), n_in = o_t + sizeof(Table) / 8;
+  Inputs in;
+  const int i_grid = declare_grid(in, a, nx), i_g = in.add(nn * N, &a.g), i_K = in.add(nn * N, &a.K), i_Kc = in.add(nn * N * N, &a.Kc),
+            i_Kp = in.add(nn * N, &a.Kphi), i_l = in.add_unpadded(nn, &a.lanes), i_b = in.add((nn + 1) / 2, &a.badin),
+            i_t = in.add_unpadded(sizeof(Table) / 8, &a.tab);
+  const size_t n_in = in.total;
   try {
     ctx->stage.assign(n_in, 0.0);
     ctx->flags.assign(nn, 0);
   } catch (const std::bad_alloc&) {
     return fail(ctx, CATCPL_ENOMEM, "catcpl_solve: out of host memory");
   }
-  double* sg = ctx->stage.data();
-  stage_grid(sg, p, nx, N);
-  memcpy(sg + o_g, p->flux, nn * N * 8);
-  memcpy(sg + o_K, p->K, nn * N * 8);
-  memcpy(sg + o_Kc, p->Kc, nn * N * N * 8);
-  memcpy(sg + o_Kp, p->Kphi, nn * N * 8);
-  stage_lanes(sg + o_l, p);
+  stage_grid(in, ctx->stage, i_grid, p, nx, N);
+  memcpy(in.host(ctx->stage, i_g), p->flux, nn * N * 8);
+  memcpy(in.host(ctx->stage, i_K), p->K, nn * N * 8);
+  memcpy(in.host(ctx->stage, i_Kc), p->Kc, nn * N * N * 8);
+  memcpy(in.host(ctx->stage, i_Kp), p->Kphi, nn * N * 8);
+  stage_lanes(in.host(ctx->stage, i_l), p);
   {
-    int32_t* bi = reinterpret_cast<int32_t*>(sg + o_b);
+    int32_t* bi = reinterpret_cast<int32_t*>(in.host(ctx->stage, i_b));
     for (size_t i = 0; i < nn; ++i) {
       bool fin = true;
       for (int k = 0; k < N; ++k) fin = fin && std::isfinite(p->flux[i * N + k]) && std::isfinite(p->K[i * N + k]) && std::isfinite(p->Kphi[i * N + k]);
@@ -356,7 +343,7 @@ int catcpl_solve(catcpl_ctx* ctx, const pnp_device_view* view, const catcpl_para
       bi[i] = fin ? 0 : 1;
     }
   }
-  fill_reactions(reinterpret_cast<Table*>(sg + o_t), p);
+  fill_reactions(reinterpret_cast<Table*>(in.host(ctx->stage, i_t)), p);
 
   // the rows that were asked for
   const Row rows[] = {{out->T_c, &a.Tc, nn * N * N}, {out->T_phi, &a.Tphi, nn * N}, {out->dflux, &a.dflux, nn * N}, {out->lambda, &a.lam, nn},
@@ -369,27 +356,15 @@ int catcpl_solve(catcpl_ctx* ctx, const pnp_device_view* view, const catcpl_para
   // persistent grid: as many waves as the device holds at once unless the caller sizes it, no more than there are groups of systems
   const int64_t groups = ((int64_t)n + TPW - 1) / TPW;
   int64_t blocks = 0;
-  if (const int rc = persistent_blocks(ctx, entry, p->max_waves, groups, [&](int* per_cu) {
-        hipError_t oe = hipSuccess;
-        dispatch(NB, [&](auto nb) { oe = resident<decltype(nb)::value>(per_cu); });
-        return oe;
-      }, &blocks))
+  if (const int rc = persistent_waves(ctx, entry, p->max_waves, [&](int* per_cu) {
+        return dispatch_nb(NB, [&](auto nb) { return resident<decltype(nb)::value>(per_cu); });
+      }, groups, &blocks))
     return rc;
   if (const int rc = reserve(ctx, entry, n_in + need_out + n_flags)) return rc;
-  place_grid(a, ctx->buf, nx);
-  a.g = ctx->buf + o_g;
-  a.K = ctx->buf + o_K;
-  a.Kc = ctx->buf + o_Kc;
-  a.Kphi = ctx->buf + o_Kp;
-  a.lanes = reinterpret_cast<const int64_t*>(ctx->buf + o_l);
-  a.badin = reinterpret_cast<const int32_t*>(ctx->buf + o_b);
-  a.tab = reinterpret_cast<const Table*>(ctx->buf + o_t);
-  double* cur = place_rows(rows, ctx->buf + n_in);
-  a.status = reinterpret_cast<int32_t*>(cur);
+  in.place(ctx->buf);
+  a.status = reinterpret_cast<int32_t*>(place_rows(rows, ctx->buf + n_in));
   if (const int rc = run_with_status(ctx, entry, st, n_in, rows, out->status, a.status, nn, [&] {
-        hipError_t le = hipSuccess;
-        dispatch(NB, [&](auto nb) { le = launch<decltype(nb)::value>(a, blocks, st); });
-        return le;
+        return dispatch_nb(NB, [&](auto nb) { return launch<decltype(nb)::value>(a, blocks, st); });
       }))
     return rc;
   char msg[64];

@@ -259,7 +259,7 @@ static_assert(CATDRC_MAX_SPECIES == pnp::kin::MAXN && CATDRC_MAX_ADSORBATES == p
               "catint_drc.h and pnp_kin.h disagree");
 static_assert(CATDRC_MAX_STEPS <= 16 && CATDRC_MAX_SPECIES <= 32, "a branch is a 2-bit field of 32 bits, an idle species one bit");
 
-struct catdrc_ctx : pnp::kin::Ctx {};
+struct catdrc_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -283,10 +283,10 @@ int catdrc_solve(catdrc_ctx* ctx, const pnp_device_view* view, const catdrc_para
 
   const int N = p->nspecies, S = p->nadsorbates, R = p->nsteps, T = S + 1;
   const size_t sn = (size_t)p->n;
-  Stage stage;
-  if (const int rc = stage_inputs(ctx, entry, p, p->theta, from_view, 1, &stage)) return rc;   // the status
   KArgs a;
   set_args(a, view, p, from_view);
+  Stage stage;
+  if (const int rc = stage_inputs(ctx, entry, p, a, p->theta, &a.theta, from_view, 1, &stage, [](Inputs&) {})) return rc;   // the status
   a.rtol = p->residual_tol;
   const Row rows[] = {{out->dflux_dlnkf, &a.dkf, sn * R * N}, {out->dflux_dlnkb, &a.dkb, sn * R * N}, {out->dflux_drc, &a.dts, sn * R * N},
                       {out->dy_drc, &a.dyts, sn * R * T},     {out->drc, &a.xrc, sn * R * N},         {out->dflux_dG, &a.dG, sn * S * N},
@@ -294,10 +294,7 @@ int catdrc_solve(catdrc_ctx* ctx, const pnp_device_view* view, const catdrc_para
                       {out->residual, &a.resid, sn}};
   if (!rows_doubles(rows) && !out->status) return CATDRC_OK;
   const int rc = run(ctx, entry, "catdrc::control_kernel", control_kernel, view, p, stage, a, rows, lds_bytes(N, S, R), 1, out->status != nullptr,
-                     [&](const double* theta, int32_t* flags) {
-                       a.theta = theta;
-                       a.status = flags;
-                     });
+                     [&](int32_t* flags) { a.status = flags; });
   if (rc) return rc;
   if (out->status) memcpy(out->status, ctx->flags.data(), sn * sizeof(int32_t));
   return CATDRC_OK;

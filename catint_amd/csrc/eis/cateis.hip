@@ -518,22 +518,6 @@ static hipError_t resident(int* per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, electrode_kernel<NB>, 64, 0);
 }
 
-// the compiled instances: NB = 2 .. 9.  f(ic<NB>)
-template <class Fn>
-static void dispatch(int NB, Fn&& f) {
-  using pnp::post::ic;
-  switch (NB) {
-    case 2: f(ic<2>()); break;
-    case 3: f(ic<3>()); break;
-    case 4: f(ic<4>()); break;
-    case 5: f(ic<5>()); break;
-    case 6: f(ic<6>()); break;
-    case 7: f(ic<7>()); break;
-    case 8: f(ic<8>()); break;
-    default: f(ic<9>()); break;
-  }
-}
-
 // an output of a call: `per` doubles per (point, omega) pair, copied turn by turn; keep: the row exists on the device whether the caller
 // wants it or not (electrode_kernel reads it)
 struct Out {
@@ -556,18 +540,11 @@ static_assert(CATEIS_MAX_SPECIES == pnp::kin::MAXN && CATEIS_MAX_ADSORBATES == p
                   CATEIS_STATUS_INPUT == pnp::kin::STATUS_INPUT,
               "catint_eis.h and pnp_kin.h disagree");
 
-// the checks and the staging of ../pnp_kin.h report into `kin`; its message is handed on
-struct cateis_ctx : pnp::team::Ctx {
-  pnp::kin::Ctx kin;
+struct cateis_ctx : pnp::post::Ctx {
   std::vector<double> turn;   // host: the per-pair residuals of a turn
 };
 
 namespace cateis {
-
-static int kin_rc(cateis_ctx* ctx, int rc) {
-  if (rc) ctx->err = ctx->kin.err;
-  return rc;
-}
 
 // what both entry points check of the kinetic half, in catkin_solve's order; then the frequencies
 static int check_kinetic(cateis_ctx* ctx, const char* entry, const pnp_device_view* view, const cateis_params* p, const cateis_outputs* out,
@@ -575,10 +552,10 @@ static int check_kinetic(cateis_ctx* ctx, const char* entry, const pnp_device_vi
   using namespace pnp::kin;
   const std::string e(entry);
   char msg[256];
-  if (const int rc = kin_rc(ctx, check_sizes(&ctx->kin, entry, "cateis_params", "cateis_outputs", p, out))) return rc;
-  if (const int rc = kin_rc(ctx, check_drop(&ctx->kin, entry, p))) return rc;
+  if (const int rc = check_sizes(ctx, entry, "cateis_params", "cateis_outputs", p, out)) return rc;
+  if (const int rc = check_drop(ctx, entry, p)) return rc;
   if (!(p->residual_tol >= 0.0) || !std::isfinite(p->residual_tol)) return fail(ctx, ERR_INVAL, e + ": residual_tol must be >= 0 and finite");
-  if (const int rc = kin_rc(ctx, check_tables(&ctx->kin, entry, p))) return rc;
+  if (const int rc = check_tables(ctx, entry, p)) return rc;
   if (!p->theta) return fail(ctx, ERR_INVAL, e + ": theta is required (the stationary coverages)");
   if (p->nfreq < 1 || p->nfreq > CATEIS_MAX_FREQ) {
     snprintf(msg, sizeof msg, "%s: nfreq = %d outside [1, %d]", entry, p->nfreq, CATEIS_MAX_FREQ);
@@ -590,7 +567,7 @@ static int check_kinetic(cateis_ctx* ctx, const char* entry, const pnp_device_vi
       snprintf(msg, sizeof msg, "%s: omega[%d] must be >= 0 and finite", entry, f);
       return fail(ctx, ERR_INVAL, msg);
     }
-  return kin_rc(ctx, check_points(&ctx->kin, entry, view, p, from_view));
+  return check_points(ctx, entry, view, p, from_view);
 }
 
 // Both entry points behind their checks.  electrode: cateis_solve
@@ -633,20 +610,18 @@ static int run(cateis_ctx* ctx, const char* entry, const pnp_device_view* view, 
   // ---- the inputs, staged on the host for one copy: those of pnp_kin.h (the coverages, lanes and table included), the frequencies, and
   // ---- for the electrode the grid, the row constants and the reaction table of pnp_team.h
   knh::Stage stage;
-  if (const int rc = kin_rc(ctx, knh::stage_inputs(&ctx->kin, entry, p, p->theta, from_view, 0, &stage))) return rc;
-  const size_t o_f = stage.n_in, o_g = o_f + even(F), o_t = o_g + (electrode ? tmh::grid_doubles(nx) : 0),
-               n_in = o_t + (electrode ? sizeof(tmh::ReactionTable) / 8 : 0);
-  try {
-    ctx->stage.assign(n_in, 0.0);
-    memcpy(ctx->stage.data(), ctx->kin.stage.data(), stage.n_in * sizeof(double));
-  } catch (const std::bad_alloc&) {
-    return fail(ctx, ERR_NOMEM, std::string(entry) + ": out of host memory");
-  }
-  double* sg = ctx->stage.data();
-  memcpy(sg + o_f, p->omega, (size_t)F * 8);
+  int i_f = 0, i_grid = 0, i_t = 0;
+  if (const int rc = knh::stage_inputs(ctx, entry, p, ka, p->theta, &ka.theta, from_view, 0, &stage, [&](Inputs& in) {
+        i_f = in.add((size_t)F, &ka.omega);
+        if (electrode) i_grid = tmh::declare_grid(in, ea, nx), i_t = in.add_unpadded(sizeof(tmh::ReactionTable) / 8, &ea.tab);
+      }))
+    return rc;
+  const Inputs& in = stage.in;
+  const size_t n_in = in.total;
+  memcpy(in.host(ctx->stage, i_f), p->omega, (size_t)F * 8);
   if (electrode) {
-    tmh::stage_grid(sg + o_g, p, nx, N);
-    tmh::fill_reactions(reinterpret_cast<tmh::ReactionTable*>(sg + o_t), p);
+    tmh::stage_grid(in, ctx->stage, i_grid, p, nx, N);
+    tmh::fill_reactions(reinterpret_cast<tmh::ReactionTable*>(in.host(ctx->stage, i_t)), p);
     ea.nx = nx; ea.ldx = view->row_pitch; ea.nreact = p->nreactions; ea.stern = 1; ea.F = F;
     ea.c = view->c_dev; ea.phi = view->phi_dev; ea.st = view->status_dev;
     ea.steric = tmh::fill_consts(ea.k, p, N, true);
@@ -679,31 +654,21 @@ static int run(cateis_ctx* ctx, const char* entry, const pnp_device_view* view, 
   hipStream_t st = from_view ? (hipStream_t)view->stream : (hipStream_t) nullptr;
   const size_t lds = kinetic_lds_bytes(N, S);
   if (lds > 48 * 1024) PNP_POST_HIP(hipFuncSetAttribute((const void*)kinetic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int64_t kin_waves = p->max_waves, el_waves = p->max_waves;
-  if (kin_waves == 0) {
-    int cus = 0, per_cu = 0;
-    PNP_POST_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    PNP_POST_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kinetic_kernel, 64, lds));
-    kin_waves = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
-    if (electrode) {
-      hipError_t oe = hipSuccess;
-      dispatch(NB, [&](auto nb) { oe = resident<decltype(nb)::value>(&per_cu); });
-      PNP_POST_HIP(oe);
-      el_waves = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
-    }
-  }
+  // persistent grids, sized for the longest turn; a shorter last turn launches no more waves than it has groups
+  const int TPW = 64 / NB;
+  int64_t kin_waves = 0, el_waves = 0;
+  if (const int rc = persistent_waves(ctx, entry, p->max_waves, [&](int* per_cu) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kinetic_kernel, 64, lds);
+      }, ((int64_t)chunk + 63) / 64, &kin_waves))
+    return rc;
+  if (electrode)
+    if (const int rc = persistent_waves(ctx, entry, p->max_waves, [&](int* per_cu) {
+          return tmh::dispatch_nb(NB, [&](auto nb) { return resident<decltype(nb)::value>(per_cu); });
+        }, ((int64_t)chunk + TPW - 1) / TPW, &el_waves))
+      return rc;
   if (const int rc = reserve(ctx, entry, n_in + need_out)) return rc;
-  double* buf = ctx->buf;
-  ka.phiM = buf + stage.o_pm;
-  if (!from_view) ka.cs = buf + stage.o_cs, ka.phis = buf + stage.o_ps;
-  if (p->sigma) ka.sigma = buf + stage.o_sg;
-  if (p->off) ka.off = buf + stage.o_off;
-  if (p->gamma && N) ka.gamma = buf + stage.o_gm;
-  ka.theta = buf + stage.o_th;
-  ka.lanes = reinterpret_cast<const int64_t*>(buf + stage.o_l);
-  ka.omega = buf + o_f;
-  const knh::Table* ktab = reinterpret_cast<const knh::Table*>(buf + stage.o_t);
-  double* cur = buf + n_in;
+  in.place(ctx->buf);
+  double* cur = ctx->buf + n_in;
   for (const Out& o : outs)
     if (o.placed()) {
       *o.dev = cur;
@@ -712,10 +677,8 @@ static int run(cateis_ctx* ctx, const char* entry, const pnp_device_view* view, 
   ka.kstat = reinterpret_cast<int32_t*>(cur);
   cur += even((chunk + 1) / 2);
   if (electrode) {
-    tmh::place_grid(ea, buf + o_g, nx);
     ea.lanes = ka.lanes;
     ea.omega = ka.omega;
-    ea.tab = reinterpret_cast<const tmh::ReactionTable*>(buf + o_t);
     ea.Kc = ka.Kc;
     ea.Kphi = ka.Kphi;
     ea.kstat = ka.kstat;
@@ -723,37 +686,29 @@ static int run(cateis_ctx* ctx, const char* entry, const pnp_device_view* view, 
   }
   const int32_t* status_dev = electrode ? ea.status : ka.kstat;
 
-  PNP_POST_HIP(hipMemcpyAsync(buf, sg, n_in * sizeof(double), hipMemcpyHostToDevice, st));
-  if (!ctx->ev0) PNP_POST_HIP(hipEventCreate(&ctx->ev0));
-  if (!ctx->ev1) PNP_POST_HIP(hipEventCreate(&ctx->ev1));
-  ctx->kernel_ms = -1.0f;
+  // ---- the turns: the staged inputs go up with the first ----
   float total_ms = 0.0f;
-  const int TPW = 64 / NB;
   for (size_t s0 = 0; s0 < nsys; s0 += chunk) {
     const size_t ns = std::min(chunk, nsys - s0);
     ka.s0 = (int64_t)s0;
     ka.ns = (int64_t)ns;
     ea.s0 = (int64_t)s0;
     ea.nsys = (int64_t)ns;
-    PNP_POST_HIP(hipEventRecord(ctx->ev0, st));
-    const int64_t kb = std::min<int64_t>(std::max<int64_t>(kin_waves, 1), ((int64_t)ns + 63) / 64);
-    hipLaunchKernelGGL(kinetic_kernel, dim3((int)kb), dim3(64), lds, st, ka, ktab);
-    PNP_POST_HIP(hipGetLastError());
-    if (electrode) {
-      const int64_t eb = std::min<int64_t>(std::max<int64_t>(el_waves, 1), ((int64_t)ns + TPW - 1) / TPW);
-      hipError_t le = hipSuccess;
-      dispatch(NB, [&](auto nb) { le = launch<decltype(nb)::value>(ea, eb, st); });
-      PNP_POST_HIP(le);
-      PNP_POST_HIP(hipGetLastError());
-    }
-    PNP_POST_HIP(hipEventRecord(ctx->ev1, st));
-    for (const Out& o : outs)
-      if (o.host && o.per) PNP_POST_HIP(hipMemcpyAsync(o.host + s0 * o.per, *o.dev, ns * o.per * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out->residual) PNP_POST_HIP(hipMemcpyAsync(ctx->turn.data(), ka.resid, ns * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out->status) PNP_POST_HIP(hipMemcpyAsync(ctx->flags.data(), status_dev, ns * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    PNP_POST_HIP(hipStreamSynchronize(st));
+    Row rows[sizeof outs / sizeof outs[0] + 1];
+    size_t nr = 0;
+    for (const Out& o : outs) rows[nr++] = Row{o.host ? o.host + s0 * o.per : nullptr, o.dev, ns * o.per};
+    rows[nr] = Row{out->residual ? ctx->turn.data() : nullptr, &ka.resid, ns};
     float ms = 0.0f;
-    PNP_POST_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    if (const int rc = launch_and_fetch(ctx, entry, st, s0 == 0 ? n_in : 0, rows, Flags{status_dev, ns, out->status != nullptr}, &ms, [&] {
+          const int64_t kb = std::min<int64_t>(kin_waves, ((int64_t)ns + 63) / 64);
+          hipLaunchKernelGGL(kinetic_kernel, dim3((int)kb), dim3(64), lds, st, ka, stage.tab);
+          if (!electrode) return hipSuccess;
+          const hipError_t ke = hipGetLastError();
+          if (ke != hipSuccess) return ke;
+          const int64_t eb = std::min<int64_t>(el_waves, ((int64_t)ns + TPW - 1) / TPW);
+          return tmh::dispatch_nb(NB, [&](auto nb) { return launch<decltype(nb)::value>(ea, eb, st); });
+        }))
+      return rc;
     total_ms += ms;
     if (out->status) memcpy(out->status + s0, ctx->flags.data(), ns * sizeof(int32_t));
     if (out->residual)

@@ -345,10 +345,7 @@ static_assert(CATEQ_OK == pnp::post::OK && CATEQ_EINVAL == pnp::post::ERR_INVAL 
                   CATEQ_EDEVICE == pnp::post::ERR_DEVICE && CATEQ_MAX_NX == pnp::post::MAX_NX && CATEQ_MAX_SPECIES == pnp::post::MAX_SPECIES,
               "catint_equil.h and pnp_post.h disagree");
 
-struct cateq_ctx : pnp::post::Ctx {
-  std::vector<double> stage;    // host: the grid weights and the per-lane parameters of the call in flight, one copy
-  std::vector<int32_t> flags;   // host: status and iterations as the kernel wrote them
-};
+struct cateq_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -428,22 +425,25 @@ int cateq_solve(cateq_ctx* ctx, const pnp_device_view* view, const cateq_params*
   choose_shape(nx, &P, &WY);
 
   // the grid weights and the per-lane parameters, staged on the host for one copy
-  const size_t o_w = 0, o_pv = o_w + even((size_t)nx - 1), o_sp = o_pv + even((size_t)nx), o_lp = o_sp + MAXS * SPF, n_in = o_lp + (size_t)n * LP;
+  Inputs in;
+  const int i_w = in.add((size_t)nx - 1, &a.w), i_pv = in.add((size_t)nx, &a.pv), i_sp = in.add((size_t)MAXS * SPF, &a.sp),
+            i_lp = in.add_unpadded((size_t)n * LP, &a.lp);
+  const size_t n_in = in.total;
   try {
     ctx->stage.assign(n_in, 0.0);
     ctx->flags.assign((size_t)2 * n, 0);
   } catch (const std::bad_alloc&) {
     return fail(ctx, CATEQ_ENOMEM, "cateq_solve: out of host memory");
   }
-  double* sg = ctx->stage.data();
+  double *sw = in.host(ctx->stage, i_w), *spv = in.host(ctx->stage, i_pv), *ssp = in.host(ctx->stage, i_sp), *slp = in.host(ctx->stage, i_lp);
   const double pe = p->dx * p->dx / p->eps;
-  for (int e = 0; e < nx - 1; ++e) sg[o_w + e] = p->dx / (p->x[e + 1] - p->x[e]);
+  for (int e = 0; e < nx - 1; ++e) sw[e] = p->dx / (p->x[e + 1] - p->x[e]);
   for (int i = 0; i < nx; ++i) {
     const double hl = i > 0 ? p->x[i] - p->x[i - 1] : 0.0, hr = i < nx - 1 ? p->x[i + 1] - p->x[i] : 0.0;
-    sg[o_pv + i] = pe * (0.5 * (hr + hl) / p->dx);
+    spv[i] = pe * (0.5 * (hr + hl) / p->dx);
   }
   for (int k = 0; k < N; ++k) {
-    double* f = sg + o_sp + k * SPF;
+    double* f = ssp + k * SPF;
     f[0] = p->charges[k] * p->beta;
     f[1] = p->charges[k];
     f[2] = f[1] * f[0];
@@ -451,7 +451,7 @@ int cateq_solve(cateq_ctx* ctx, const pnp_device_view* view, const cateq_params*
     f[4] = vol[k] * f[0];
   }
   for (int64_t i = 0; i < n; ++i) {
-    double* l = sg + o_lp + i * LP;
+    double* l = slp + i * LP;
     double phi0 = 0.0;
     for (int k = 0; k < N; ++k) phi0 += vol[k] * p->c_bulk[i * N + k];
     l[0] = p->phiM[i];
@@ -463,14 +463,11 @@ int cateq_solve(cateq_ctx* ctx, const pnp_device_view* view, const cateq_params*
   hipStream_t st = (hipStream_t)view->stream;
   const size_t n_c = (size_t)n * N * pitch, n_phi = (size_t)n * pitch;
   if (const int rc = reserve(ctx, entry, n_in + n_c + n_phi + even((size_t)n))) return rc;   // 2 n int32 = n doubles
-  a.w = ctx->buf + o_w;
-  a.pv = ctx->buf + o_pv;
-  a.lp = ctx->buf + o_lp;
-  a.sp = ctx->buf + o_sp;
+  in.place(ctx->buf);
   a.oc = ctx->buf + n_in;
   a.ophi = a.oc + n_c;
   a.oflag = reinterpret_cast<int32_t*>(a.ophi + n_phi);
-  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, sg, n_in * sizeof(double), hipMemcpyHostToDevice, st));
+  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, ctx->stage.data(), n_in * sizeof(double), hipMemcpyHostToDevice, st));
   int cus = 0;
   PNP_POST_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
   if (!ctx->ev0) PNP_POST_HIP(hipEventCreate(&ctx->ev0));

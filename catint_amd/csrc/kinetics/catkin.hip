@@ -171,7 +171,7 @@ static_assert(CATKIN_MAX_SPECIES == pnp::kin::MAXN && CATKIN_MAX_ADSORBATES == p
                   CATKIN_DROP_STERN == pnp::kin::DROP_STERN,
               "catint_kinetics.h and pnp_kin.h disagree");
 
-struct catkin_ctx : pnp::kin::Ctx {};
+struct catkin_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -195,10 +195,10 @@ int catkin_solve(catkin_ctx* ctx, const pnp_device_view* view, const catkin_para
 
   const int N = p->nspecies, S = p->nadsorbates, R = p->nsteps, T = S + 1;
   const size_t sn = (size_t)p->n;
-  Stage stage;
-  if (const int rc = stage_inputs(ctx, entry, p, p->theta_guess, from_view, 2, &stage)) return rc;   // status and iterations
   KArgs a;
   set_args(a, view, p, from_view);
+  Stage stage;
+  if (const int rc = stage_inputs(ctx, entry, p, a, p->theta_guess, &a.guess, from_view, 2, &stage, [](Inputs&) {})) return rc;   // status and iterations
   a.maxit = p->maxit;
   a.tol = p->tol;
   const Row rows[] = {{out->theta, &a.theta, sn * T},       {out->rate, &a.rate, sn * R},           {out->rate_gross, &a.gross, sn * R},
@@ -207,8 +207,7 @@ int catkin_solve(catkin_ctx* ctx, const pnp_device_view* view, const catkin_para
   a.sens = (out->dflux_dc && N) || (out->dflux_dphi && N);
   if (!rows_doubles(rows) && !out->status && !out->iterations) return CATKIN_OK;
   const int rc = run(ctx, entry, "catkin::steady_kernel", steady_kernel, view, p, stage, a, rows, lds_bytes(N, S), 2, out->status || out->iterations,
-                     [&](const double* guess, int32_t* flags) {
-                       if (p->theta_guess) a.guess = guess;
+                     [&](int32_t* flags) {
                        a.status = flags;
                        a.iters = flags + sn;
                      });

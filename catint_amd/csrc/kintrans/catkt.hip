@@ -310,7 +310,7 @@ static_assert(CATKT_OK == pnp::post::OK && CATKT_EINVAL == pnp::post::ERR_INVAL 
               "catint_kintrans.h and pnp_post.h disagree");
 static_assert(CATKT_INPUT == pnp::kin::STATUS_INPUT, "catint_kintrans.h and pnp_kin.h disagree");
 
-struct catkt_ctx : pnp::kin::Ctx {};
+struct catkt_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -357,19 +357,14 @@ int catkt_solve(catkt_ctx* ctx, const pnp_device_view* view, const catkt_params*
 
   const int N = p->nspecies, S = p->nadsorbates, T = S + 1;
   const size_t sn = (size_t)p->n, so = (size_t)p->n_out;
-  Stage stage;
-  if (const int rc = stage_inputs(ctx, entry, p, p->theta0, from_view, 4, &stage)) return rc;   // status and the three counters
-  // the output times behind the staged inputs of the shared layout: one copy still
-  const size_t o_tout = stage.n_in;
-  stage.n_in += even(so);
-  try {
-    ctx->stage.resize(stage.n_in, 0.0);
-  } catch (const std::bad_alloc&) {
-    return fail(ctx, CATKT_ENOMEM, "catkt_solve: out of host memory");
-  }
-  memcpy(ctx->stage.data() + o_tout, p->t_out, so * sizeof(double));
   KArgs a;
   set_args(a, view, p, from_view);
+  // the output times behind the staged inputs of the shared layout: one copy still
+  Stage stage;
+  int i_tout = 0;
+  if (const int rc = stage_inputs(ctx, entry, p, a, p->theta0, &a.theta0, from_view, 4, &stage, [&](Inputs& in) { i_tout = in.add(so, &a.tout); }))
+    return rc;   // status and the three counters
+  memcpy(stage.in.host(ctx->stage, i_tout), p->t_out, so * sizeof(double));
   a.nmaxit = p->newton_maxit;
   a.max_steps = p->max_steps;
   a.n_out = p->n_out;
@@ -382,9 +377,7 @@ int catkt_solve(catkt_ctx* ctx, const pnp_device_view* view, const catkt_params*
                       {out->drift, &a.drift, sn * so},     {out->t_reached, &a.treached, sn}};
   if (!rows_doubles(rows) && !out->status && !out->steps) return CATKT_OK;
   const int rc = run(ctx, entry, "catkt::transient_kernel", transient_kernel, view, p, stage, a, rows, lds_bytes(N, S), 4, out->status || out->steps,
-                     [&](const double* theta0, int32_t* flags) {
-                       if (p->theta0) a.theta0 = theta0;
-                       a.tout = ctx->buf + o_tout;
+                     [&](int32_t* flags) {
                        a.status = flags;
                        a.steps = flags + sn;
                      });

@@ -35,16 +35,9 @@ namespace catmodes {
 
 using namespace pnp::team;
 
-constexpr int MAXW = PNP_MAX_WALL_REACTIONS;
 constexpr double BREAK2 = CATMODES_BREAKDOWN * CATMODES_BREAKDOWN;
 
-// the reaction and wall tables of one call, flattened on the host (every index validated there)
-struct Table : ReactionTable {
-  int32_t wspecies[MAXW], pad_[MAXW];
-  double nu[MAXW][MAXS + 1];        // column N: 0
-  double alpha[MAXW], sat[MAXW];
-};
-static_assert(sizeof(Table) % 8 == 0, "the table is copied as doubles");
+using Table = pnp::team::WallTable;   // the reaction and wall tables of one call
 
 struct KArgs {
   int32_t nx, ldx, nreact, nwall, stern, steric, m, K;
@@ -522,21 +515,6 @@ static hipError_t resident(int* per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, modes_kernel<NB, CATMODES_MAX_SUBSPACE>, 64, 0);
 }
 
-// the compiled instances: NB = 2 .. 9, one width of the carried columns.  f(ic<NB>)
-template <class Fn>
-static void dispatch(int NB, Fn&& f) {
-  switch (NB) {
-    case 2: f(ic<2>()); break;
-    case 3: f(ic<3>()); break;
-    case 4: f(ic<4>()); break;
-    case 5: f(ic<5>()); break;
-    case 6: f(ic<6>()); break;
-    case 7: f(ic<7>()); break;
-    case 8: f(ic<8>()); break;
-    default: f(ic<9>()); break;
-  }
-}
-
 }  // namespace catmodes
 
 static_assert(CATMODES_OK == pnp::post::OK && CATMODES_EINVAL == pnp::post::ERR_INVAL && CATMODES_ENOMEM == pnp::post::ERR_NOMEM &&
@@ -546,7 +524,7 @@ static_assert(CATMODES_WALL_DIRICHLET == pnp::team::WALL_DIRICHLET && CATMODES_W
                   CATMODES_PIVOT_GROWTH_LIMIT == pnp::team::PIVOT_GROWTH_LIMIT,
               "catint_modes.h and pnp_team.h disagree");
 
-struct catmodes_ctx : pnp::team::Ctx {};
+struct catmodes_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -570,18 +548,9 @@ int catmodes_solve(catmodes_ctx* ctx, const pnp_device_view* view, const catmode
   if (const int rc = check_species(ctx, entry, p, N)) return rc;
   const int R = p->nreactions, W = p->n_wall, m = p->subspace, K = p->iterations;
   if (const int rc = check_nreactions(ctx, entry, R)) return rc;
-  if (W < 0 || W > PNP_MAX_WALL_REACTIONS) {
-    snprintf(msg, sizeof msg, "catmodes_solve: n_wall = %d outside [0, %d]", W, PNP_MAX_WALL_REACTIONS);
-    return fail(ctx, CATMODES_EINVAL, msg);
-  }
+  if (const int rc = check_nwall(ctx, entry, W)) return rc;
   if (const int rc = check_reactions(ctx, entry, p, N)) return rc;
-  if (W > 0 && !p->k) return fail(ctx, CATMODES_EINVAL, "catmodes_solve: n_wall > 0 needs the rate constants k");
-  if (W > 0 && (!p->wall_species || !p->nu)) return fail(ctx, CATMODES_EINVAL, "catmodes_solve: n_wall > 0 needs wall_species and nu");
-  for (int r = 0; r < W; ++r)
-    if (p->wall_species[r] < -1 || p->wall_species[r] >= N) {
-      snprintf(msg, sizeof msg, "catmodes_solve: wall reaction %d names species index %d outside [-1, %d)", r, p->wall_species[r], N);
-      return fail(ctx, CATMODES_EINVAL, msg);
-    }
+  if (const int rc = check_wall(ctx, entry, p, N)) return rc;
   if (!p->phiM) return fail(ctx, CATMODES_EINVAL, "catmodes_solve: phiM is required");
   if (m < 1 || m > CATMODES_MAX_SUBSPACE) {
     snprintf(msg, sizeof msg, "catmodes_solve: subspace = %d outside [1, %d]", m, CATMODES_MAX_SUBSPACE);
@@ -612,24 +581,26 @@ int catmodes_solve(catmodes_ctx* ctx, const pnp_device_view* view, const catmode
 
   // the inputs, staged on the host for one copy: edge weights, control volumes, row constants, potentials, rate constants, lanes (int64
   // in the place of doubles), the flags of non-finite inputs (int32 pairs), the start vectors, tables
-  const size_t o_p = grid_doubles(nx), o_k = o_p + even(B), o_l = o_k + even((size_t)B * W), o_b = o_l + nn, o_s = o_b + even((nn + 1) / 2),
-               o_t = o_s + even(nstart), n_in = o_t + sizeof(Table) / 8;
+  Inputs in;
+  const int i_grid = declare_grid(in, a, nx), i_p = in.add((size_t)B, &a.phiM), i_k = in.add((size_t)B * W, &a.kwall),
+            i_l = in.add_unpadded(nn, &a.lanes), i_b = in.add((nn + 1) / 2, &a.badin), i_s = in.add(nstart, &a.start),
+            i_t = in.add_unpadded(sizeof(Table) / 8, &a.tab);
+  const size_t n_in = in.total;
   try {
     ctx->stage.assign(n_in, 0.0);
     ctx->flags.assign(nn, 0);
   } catch (const std::bad_alloc&) {
     return fail(ctx, CATMODES_ENOMEM, "catmodes_solve: out of host memory");
   }
-  double* sg = ctx->stage.data();
-  stage_grid(sg, p, nx, N);
-  memcpy(sg + o_p, p->phiM, (size_t)B * 8);
-  if (W) memcpy(sg + o_k, p->k, (size_t)B * W * 8);
-  stage_lanes(sg + o_l, p);
-  memcpy(sg + o_s, p->start, nstart * 8);
+  stage_grid(in, ctx->stage, i_grid, p, nx, N);
+  memcpy(in.host(ctx->stage, i_p), p->phiM, (size_t)B * 8);
+  if (W) memcpy(in.host(ctx->stage, i_k), p->k, (size_t)B * W * 8);
+  stage_lanes(in.host(ctx->stage, i_l), p);
+  memcpy(in.host(ctx->stage, i_s), p->start, nstart * 8);
   {
     bool start_fin = true;
     for (size_t i = 0; i < nstart; ++i) start_fin = start_fin && std::isfinite(p->start[i]);
-    int32_t* bi = reinterpret_cast<int32_t*>(sg + o_b);
+    int32_t* bi = reinterpret_cast<int32_t*>(in.host(ctx->stage, i_b));
     for (size_t i = 0; i < nn; ++i) {
       const int64_t b = p->lanes ? p->lanes[i] : (int64_t)i;
       bool fin = start_fin && std::isfinite(p->phiM[b]);
@@ -637,14 +608,9 @@ int catmodes_solve(catmodes_ctx* ctx, const pnp_device_view* view, const catmode
       bi[i] = fin ? 0 : 1;
     }
   }
-  Table* tb = reinterpret_cast<Table*>(sg + o_t);
+  Table* tb = reinterpret_cast<Table*>(in.host(ctx->stage, i_t));
   fill_reactions(tb, p);
-  for (int r = 0; r < W; ++r) {
-    tb->wspecies[r] = p->wall_species[r];
-    tb->alpha[r] = p->alpha ? p->alpha[r] : 0.0;
-    tb->sat[r] = p->saturation ? p->saturation[r] : 0.0;
-    for (int k = 0; k < N; ++k) tb->nu[r][k] = p->nu[r * N + k];
-  }
+  fill_wall(tb, p, N);
 
   // the rows that were asked for
   const Row rows[] = {{out->ritz, &a.ritz, nn * m * m}, {out->gram, &a.gram, nn * m * m}, {out->basis, &a.basis, nn * m * E}};
@@ -657,11 +623,9 @@ int catmodes_solve(catmodes_ctx* ctx, const pnp_device_view* view, const catmode
   // and no more than the workspace cap admits (at least one)
   const int64_t groups = ((int64_t)n + TPW - 1) / TPW;
   int64_t blocks = 0;
-  if (const int rc = persistent_blocks(ctx, entry, p->max_waves, groups, [&](int* per_cu) {
-        hipError_t oe = hipSuccess;
-        dispatch(NB, [&](auto nb) { oe = resident<decltype(nb)::value>(per_cu); });
-        return oe;
-      }, &blocks))
+  if (const int rc = persistent_waves(ctx, entry, p->max_waves, [&](int* per_cu) {
+        return dispatch_nb(NB, [&](auto nb) { return resident<decltype(nb)::value>(per_cu); });
+      }, groups, &blocks))
     return rc;
   size_t cap = (size_t)2 << 30;
   if (const char* e = getenv("CATMODES_WORKSPACE_BYTES")) {
@@ -672,22 +636,13 @@ int catmodes_solve(catmodes_ctx* ctx, const pnp_device_view* view, const catmode
   const size_t per_wave = (size_t)TPW * (size_t)a.slot;   // doubles
   blocks = std::min<int64_t>(blocks, std::max<int64_t>(1, (int64_t)(cap / 8 / per_wave)));
   const size_t ws_doubles = (size_t)blocks * per_wave;
-  const size_t o_ws = even(n_in + need_out + n_flags);   // the slots are read and written 16 bytes at a time
-  if (const int rc = reserve(ctx, entry, o_ws + ws_doubles)) return rc;
-  place_grid(a, ctx->buf, nx);
-  a.phiM = ctx->buf + o_p;
-  a.kwall = ctx->buf + o_k;
-  a.lanes = reinterpret_cast<const int64_t*>(ctx->buf + o_l);
-  a.badin = reinterpret_cast<const int32_t*>(ctx->buf + o_b);
-  a.start = ctx->buf + o_s;
-  a.tab = reinterpret_cast<const Table*>(ctx->buf + o_t);
-  double* cur = place_rows(rows, ctx->buf + n_in);
-  a.flags = reinterpret_cast<int32_t*>(cur);
-  a.ws = ctx->buf + o_ws;
+  const size_t ws_at = even(n_in + need_out + n_flags);   // the slots are read and written 16 bytes at a time
+  if (const int rc = reserve(ctx, entry, ws_at + ws_doubles)) return rc;
+  in.place(ctx->buf);
+  a.flags = reinterpret_cast<int32_t*>(place_rows(rows, ctx->buf + n_in));
+  a.ws = ctx->buf + ws_at;
   if (const int rc = run_with_status(ctx, entry, st, n_in, rows, out->status, a.flags, nn, [&] {
-        hipError_t le = hipSuccess;
-        dispatch(NB, [&](auto nb) { le = launch<decltype(nb)::value>(a, blocks, st); });
-        return le;
+        return dispatch_nb(NB, [&](auto nb) { return launch<decltype(nb)::value>(a, blocks, st); });
       }))
     return rc;
   snprintf(msg, sizeof msg, "catmodes::modes_kernel<%d, %d>", NB, PC);

@@ -1,7 +1,8 @@
-// What the two libraries that work on a mean-field surface microkinetic model with ONE OPERATING POINT PER LANE have in common
-// (kinetics/catkin.hip, drc/catdrc.hip): the tables of a call, the rate constants and rates, the scaled rows of the steady state, the
-// per-lane LU, and the host code around a launch.  Each library is one translation unit and compiles its own copy: nothing here is
-// exported.  The frame of an entry point (context, rows, reserve) is that of pnp_post.h.  gfx950 / MI355X only.
+// What the libraries that work on a mean-field surface microkinetic model with ONE OPERATING POINT PER LANE have in common
+// (kinetics/catkin.hip, drc/catdrc.hip, kintrans/catkt.hip, scfkin/catscfkin.hip, eis/cateis.hip): the tables of a call, the rate constants
+// and rates, the scaled rows of the steady state, the per-lane LU, and the host code around a launch.  Each library is one translation
+// unit and compiles its own copy: nothing here is exported.  The frame of an entry point (context, staged inputs, rows, reserve, the
+// tail) is that of pnp_post.h and pnp_stage.h.  gfx950 / MI355X only.
 //
 // Mapping: one operating point per lane, one wave per workgroup, persistent waves walking groups of 64 points.  No lane ever reads what
 // another lane wrote, so there is no barrier and no cross-lane exchange; the only per-lane control is the row a lane chooses as its
@@ -367,12 +368,7 @@ __device__ __forceinline__ void steady_fluxes(const KA& A, const Table& tb, cons
   }
 }
 
-// ---- host: the context ---------------------------------------------------------------------------------------------------------------
-struct Ctx : pnp::post::Ctx {
-  std::vector<double> stage;    // host: the inputs of the call in flight, one copy
-  std::vector<int32_t> flags;   // host: the int32 rows (status, iterations) as the kernel wrote them
-};
-
+// (the context is pnp::post::Ctx)
 // ---- host: what an entry point checks, in three parts; the library's own checks stand between them.  0 or the code.  Params:
 // ---- catkin_params / catdrc_params, read by the member names the two share; entry: the exported function, the head of every message --
 static bool posfin(double v) { return v > 0.0 && std::isfinite(v); }
@@ -511,10 +507,12 @@ static int check_points(Ctx* ctx, const char* entry, const pnp_device_view* view
 }
 
 // ---- host: the inputs of a call, staged for one copy -----------------------------------------------------------------------------------
-// offsets in doubles into the staging vector and, after the copy, into the context's device buffer
 struct Stage {
-  bool from_view;      // the surface state comes from the view, not from csurf and phi_surface
-  size_t o_pm, o_cs, o_ps, o_sg, o_off, o_gm, o_th, o_l, o_t, n_in;   // phiM, csurf, phi_surface, sigma, off, gamma, coverages, lanes, Table; all
+  bool from_view;     // the surface state comes from the view, not from csurf and phi_surface
+  Inputs in;          // the inputs every kernel here reads, then what the library declared behind them
+  const Table* tab;   // device: the table, a kernel argument of its own (read-only: scalar loads)
+  Stage() = default;
+  Stage(const Stage&) = delete;   // `in` holds the address of `tab`
 };
 
 template <class Params>
@@ -530,43 +528,44 @@ static void fill_table(Table* tb, const Params* p) {
   for (int t = 0; t < T; ++t) tb->ns[t] = p->site_count[t];
 }
 
-// Lays out and fills ctx->stage, the Table included, and sizes ctx->flags to `flag_rows` int32 rows of n.  theta: the coverages
-// [n][T] the library takes (catkin's optional guess, catdrc's state), or null
-template <class Params>
-static int stage_inputs(Ctx* ctx, const char* entry, const Params* p, const double* theta, bool from_view, int flag_rows, Stage* s) {
+// Declares the inputs every kernel here reads, in this order, with the members of the arguments `a` that take their device addresses:
+// phiM; csurf and phi_surface (not from the view); sigma, off, gamma (where given); the coverages [n][T] the library takes (theta:
+// catkin's optional guess, catdrc's state, or null; their address goes to *theta_dev); the lanes; the Table (s->tab).  more(s->in)
+// declares what the library stages behind them.  Then sizes ctx->stage for all of it, fills what was declared here, and sizes
+// ctx->flags to `flag_rows` int32 rows of n.
+template <class KA, class Params, class More>
+static int stage_inputs(Ctx* ctx, const char* entry, const Params* p, KA& a, const double* theta, const double** theta_dev, bool from_view,
+                        int flag_rows, Stage* s, More&& more) {
   const int N = p->nspecies, R = p->nsteps, T = p->nadsorbates + 1;
   const int64_t n = p->n;
   const size_t sn = (size_t)n;
   s->from_view = from_view;
-  s->o_pm = 0;
-  s->o_cs = s->o_pm + even(sn);
-  s->o_ps = s->o_cs + (from_view ? 0 : even(sn * N));
-  s->o_sg = s->o_ps + (from_view ? 0 : even(sn));
-  s->o_off = s->o_sg + (p->sigma ? even(sn) : 0);
-  s->o_gm = s->o_off + (p->off ? sn * R * 2 : 0);
-  s->o_th = s->o_gm + (p->gamma ? even(sn * N) : 0);
-  s->o_l = s->o_th + (theta ? even(sn * T) : 0);
-  s->o_t = s->o_l + sn;
-  s->n_in = s->o_t + sizeof(Table) / 8;
+  Inputs& in = s->in;
+  const int i_pm = in.add(sn, &a.phiM);
+  const int i_cs = from_view ? -1 : in.add(sn * N, &a.cs), i_ps = from_view ? -1 : in.add(sn, &a.phis);
+  const int i_sg = p->sigma ? in.add(sn, &a.sigma) : -1, i_off = p->off ? in.add(sn * R * 2, &a.off) : -1;
+  const int i_gm = (p->gamma && N) ? in.add(sn * N, &a.gamma) : -1, i_th = theta ? in.add(sn * T, theta_dev) : -1;
+  const int i_l = in.add_unpadded(sn, &a.lanes), i_t = in.add_unpadded(sizeof(Table) / 8, &s->tab);
+  more(in);
   try {
-    ctx->stage.assign(s->n_in, 0.0);
+    ctx->stage.assign(in.total, 0.0);
     ctx->flags.assign(flag_rows * sn, 0);
   } catch (const std::bad_alloc&) {
     return fail(ctx, ERR_NOMEM, std::string(entry) + ": out of host memory");
   }
-  double* sg = ctx->stage.data();
-  memcpy(sg + s->o_pm, p->phiM, sn * 8);
+  std::vector<double>& sg = ctx->stage;
+  memcpy(in.host(sg, i_pm), p->phiM, sn * 8);
   if (!from_view) {
-    if (N) memcpy(sg + s->o_cs, p->csurf, sn * N * 8);
-    memcpy(sg + s->o_ps, p->phi_surface, sn * 8);
+    if (N) memcpy(in.host(sg, i_cs), p->csurf, sn * N * 8);
+    memcpy(in.host(sg, i_ps), p->phi_surface, sn * 8);
   }
-  if (p->sigma) memcpy(sg + s->o_sg, p->sigma, sn * 8);
-  if (p->off) memcpy(sg + s->o_off, p->off, sn * R * 2 * 8);
-  if (p->gamma && N) memcpy(sg + s->o_gm, p->gamma, sn * N * 8);
-  if (theta) memcpy(sg + s->o_th, theta, sn * T * 8);
-  int64_t* l = reinterpret_cast<int64_t*>(sg + s->o_l);
+  if (p->sigma) memcpy(in.host(sg, i_sg), p->sigma, sn * 8);
+  if (p->off) memcpy(in.host(sg, i_off), p->off, sn * R * 2 * 8);
+  if (p->gamma && N) memcpy(in.host(sg, i_gm), p->gamma, sn * N * 8);
+  if (theta) memcpy(in.host(sg, i_th), theta, sn * T * 8);
+  int64_t* l = reinterpret_cast<int64_t*>(in.host(sg, i_l));
   for (int64_t i = 0; i < n; ++i) l[i] = (from_view && p->lanes) ? p->lanes[i] : i;
-  fill_table(reinterpret_cast<Table*>(sg + s->o_t), p);
+  fill_table(reinterpret_cast<Table*>(in.host(sg, i_t)), p);
   return OK;
 }
 
@@ -583,53 +582,33 @@ static void set_args(KA& a, const pnp_device_view* view, const Params* p, bool f
   }
 }
 
-// The tail of an entry point.  One wave per block: max_waves of them, or (0) what the device holds at `lds` bytes each; the staged
-// inputs to the device buffer, the output rows and `flag_rows` int32 rows of n behind them; `kernel` between the context's two events
-// (last_kernel_ms) under the name `kernel_name`; the wanted rows back, the int32 rows back to ctx->flags when want_flags; the stream
-// drained.  own(const double* theta, int32_t* flags) puts the device addresses of the staged coverages (where there are any) and of
-// the int32 rows into the arguments `a` under the library's own names.
+// The tail of an entry point.  One wave per block: max_waves of them, or (0) what the device holds at `lds` bytes each; the output
+// rows and `flag_rows` int32 rows of n behind the staged inputs; own(int32_t* flags) puts the device address of the int32 rows into
+// the arguments `a` under the library's own names; then pnp::post::launch_and_fetch with `kernel`, whose name `kernel_name` is
+// recorded (the int32 rows come back to ctx->flags when want_flags).
 template <class KA, class Params, size_t NR, class F>
 static int run(Ctx* ctx, const char* entry, const char* kernel_name, void (*kernel)(const KA, const Table*), const pnp_device_view* view, const Params* p,
                const Stage& s, KA& a, const Row (&rows)[NR], size_t lds, int flag_rows, bool want_flags, F&& own) {
-  const bool from_view = s.from_view;
   const int64_t n = p->n;
-  const size_t sn = (size_t)n;
+  const size_t sn = (size_t)n, n_in = s.in.total;
   const size_t need_out = rows_doubles(rows), n_flags = even(sn) * flag_rows / 2;
   PNP_POST_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = from_view ? (hipStream_t)view->stream : (hipStream_t) nullptr;
+  hipStream_t st = s.from_view ? (hipStream_t)view->stream : (hipStream_t) nullptr;
   if (lds > 48 * 1024) PNP_POST_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t groups = (n + 63) / 64;
-  int64_t blocks = p->max_waves;
-  if (blocks == 0) {
-    int cus = 0, per_cu = 0;
-    PNP_POST_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    PNP_POST_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, lds));
-    blocks = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
-  }
-  blocks = std::min(std::max<int64_t>(blocks, 1), groups);
-  if (const int rc = reserve(ctx, entry, s.n_in + need_out + n_flags)) return rc;
-  a.phiM = ctx->buf + s.o_pm;
-  if (!from_view) a.cs = ctx->buf + s.o_cs, a.phis = ctx->buf + s.o_ps;
-  if (p->sigma) a.sigma = ctx->buf + s.o_sg;
-  if (p->off) a.off = ctx->buf + s.o_off;
-  if (p->gamma && p->nspecies) a.gamma = ctx->buf + s.o_gm;
-  a.lanes = reinterpret_cast<const int64_t*>(ctx->buf + s.o_l);
-  const Table* tab = reinterpret_cast<const Table*>(ctx->buf + s.o_t);   // a kernel argument of its own (read-only: scalar loads)
-  int32_t* flags_dev = reinterpret_cast<int32_t*>(place_rows(rows, ctx->buf + s.n_in));
-  own(ctx->buf + s.o_th, flags_dev);
-  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, ctx->stage.data(), s.n_in * sizeof(double), hipMemcpyHostToDevice, st));
-  if (!ctx->ev0) PNP_POST_HIP(hipEventCreate(&ctx->ev0));
-  if (!ctx->ev1) PNP_POST_HIP(hipEventCreate(&ctx->ev1));
-  ctx->kernel_ms = -1.0f;
-  PNP_POST_HIP(hipEventRecord(ctx->ev0, st));
-  hipLaunchKernelGGL(kernel, dim3((int)blocks), dim3(64), lds, st, a, tab);
-  PNP_POST_HIP(hipGetLastError());
-  PNP_POST_HIP(hipEventRecord(ctx->ev1, st));
-  for (const Row& r : rows)
-    if (r.wanted()) PNP_POST_HIP(hipMemcpyAsync(r.host, *r.dev, r.n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (want_flags) PNP_POST_HIP(hipMemcpyAsync(ctx->flags.data(), flags_dev, flag_rows * sn * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  PNP_POST_HIP(hipStreamSynchronize(st));
-  PNP_POST_HIP(hipEventElapsedTime(&ctx->kernel_ms, ctx->ev0, ctx->ev1));
+  int64_t blocks = 0;
+  if (const int rc = persistent_waves(ctx, entry, p->max_waves, [&](int* per_cu) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, 64, lds);
+      }, (n + 63) / 64, &blocks))
+    return rc;
+  if (const int rc = reserve(ctx, entry, n_in + need_out + n_flags)) return rc;
+  s.in.place(ctx->buf);
+  int32_t* flags_dev = reinterpret_cast<int32_t*>(place_rows(rows, ctx->buf + n_in));
+  own(flags_dev);
+  if (const int rc = launch_and_fetch(ctx, entry, st, n_in, rows, Flags{flags_dev, flag_rows * sn, want_flags}, &ctx->kernel_ms, [&] {
+        hipLaunchKernelGGL(kernel, dim3((int)blocks), dim3(64), lds, st, a, s.tab);
+        return hipSuccess;
+      }))
+    return rc;
   ctx->last_kernel = kernel_name;
   return OK;
 }

@@ -13,12 +13,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <new>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "pnp_math.h"
+#include "pnp_stage.h"
 #include "pnp_wave.h"
 
 namespace pnp {
@@ -133,6 +136,8 @@ struct Ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernel of the last call (last_kernel_ms)
   float kernel_ms = -1.0f;
   std::string err, last_kernel;
+  std::vector<double> stage;    // host: the inputs of the call in flight, one copy (pnp_stage.h: Inputs)
+  std::vector<int32_t> flags;   // host: the int32 rows (status, counters) as the kernel wrote them
 };
 
 static thread_local std::string g_create_error;
@@ -212,35 +217,6 @@ static int check_view(Ctx* ctx, const char* entry, const char* params_name, cons
   return OK;
 }
 
-// An output row: n doubles go to `host` from the device address the library's kernel arguments keep at *dev.  A row is wanted when
-// the caller gave a pointer and it is not empty; the wanted rows lie one behind the other, each padded to an even count.
-struct Row {
-  double* host;
-  double** dev;
-  size_t n;
-  bool wanted() const { return host && n; }
-};
-static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
-
-template <size_t NR>
-static size_t rows_doubles(const Row (&rows)[NR]) {
-  size_t need = 0;
-  for (const Row& r : rows)
-    if (r.wanted()) need += even(r.n);
-  return need;
-}
-
-// sets *dev of the wanted rows from `cur` on; the first double behind them
-template <size_t NR>
-static double* place_rows(const Row (&rows)[NR], double* cur) {
-  for (const Row& r : rows)
-    if (r.wanted()) {
-      *r.dev = cur;
-      cur += even(r.n);
-    }
-  return cur;
-}
-
 // the context's device buffer only grows
 static int reserve(Ctx* ctx, const char* entry, size_t need) {
   if (need > ctx->buf_doubles) {
@@ -253,22 +229,60 @@ static int reserve(Ctx* ctx, const char* entry, size_t need) {
   return OK;
 }
 
-// The tail of an entry point, on stream st: the chosen instance of `kernel` between the context's two events (f: see launch_shape),
-// the wanted rows copied back, and the stream drained.
-template <size_t NR, class F>
-static int run(Ctx* ctx, const char* entry, hipStream_t st, const Row (&rows)[NR], const char* kernel, int P, int WY, bool steric, F&& f) {
+// Persistent grid: as many waves as the device holds at once (occupancy(&per_cu): the occupancy query of the chosen instance, made only
+// when the caller does not size the grid with max_waves), no more than there are groups of systems.
+template <class Occ>
+static int persistent_waves(Ctx* ctx, const char* entry, int64_t max_waves, Occ&& occupancy, int64_t groups, int64_t* out) {
+  int64_t blocks = max_waves;
+  if (blocks == 0) {
+    int cus = 0, per_cu = 0;
+    PNP_POST_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const hipError_t oe = occupancy(&per_cu);
+    PNP_POST_HIP(oe);
+    blocks = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
+  }
+  *out = std::min(std::max<int64_t>(blocks, 1), groups);
+  return OK;
+}
+
+// the int32 rows a kernel writes behind its output rows: n of them at dev, copied to ctx->flags when wanted
+struct Flags {
+  const int32_t* dev;
+  size_t n;
+  bool wanted;
+};
+
+// The tail of every entry point, on stream st: the first n_in doubles of ctx->stage copied to the device buffer (0: nothing), launch()
+// (the chosen instance; its hipError_t) between the context's two events, the wanted rows and the wanted flags copied back, the stream
+// drained, and the time between the events in *ms.
+template <size_t NR, class L>
+static int launch_and_fetch(Ctx* ctx, const char* entry, hipStream_t st, size_t n_in, const Row (&rows)[NR], const Flags& fl, float* ms, L&& launch) {
+  if (n_in) PNP_POST_HIP(hipMemcpyAsync(ctx->buf, ctx->stage.data(), n_in * sizeof(double), hipMemcpyHostToDevice, st));
   if (!ctx->ev0) PNP_POST_HIP(hipEventCreate(&ctx->ev0));
   if (!ctx->ev1) PNP_POST_HIP(hipEventCreate(&ctx->ev1));
   ctx->kernel_ms = -1.0f;
   PNP_POST_HIP(hipEventRecord(ctx->ev0, st));
-  if (steric) launch_shape<true>(P, WY, f);
-  else launch_shape<false>(P, WY, f);
+  const hipError_t le = launch();
+  PNP_POST_HIP(le);
   PNP_POST_HIP(hipGetLastError());
   PNP_POST_HIP(hipEventRecord(ctx->ev1, st));
   for (const Row& r : rows)
     if (r.wanted()) PNP_POST_HIP(hipMemcpyAsync(r.host, *r.dev, r.n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (fl.wanted) PNP_POST_HIP(hipMemcpyAsync(ctx->flags.data(), fl.dev, fl.n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   PNP_POST_HIP(hipStreamSynchronize(st));
-  PNP_POST_HIP(hipEventElapsedTime(&ctx->kernel_ms, ctx->ev0, ctx->ev1));
+  PNP_POST_HIP(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+  return OK;
+}
+
+// The tail of the libraries whose kernel comes in (P, WY, steric) instances (f: see launch_shape) and writes no flags
+template <size_t NR, class F>
+static int run(Ctx* ctx, const char* entry, hipStream_t st, const Row (&rows)[NR], const char* kernel, int P, int WY, bool steric, F&& f) {
+  if (const int rc = launch_and_fetch(ctx, entry, st, 0, rows, Flags{nullptr, 0, false}, &ctx->kernel_ms, [&] {
+        if (steric) launch_shape<true>(P, WY, f);
+        else launch_shape<false>(P, WY, f);
+        return hipSuccess;
+      }))
+    return rc;
   char msg[128];
   snprintf(msg, sizeof msg, "%s<%d, %d, %s>", kernel, P, WY, steric ? "true" : "false");
   ctx->last_kernel = msg;

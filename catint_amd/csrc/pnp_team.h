@@ -1,7 +1,8 @@
-// What the two libraries that eliminate the stationary Jacobian of the physical mode with a TEAM of lanes per system have in common
-// (response/catresp.hip, couple/catcpl.hip): the rows of the Jacobian, the block Thomas walk from the bulk to the wall, and the host
-// code around a launch.  Each library is one translation unit and compiles its own copy: nothing here is exported.  The frame of an
-// entry point (context, check_view, rows, reserve) is that of pnp_post.h.  gfx950 / MI355X only.
+// What the libraries that eliminate the stationary Jacobian of the physical mode with a TEAM of lanes per system have in common
+// (response/catresp.hip, couple/catcpl.hip, sens/catsens.hip, modes/catmodes.hip, eis/cateis.hip): the rows of the Jacobian, the block
+// Thomas walk from the bulk to the wall, the reaction and wall tables, and the host code around a launch.  Each library is one
+// translation unit and compiles its own copy: nothing here is exported.  The frame of an entry point (context, check_view, staged
+// inputs, rows, reserve, the tail) is that of pnp_post.h and pnp_stage.h.  gfx950 / MI355X only.
 //
 // Mapping: a team of NB = N + 1 adjacent lanes per system; lane r owns row r of the working block row [D' | L] (2 NB numbers, real or
 // complex) in registers.  64 / NB teams per wave, one wave per workgroup, no workgroup barrier.  The lanes beyond the last full team form
@@ -53,6 +54,14 @@ struct ReactionTable {
   double net[MAXR][MAXS + 1];       // n_rhs(k, r) - n_lhs(k, r); column N: 0
 };
 static_assert(sizeof(ReactionTable) % 8 == 0, "the table is copied as doubles");
+
+// ... and the wall table behind it, in the libraries that take one
+struct WallTable : ReactionTable {
+  int32_t wspecies[PNP_MAX_WALL_REACTIONS], pad_[PNP_MAX_WALL_REACTIONS];
+  double nu[PNP_MAX_WALL_REACTIONS][MAXS + 1];   // column N: 0
+  double alpha[PNP_MAX_WALL_REACTIONS], sat[PNP_MAX_WALL_REACTIONS];
+};
+static_assert(sizeof(WallTable) % 8 == 0, "the table is copied as doubles");
 
 // The constants of the medium, member `k` of a kernel's arguments.  The shared functions read these further members of the arguments
 // (type KA) by name, so each kernel keeps the layout of its own: int32 nx, nreact, stern, steric; const double *wgt, *vol ([nx-1]
@@ -386,11 +395,7 @@ __device__ __forceinline__ double team_sum(const double* row, const Lane& ln) {
 }
 
 // ---- host: the context and the checks of an entry point ----------------------------------------------------------------------------
-struct Ctx : pnp::post::Ctx {
-  std::vector<double> stage;    // host: the inputs of the call in flight, one copy
-  std::vector<int32_t> flags;   // host: status as the kernel wrote it
-};
-
+// (the context is pnp::post::Ctx)
 static bool posfin(double v) { return v > 0.0 && std::isfinite(v); }
 
 // The checks come in pieces so that an entry point can keep its own between them; each returns 0 or the code.  Params: catresp_params /
@@ -454,6 +459,32 @@ static int check_reactions(Ctx* ctx, const char* entry, const Params* p, int N) 
   return OK;
 }
 
+// the wall table: its size (which the libraries check before check_reactions) ...
+static int check_nwall(Ctx* ctx, const char* entry, int W) {
+  char msg[256];
+  if (W < 0 || W > PNP_MAX_WALL_REACTIONS) {
+    snprintf(msg, sizeof msg, "%s: n_wall = %d outside [0, %d]", entry, W, PNP_MAX_WALL_REACTIONS);
+    return fail(ctx, ERR_INVAL, msg);
+  }
+  return OK;
+}
+
+// ... and its entries (after check_reactions)
+template <class Params>
+static int check_wall(Ctx* ctx, const char* entry, const Params* p, int N) {
+  char msg[256];
+  const std::string e(entry);
+  const int W = p->n_wall;
+  if (W > 0 && !p->k) return fail(ctx, ERR_INVAL, e + ": n_wall > 0 needs the rate constants k");
+  if (W > 0 && (!p->wall_species || !p->nu)) return fail(ctx, ERR_INVAL, e + ": n_wall > 0 needs wall_species and nu");
+  for (int r = 0; r < W; ++r)
+    if (p->wall_species[r] < -1 || p->wall_species[r] >= N) {
+      snprintf(msg, sizeof msg, "%s: wall reaction %d names species index %d outside [-1, %d)", entry, r, p->wall_species[r], N);
+      return fail(ctx, ERR_INVAL, msg);
+    }
+  return OK;
+}
+
 template <class Params>
 static int check_lanes(Ctx* ctx, const char* entry, const Params* p, int64_t B) {
   char msg[256];
@@ -486,21 +517,26 @@ static bool fill_consts(Consts& k, const Params* p, int N, bool stern) {
   return steric;
 }
 
-// The head of the staged inputs (and of the device buffer they are copied to): edge weights, control volumes, row constants -- each
-// padded to an even count; what a library adds starts at grid_doubles(nx).
-static size_t grid_vol(int nx) { return even((size_t)nx - 1); }
-static size_t grid_sp(int nx) { return grid_vol(nx) + even(nx); }
-static size_t grid_doubles(int nx) { return grid_sp(nx) + (size_t)(MAXS + 1) * SPF; }
+// The grid as every kernel here reads it, three staged inputs in a row: edge weights dx / h_e -> a.wgt, control volumes v_i -> a.vol,
+// row constants -> a.sp.  Returns the first of the three slots for stage_grid.
+template <class KA>
+static int declare_grid(Inputs& in, KA& a, int nx) {
+  const int first = in.add((size_t)nx - 1, &a.wgt);
+  in.add((size_t)nx, &a.vol);
+  in.add((size_t)(MAXS + 1) * SPF, &a.sp);
+  return first;
+}
 
 template <class Params>
-static void stage_grid(double* sg, const Params* p, int nx, int N) {
-  for (int e = 0; e < nx - 1; ++e) sg[e] = p->dx / (p->x[e + 1] - p->x[e]);
+static void stage_grid(const Inputs& in, std::vector<double>& stage, int first, const Params* p, int nx, int N) {
+  double *wgt = in.host(stage, first), *vol = in.host(stage, first + 1), *sp = in.host(stage, first + 2);
+  for (int e = 0; e < nx - 1; ++e) wgt[e] = p->dx / (p->x[e + 1] - p->x[e]);
   for (int i = 0; i < nx; ++i) {
     const double hl = i > 0 ? p->x[i] - p->x[i - 1] : 0.0, hr = i < nx - 1 ? p->x[i + 1] - p->x[i] : 0.0;
-    sg[grid_vol(nx) + i] = 0.5 * (hr + hl) / p->dx;
+    vol[i] = 0.5 * (hr + hl) / p->dx;
   }
   for (int k = 0; k <= N; ++k) {
-    double* s = sg + grid_sp(nx) + k * SPF;
+    double* s = sp + k * SPF;
     s[0] = 1.0;
     if (k < N) {
       s[0] = p->D[k];
@@ -512,15 +548,8 @@ static void stage_grid(double* sg, const Params* p, int nx, int N) {
   }
 }
 
-// the kernel's pointers to what stage_grid wrote, once it lies at `buf` on the device
-template <class KA>
-static void place_grid(KA& a, const double* buf, int nx) {
-  a.wgt = buf;
-  a.vol = buf + grid_vol(nx);
-  a.sp = buf + grid_sp(nx);
-}
-
-// the selected operating points (int64 in the place of doubles); lanes NULL: the first n
+// the selected operating points (int64 in the place of doubles, one unpadded input: what follows has always started right behind
+// them); lanes NULL: the first n
 template <class Params>
 static void stage_lanes(double* at, const Params* p) {
   int64_t* l = reinterpret_cast<int64_t*>(at);
@@ -540,43 +569,39 @@ static void fill_reactions(ReactionTable* tb, const Params* p) {
   }
 }
 
-// ---- host: the launch --------------------------------------------------------------------------------------------------------------
-// Persistent grid: as many waves as the device holds at once (resident(&per_cu): the occupancy query of the chosen instance) unless the
-// caller sizes it with max_waves, no more than there are groups of systems.
-template <class Occ>
-static int persistent_blocks(Ctx* ctx, const char* entry, int64_t max_waves, int64_t groups, Occ&& resident, int64_t* out) {
-  int64_t blocks = max_waves;
-  if (blocks == 0) {
-    int cus = 0, per_cu = 0;
-    PNP_POST_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    const hipError_t oe = resident(&per_cu);
-    PNP_POST_HIP(oe);
-    blocks = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
+// the wall part of a zeroed table (after check_wall)
+template <class Params>
+static void fill_wall(WallTable* tb, const Params* p, int N) {
+  for (int r = 0; r < p->n_wall; ++r) {
+    tb->wspecies[r] = p->wall_species[r];
+    tb->alpha[r] = p->alpha ? p->alpha[r] : 0.0;
+    tb->sat[r] = p->saturation ? p->saturation[r] : 0.0;
+    for (int k = 0; k < N; ++k) tb->nu[r][k] = p->nu[r * N + k];
   }
-  *out = std::min(std::max<int64_t>(blocks, 1), groups);
-  return OK;
 }
 
-// The tail of an entry point, on stream st: the n_in staged doubles copied to the device buffer, launch() (the chosen instance; its
-// hipError_t) between the context's two events, the wanted rows and the nsys int32 of the status row copied back (status: the caller's
-// row or NULL; status_dev: the kernel's), and the stream drained.
+// ---- host: the launch --------------------------------------------------------------------------------------------------------------
+// the compiled block sizes: NB = 2 .. 9.  What f(ic<NB>) returns
+template <class Fn>
+static auto dispatch_nb(int NB, Fn&& f) {
+  switch (NB) {
+    case 2: return f(ic<2>());
+    case 3: return f(ic<3>());
+    case 4: return f(ic<4>());
+    case 5: return f(ic<5>());
+    case 6: return f(ic<6>());
+    case 7: return f(ic<7>());
+    case 8: return f(ic<8>());
+    default: return f(ic<9>());
+  }
+}
+
+// The tail of an entry point whose kernel writes one status row: pnp::post::launch_and_fetch, and the nsys int32 of the row handed to
+// the caller (status: the caller's row or NULL; status_dev: the kernel's).
 template <size_t NR, class L>
 static int run_with_status(Ctx* ctx, const char* entry, hipStream_t st, size_t n_in, const Row (&rows)[NR], int32_t* status,
                            const int32_t* status_dev, size_t nsys, L&& launch) {
-  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, ctx->stage.data(), n_in * sizeof(double), hipMemcpyHostToDevice, st));
-  if (!ctx->ev0) PNP_POST_HIP(hipEventCreate(&ctx->ev0));
-  if (!ctx->ev1) PNP_POST_HIP(hipEventCreate(&ctx->ev1));
-  ctx->kernel_ms = -1.0f;
-  PNP_POST_HIP(hipEventRecord(ctx->ev0, st));
-  const hipError_t le = launch();
-  PNP_POST_HIP(le);
-  PNP_POST_HIP(hipGetLastError());
-  PNP_POST_HIP(hipEventRecord(ctx->ev1, st));
-  for (const Row& r : rows)
-    if (r.wanted()) PNP_POST_HIP(hipMemcpyAsync(r.host, *r.dev, r.n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (status) PNP_POST_HIP(hipMemcpyAsync(ctx->flags.data(), status_dev, nsys * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  PNP_POST_HIP(hipStreamSynchronize(st));
-  PNP_POST_HIP(hipEventElapsedTime(&ctx->kernel_ms, ctx->ev0, ctx->ev1));
+  if (const int rc = launch_and_fetch(ctx, entry, st, n_in, rows, Flags{status_dev, nsys, status != nullptr}, &ctx->kernel_ms, launch)) return rc;
   if (status) memcpy(status, ctx->flags.data(), nsys * sizeof(int32_t));
   return OK;
 }

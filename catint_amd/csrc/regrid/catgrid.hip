@@ -175,9 +175,7 @@ static_assert(CATGRID_OK == pnp::post::OK && CATGRID_EINVAL == pnp::post::ERR_IN
                   CATGRID_EDEVICE == pnp::post::ERR_DEVICE && CATGRID_MAX_NX == pnp::post::MAX_NX && CATGRID_MAX_SPECIES == pnp::post::MAX_SPECIES,
               "catint_regrid.h and pnp_post.h disagree");
 
-struct catgrid_ctx : pnp::post::Ctx {
-  std::vector<double> stage;   // host: the table and the lane list of the call in flight, one copy
-};
+struct catgrid_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -246,16 +244,18 @@ int catgrid_resample(catgrid_ctx* ctx, const pnp_device_view* view, const catgri
   const int big = std::max(nx, nxt), WY = big <= 1026 ? 1 : (big <= 2050 ? 2 : 4);
 
   // the table of the target points (cell, cell coordinate, cell length) and the lane list, staged on the host for one copy
-  const size_t o_s = 0, o_h = o_s + pitch, o_e = o_h + pitch, o_l = o_e + pitch / 2, n_in = o_l + even((size_t)n);
+  Inputs in;
+  const int i_s = in.add((size_t)pitch, &a.s), i_h = in.add((size_t)pitch, &a.h), i_e = in.add((size_t)pitch / 2, &a.e), i_l = in.add((size_t)n, &a.lanes);
+  const size_t n_in = in.total;
   try {
     ctx->stage.assign(n_in, 0.0);
   } catch (const std::bad_alloc&) {
     return fail(ctx, CATGRID_ENOMEM, "catgrid_resample: out of host memory");
   }
-  double* sg = ctx->stage.data();
-  int32_t* se = reinterpret_cast<int32_t*>(sg + o_e);
-  int64_t* sl = reinterpret_cast<int64_t*>(sg + o_l);
-  for (int j = 0; j < pitch; ++j) sg[o_h + j] = 1.0;
+  double *ss = in.host(ctx->stage, i_s), *sh = in.host(ctx->stage, i_h);
+  int32_t* se = reinterpret_cast<int32_t*>(in.host(ctx->stage, i_e));
+  int64_t* sl = reinterpret_cast<int64_t*>(in.host(ctx->stage, i_l));
+  for (int j = 0; j < pitch; ++j) sh[j] = 1.0;
   for (int j = 0; j < nxt; ++j) {
     const double X = p->x_target[j];
     int e = (int)(std::upper_bound(p->x, p->x + nx, X) - p->x) - 1;   // the largest e with x[e] <= X
@@ -263,12 +263,12 @@ int catgrid_resample(catgrid_ctx* ctx, const pnp_device_view* view, const catgri
     const double he = p->x[e + 1] - p->x[e];
     if (X == p->x[nx - 1]) {     // the last node: a copy
       se[j] = nx - 1;
-      sg[o_s + j] = 0.0;
+      ss[j] = 0.0;
     } else {
       se[j] = e;
-      sg[o_s + j] = (X - p->x[e]) / he;
+      ss[j] = (X - p->x[e]) / he;
     }
-    sg[o_h + j] = he;
+    sh[j] = he;
   }
   for (int64_t i = 0; i < n; ++i) sl[i] = p->lanes ? p->lanes[i] : i;
 
@@ -276,13 +276,10 @@ int catgrid_resample(catgrid_ctx* ctx, const pnp_device_view* view, const catgri
   hipStream_t st = (hipStream_t)view->stream;
   const size_t n_c = (size_t)n * N * pitch, n_phi = (size_t)n * pitch;
   if (const int rc = reserve(ctx, entry, n_in + n_c + n_phi)) return rc;
-  a.s = ctx->buf + o_s;
-  a.h = ctx->buf + o_h;
-  a.e = reinterpret_cast<const int32_t*>(ctx->buf + o_e);
-  a.lanes = reinterpret_cast<const int64_t*>(ctx->buf + o_l);
+  in.place(ctx->buf);
   a.oc = ctx->buf + n_in;
   a.ophi = a.oc + n_c;
-  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, sg, n_in * sizeof(double), hipMemcpyHostToDevice, st));
+  PNP_POST_HIP(hipMemcpyAsync(ctx->buf, ctx->stage.data(), n_in * sizeof(double), hipMemcpyHostToDevice, st));
   if (!ctx->ev0) PNP_POST_HIP(hipEventCreate(&ctx->ev0));
   if (!ctx->ev1) PNP_POST_HIP(hipEventCreate(&ctx->ev1));
   ctx->kernel_ms = -1.0f;

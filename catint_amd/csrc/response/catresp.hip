@@ -32,15 +32,7 @@ namespace catresp {
 
 using namespace pnp::team;
 
-constexpr int MAXW = PNP_MAX_WALL_REACTIONS;
-
-// the reaction and wall tables of one call, flattened on the host (every index validated there)
-struct Table : ReactionTable {
-  int32_t wspecies[MAXW], pad_[MAXW];
-  double nu[MAXW][MAXS + 1];        // column N: 0
-  double alpha[MAXW], sat[MAXW];
-};
-static_assert(sizeof(Table) % 8 == 0, "the table is copied as doubles");
+using Table = pnp::team::WallTable;   // the reaction and wall tables of one call
 
 struct KArgs {
   int32_t nx, ldx, nreact, nwall, stern, pert, pspecies, F, steric, slots_pad_;
@@ -288,23 +280,14 @@ static hipError_t resident(int* per_cu) {
 
 // the compiled instances: NB = 2 .. 9, real / complex, scalars only / records.  f(ic<NB>, bool_constant<CX>, bool_constant<REC>)
 template <class Fn>
-static void dispatch(int NB, bool cx, bool rec, Fn&& f) {
+static hipError_t dispatch(int NB, bool cx, bool rec, Fn&& f) {
   const auto with_nb = [&](auto nb) {
-    if (cx && rec) f(nb, std::true_type(), std::true_type());
-    else if (cx) f(nb, std::true_type(), std::false_type());
-    else if (rec) f(nb, std::false_type(), std::true_type());
-    else f(nb, std::false_type(), std::false_type());
+    if (cx && rec) return f(nb, std::true_type(), std::true_type());
+    if (cx) return f(nb, std::true_type(), std::false_type());
+    if (rec) return f(nb, std::false_type(), std::true_type());
+    return f(nb, std::false_type(), std::false_type());
   };
-  switch (NB) {
-    case 2: with_nb(ic<2>()); break;
-    case 3: with_nb(ic<3>()); break;
-    case 4: with_nb(ic<4>()); break;
-    case 5: with_nb(ic<5>()); break;
-    case 6: with_nb(ic<6>()); break;
-    case 7: with_nb(ic<7>()); break;
-    case 8: with_nb(ic<8>()); break;
-    default: with_nb(ic<9>()); break;
-  }
+  return dispatch_nb(NB, with_nb);
 }
 
 }  // namespace catresp
@@ -316,7 +299,7 @@ static_assert(CATRESP_WALL_DIRICHLET == pnp::team::WALL_DIRICHLET && CATRESP_WAL
                   CATRESP_PIVOT_GROWTH_LIMIT == pnp::team::PIVOT_GROWTH_LIMIT,
               "catint_response.h and pnp_team.h disagree");
 
-struct catresp_ctx : pnp::team::Ctx {};
+struct catresp_ctx : pnp::post::Ctx {};
 
 extern "C" {
 
@@ -342,18 +325,9 @@ int catresp_solve(catresp_ctx* ctx, const pnp_device_view* view, const catresp_p
   if (const int rc = check_species(ctx, entry, p, N)) return rc;
   const int R = p->nreactions, W = p->n_wall, F = p->nfreq;
   if (const int rc = check_nreactions(ctx, entry, R)) return rc;
-  if (W < 0 || W > PNP_MAX_WALL_REACTIONS) {
-    snprintf(msg, sizeof msg, "catresp_solve: n_wall = %d outside [0, %d]", W, PNP_MAX_WALL_REACTIONS);
-    return fail(ctx, CATRESP_EINVAL, msg);
-  }
+  if (const int rc = check_nwall(ctx, entry, W)) return rc;
   if (const int rc = check_reactions(ctx, entry, p, N)) return rc;
-  if (W > 0 && !p->k) return fail(ctx, CATRESP_EINVAL, "catresp_solve: n_wall > 0 needs the rate constants k");
-  if (W > 0 && (!p->wall_species || !p->nu)) return fail(ctx, CATRESP_EINVAL, "catresp_solve: n_wall > 0 needs wall_species and nu");
-  for (int r = 0; r < W; ++r)
-    if (p->wall_species[r] < -1 || p->wall_species[r] >= N) {
-      snprintf(msg, sizeof msg, "catresp_solve: wall reaction %d names species index %d outside [-1, %d)", r, p->wall_species[r], N);
-      return fail(ctx, CATRESP_EINVAL, msg);
-    }
+  if (const int rc = check_wall(ctx, entry, p, N)) return rc;
   if (F < 1 || F > CATRESP_MAX_FREQ) {
     snprintf(msg, sizeof msg, "catresp_solve: nfreq = %d outside [1, %d]", F, CATRESP_MAX_FREQ);
     return fail(ctx, CATRESP_EINVAL, msg);
@@ -385,29 +359,24 @@ int catresp_solve(catresp_ctx* ctx, const pnp_device_view* view, const catresp_p
 
   // the inputs, staged on the host for one copy: edge weights, control volumes, row constants, potentials, rate constants,
   // frequencies, lanes (int64 in the place of doubles), tables
-  const size_t o_p = grid_doubles(nx), o_k = o_p + even(B), o_f = o_k + even((size_t)B * W), o_l = o_f + even(F), o_t = o_l + (size_t)n,
-               n_in = o_t + sizeof(Table) / 8;
-  const size_t nsys = (size_t)n * F;
+  Inputs in;
+  const int i_grid = declare_grid(in, a, nx), i_p = in.add((size_t)B, &a.phiM), i_k = in.add((size_t)B * W, &a.kwall),
+            i_f = in.add((size_t)F, &a.omega), i_l = in.add_unpadded((size_t)n, &a.lanes), i_t = in.add_unpadded(sizeof(Table) / 8, &a.tab);
+  const size_t n_in = in.total, nsys = (size_t)n * F;
   try {
     ctx->stage.assign(n_in, 0.0);
     ctx->flags.assign(nsys, 0);
   } catch (const std::bad_alloc&) {
     return fail(ctx, CATRESP_ENOMEM, "catresp_solve: out of host memory");
   }
-  double* sg = ctx->stage.data();
-  stage_grid(sg, p, nx, N);
-  memcpy(sg + o_p, p->phiM, (size_t)B * 8);
-  if (W) memcpy(sg + o_k, p->k, (size_t)B * W * 8);
-  memcpy(sg + o_f, p->omega, (size_t)F * 8);
-  stage_lanes(sg + o_l, p);
-  Table* tb = reinterpret_cast<Table*>(sg + o_t);
+  stage_grid(in, ctx->stage, i_grid, p, nx, N);
+  memcpy(in.host(ctx->stage, i_p), p->phiM, (size_t)B * 8);
+  if (W) memcpy(in.host(ctx->stage, i_k), p->k, (size_t)B * W * 8);
+  memcpy(in.host(ctx->stage, i_f), p->omega, (size_t)F * 8);
+  stage_lanes(in.host(ctx->stage, i_l), p);
+  Table* tb = reinterpret_cast<Table*>(in.host(ctx->stage, i_t));
   fill_reactions(tb, p);
-  for (int r = 0; r < W; ++r) {
-    tb->wspecies[r] = p->wall_species[r];
-    tb->alpha[r] = p->alpha ? p->alpha[r] : 0.0;
-    tb->sat[r] = p->saturation ? p->saturation[r] : 0.0;
-    for (int k = 0; k < N; ++k) tb->nu[r][k] = p->nu[r * N + k];
-  }
+  fill_wall(tb, p, N);
 
   // the rows that were asked for (complex: two doubles per entry)
   const Row rows[] = {{out->dphi_surface, &a.dphis, 2 * nsys}, {out->dc_surface, &a.dcs, 2 * nsys * N}, {out->dsigma, &a.dsig, 2 * nsys},
@@ -422,11 +391,9 @@ int catresp_solve(catresp_ctx* ctx, const pnp_device_view* view, const catresp_p
   // with records, no more than the workspace cap admits (at least one)
   const int64_t groups = ((int64_t)nsys + TPW - 1) / TPW;
   int64_t blocks = 0;
-  if (const int rc = persistent_blocks(ctx, entry, p->max_waves, groups, [&](int* per_cu) {
-        hipError_t oe = hipSuccess;
-        dispatch(NB, complex_call, rec, [&](auto nb, auto cx, auto rc_) { oe = resident<decltype(nb)::value, decltype(cx)::value, decltype(rc_)::value>(per_cu); });
-        return oe;
-      }, &blocks))
+  if (const int rc = persistent_waves(ctx, entry, p->max_waves, [&](int* per_cu) {
+        return dispatch(NB, complex_call, rec, [&](auto nb, auto cx, auto rc_) { return resident<decltype(nb)::value, decltype(cx)::value, decltype(rc_)::value>(per_cu); });
+      }, groups, &blocks))
     return rc;
   size_t ws_doubles = 0;
   if (rec) {
@@ -441,19 +408,12 @@ int catresp_solve(catresp_ctx* ctx, const pnp_device_view* view, const catresp_p
     ws_doubles = (size_t)blocks * per_wave;
   }
   if (const int rc = reserve(ctx, entry, n_in + need_out + n_flags + ws_doubles)) return rc;
-  place_grid(a, ctx->buf, nx);
-  a.phiM = ctx->buf + o_p;
-  a.kwall = ctx->buf + o_k;
-  a.omega = ctx->buf + o_f;
-  a.lanes = reinterpret_cast<const int64_t*>(ctx->buf + o_l);
-  a.tab = reinterpret_cast<const Table*>(ctx->buf + o_t);
+  in.place(ctx->buf);
   double* cur = place_rows(rows, ctx->buf + n_in);
   a.status = reinterpret_cast<int32_t*>(cur);
   a.ws = cur + n_flags;
   if (const int rc = run_with_status(ctx, entry, st, n_in, rows, out->status, a.status, nsys, [&] {
-        hipError_t le = hipSuccess;
-        dispatch(NB, complex_call, rec, [&](auto nb, auto cx, auto rc_) { le = launch<decltype(nb)::value, decltype(cx)::value, decltype(rc_)::value>(a, blocks, st); });
-        return le;
+        return dispatch(NB, complex_call, rec, [&](auto nb, auto cx, auto rc_) { return launch<decltype(nb)::value, decltype(cx)::value, decltype(rc_)::value>(a, blocks, st); });
       }))
     return rc;
   snprintf(msg, sizeof msg, "catresp::response_kernel<%d, %s, %s>", NB, complex_call ? "true" : "false", rec ? "true" : "false");

@@ -108,7 +108,7 @@ static_assert(CATSK_MAX_SPECIES == pnp::kin::MAXN && CATSK_MAX_ADSORBATES == pnp
 // From catsk_begin on the context's device buffer holds, in doubles from its start: the Table, phiM [B], gamma [B][N]
 // (when given), theta [B][T], flux_scale [B][N], flux_last [B][N], the four int32 rows [4][B], and the buffers of catsk_step_host:
 // csurf [B][N], phi_surface [B], flux [B][N], active [B] int32
-struct catsk_ctx : pnp::kin::Ctx {
+struct catsk_ctx : pnp::post::Ctx {
   bool begun = false;
   int N = 0, S = 0, R = 0;
   int64_t B = 0;

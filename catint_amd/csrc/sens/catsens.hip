@@ -25,15 +25,8 @@ namespace catsens {
 
 using namespace pnp::team;
 
-constexpr int MAXW = PNP_MAX_WALL_REACTIONS;
 
-// the reaction and wall tables of one call, flattened on the host (every index validated there)
-struct Table : ReactionTable {
-  int32_t wspecies[MAXW], pad_[MAXW];
-  double nu[MAXW][MAXS + 1];        // column N: 0
-  double alpha[MAXW], sat[MAXW];
-};
-static_assert(sizeof(Table) % 8 == 0, "the table is copied as doubles");
+using Table = pnp::team::WallTable;   // the reaction and wall tables of one call
 
 struct KArgs {
   int32_t nx, ldx, nreact, nwall, stern, steric, P, nchunk;
@@ -394,21 +387,6 @@ static hipError_t resident(int* per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, sens_kernel<NB, CATSENS_CHUNK>, 64, 0);
 }
 
-// the compiled instances: NB = 2 .. 9, one chunk width.  f(ic<NB>)
-template <class Fn>
-static void dispatch(int NB, Fn&& f) {
-  switch (NB) {
-    case 2: f(ic<2>()); break;
-    case 3: f(ic<3>()); break;
-    case 4: f(ic<4>()); break;
-    case 5: f(ic<5>()); break;
-    case 6: f(ic<6>()); break;
-    case 7: f(ic<7>()); break;
-    case 8: f(ic<8>()); break;
-    default: f(ic<9>()); break;
-  }
-}
-
 }  // namespace catsens
 
 static_assert(CATSENS_OK == pnp::post::OK && CATSENS_EINVAL == pnp::post::ERR_INVAL && CATSENS_ENOMEM == pnp::post::ERR_NOMEM &&
@@ -418,7 +396,7 @@ static_assert(CATSENS_WALL_DIRICHLET == pnp::team::WALL_DIRICHLET && CATSENS_WAL
                   CATSENS_PIVOT_GROWTH_LIMIT == pnp::team::PIVOT_GROWTH_LIMIT,
               "catint_sens.h and pnp_team.h disagree");
 
-struct catsens_ctx : pnp::team::Ctx {
+struct catsens_ctx : pnp::post::Ctx {
   std::vector<int32_t> chunk_flags;   // host: status of every (point, chunk)
 };
 
@@ -445,18 +423,9 @@ int catsens_solve(catsens_ctx* ctx, const pnp_device_view* view, const catsens_p
   if (const int rc = check_species(ctx, entry, p, N)) return rc;
   const int R = p->nreactions, W = p->n_wall, P = p->nparams;
   if (const int rc = check_nreactions(ctx, entry, R)) return rc;
-  if (W < 0 || W > PNP_MAX_WALL_REACTIONS) {
-    snprintf(msg, sizeof msg, "catsens_solve: n_wall = %d outside [0, %d]", W, PNP_MAX_WALL_REACTIONS);
-    return fail(ctx, CATSENS_EINVAL, msg);
-  }
+  if (const int rc = check_nwall(ctx, entry, W)) return rc;
   if (const int rc = check_reactions(ctx, entry, p, N)) return rc;
-  if (W > 0 && !p->k) return fail(ctx, CATSENS_EINVAL, "catsens_solve: n_wall > 0 needs the rate constants k");
-  if (W > 0 && (!p->wall_species || !p->nu)) return fail(ctx, CATSENS_EINVAL, "catsens_solve: n_wall > 0 needs wall_species and nu");
-  for (int r = 0; r < W; ++r)
-    if (p->wall_species[r] < -1 || p->wall_species[r] >= N) {
-      snprintf(msg, sizeof msg, "catsens_solve: wall reaction %d names species index %d outside [-1, %d)", r, p->wall_species[r], N);
-      return fail(ctx, CATSENS_EINVAL, msg);
-    }
+  if (const int rc = check_wall(ctx, entry, p, N)) return rc;
   if (!p->phiM) return fail(ctx, CATSENS_EINVAL, "catsens_solve: phiM is required");
   if (P < 1 || P > CATSENS_MAX_PARAMS) {
     snprintf(msg, sizeof msg, "catsens_solve: nparams = %d outside [1, %d]", P, CATSENS_MAX_PARAMS);
@@ -510,8 +479,11 @@ int catsens_solve(catsens_ctx* ctx, const pnp_device_view* view, const catsens_p
 
   // the inputs, staged on the host for one copy: edge weights, control volumes, row constants, edge lengths, potentials, rate
   // constants, fluxes, lanes (int64 in the place of doubles), the flags of non-finite inputs and the columns' keys (int32 pairs), tables
-  const size_t o_h = grid_doubles(nx), o_p = o_h + even((size_t)nx - 1), o_k = o_p + even(B), o_g = o_k + even((size_t)B * W), o_l = o_g + even(nn * N),
-               o_b = o_l + nn, o_ky = o_b + even((nn + 1) / 2), o_t = o_ky + ncol / 2, n_in = o_t + sizeof(Table) / 8;
+  Inputs in;
+  const int i_grid = declare_grid(in, a, nx), i_h = in.add((size_t)nx - 1, &a.h), i_p = in.add((size_t)B, &a.phiM),
+            i_k = in.add((size_t)B * W, &a.kwall), i_g = in.add(nn * N, &a.flux), i_l = in.add_unpadded(nn, &a.lanes),
+            i_b = in.add((nn + 1) / 2, &a.badin), i_ky = in.add_unpadded(ncol / 2, &a.key), i_t = in.add_unpadded(sizeof(Table) / 8, &a.tab);
+  const size_t n_in = in.total;
   try {
     ctx->stage.assign(n_in, 0.0);
     ctx->flags.assign(nsys, 0);
@@ -519,15 +491,15 @@ int catsens_solve(catsens_ctx* ctx, const pnp_device_view* view, const catsens_p
   } catch (const std::bad_alloc&) {
     return fail(ctx, CATSENS_ENOMEM, "catsens_solve: out of host memory");
   }
-  double* sg = ctx->stage.data();
-  stage_grid(sg, p, nx, N);
-  for (int e = 0; e < nx - 1; ++e) sg[o_h + e] = p->x[e + 1] - p->x[e];
-  memcpy(sg + o_p, p->phiM, (size_t)B * 8);
-  if (W) memcpy(sg + o_k, p->k, (size_t)B * W * 8);
-  memcpy(sg + o_g, p->flux, nn * N * 8);
-  stage_lanes(sg + o_l, p);
+  stage_grid(in, ctx->stage, i_grid, p, nx, N);
+  double* h = in.host(ctx->stage, i_h);
+  for (int e = 0; e < nx - 1; ++e) h[e] = p->x[e + 1] - p->x[e];
+  memcpy(in.host(ctx->stage, i_p), p->phiM, (size_t)B * 8);
+  if (W) memcpy(in.host(ctx->stage, i_k), p->k, (size_t)B * W * 8);
+  memcpy(in.host(ctx->stage, i_g), p->flux, nn * N * 8);
+  stage_lanes(in.host(ctx->stage, i_l), p);
   {
-    int32_t* bi = reinterpret_cast<int32_t*>(sg + o_b);
+    int32_t* bi = reinterpret_cast<int32_t*>(in.host(ctx->stage, i_b));
     for (size_t i = 0; i < nn; ++i) {
       const int64_t b = p->lanes ? p->lanes[i] : (int64_t)i;
       bool fin = std::isfinite(p->phiM[b]);
@@ -535,21 +507,16 @@ int catsens_solve(catsens_ctx* ctx, const pnp_device_view* view, const catsens_p
       for (int r = 0; r < W; ++r) fin = fin && std::isfinite(p->k[b * W + r]);
       bi[i] = fin ? 0 : 1;
     }
-    int32_t* ky = reinterpret_cast<int32_t*>(sg + o_ky);
+    int32_t* ky = reinterpret_cast<int32_t*>(in.host(ctx->stage, i_ky));
     for (size_t m = 0; m < ncol; ++m) {
       const int kd = m < (size_t)P ? p->kind[m] : -1;
       const bool indexed = kd != CATSENS_PHIM && kd != CATSENS_VELOCITY && kd != CATSENS_STERN_CAPACITANCE;
       ky[m] = kd < 0 ? -1 : key_of(kd, indexed ? p->index[m] : -1);
     }
   }
-  Table* tb = reinterpret_cast<Table*>(sg + o_t);
+  Table* tb = reinterpret_cast<Table*>(in.host(ctx->stage, i_t));
   fill_reactions(tb, p);
-  for (int r = 0; r < W; ++r) {
-    tb->wspecies[r] = p->wall_species[r];
-    tb->alpha[r] = p->alpha ? p->alpha[r] : 0.0;
-    tb->sat[r] = p->saturation ? p->saturation[r] : 0.0;
-    for (int k = 0; k < N; ++k) tb->nu[r][k] = p->nu[r * N + k];
-  }
+  fill_wall(tb, p, N);
 
   // the rows that were asked for
   const size_t np = nn * P;
@@ -563,28 +530,15 @@ int catsens_solve(catsens_ctx* ctx, const pnp_device_view* view, const catsens_p
   // persistent grid: as many waves as the device holds at once unless the caller sizes it, no more than there are groups of systems
   const int64_t groups = ((int64_t)nsys + TPW - 1) / TPW;
   int64_t blocks = 0;
-  if (const int rc = persistent_blocks(ctx, entry, p->max_waves, groups, [&](int* per_cu) {
-        hipError_t oe = hipSuccess;
-        dispatch(NB, [&](auto nb) { oe = resident<decltype(nb)::value>(per_cu); });
-        return oe;
-      }, &blocks))
+  if (const int rc = persistent_waves(ctx, entry, p->max_waves, [&](int* per_cu) {
+        return dispatch_nb(NB, [&](auto nb) { return resident<decltype(nb)::value>(per_cu); });
+      }, groups, &blocks))
     return rc;
   if (const int rc = reserve(ctx, entry, n_in + need_out + n_flags)) return rc;
-  place_grid(a, ctx->buf, nx);
-  a.h = ctx->buf + o_h;
-  a.phiM = ctx->buf + o_p;
-  a.kwall = ctx->buf + o_k;
-  a.flux = ctx->buf + o_g;
-  a.lanes = reinterpret_cast<const int64_t*>(ctx->buf + o_l);
-  a.badin = reinterpret_cast<const int32_t*>(ctx->buf + o_b);
-  a.key = reinterpret_cast<const int32_t*>(ctx->buf + o_ky);
-  a.tab = reinterpret_cast<const Table*>(ctx->buf + o_t);
-  double* cur = place_rows(rows, ctx->buf + n_in);
-  a.flags = reinterpret_cast<int32_t*>(cur);
+  in.place(ctx->buf);
+  a.flags = reinterpret_cast<int32_t*>(place_rows(rows, ctx->buf + n_in));
   if (const int rc = run_with_status(ctx, entry, st, n_in, rows, out->status ? ctx->chunk_flags.data() : nullptr, a.flags, nsys, [&] {
-        hipError_t le = hipSuccess;
-        dispatch(NB, [&](auto nb) { le = launch<decltype(nb)::value>(a, blocks, st); });
-        return le;
+        return dispatch_nb(NB, [&](auto nb) { return launch<decltype(nb)::value>(a, blocks, st); });
       }))
     return rc;
   if (out->status)
