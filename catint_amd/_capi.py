@@ -277,6 +277,7 @@ class PnpSolver(object):
         self._rate_control = None
         self._transient = None
         self._impedance = None
+        self._interact = None
 
     def _check(self, rc):
         if rc != 0:
@@ -316,6 +317,9 @@ class PnpSolver(object):
         if getattr(self, '_impedance', None) is not None:
             self._impedance.close()
             self._impedance = None
+        if getattr(self, '_interact', None) is not None:
+            self._interact.close()
+            self._interact = None
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -775,7 +779,7 @@ class PnpSolver(object):
 
     def get_kinetics(self, model_or_tables, phiM=None, lanes=None, csurf=None, phi_surface=None, theta_guess=None, fields=None,
                      potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None,
-                     tol=None, maxit=None, max_waves=0, rescue=False):
+                     tol=None, maxit=None, max_waves=0, rescue=False, ramp=None):
         """The steady state of a mean-field surface microkinetic model (include/catint_kinetics.h) solved on the device, one operating
         point per entry of `lanes` (None: all lanes, in order; repeats allowed): coverages, step rates, the wall fluxes into the
         electrolyte and, when asked for, their sensitivities to the surface concentrations and potentials.  model_or_tables: a
@@ -791,8 +795,14 @@ class PnpSolver(object):
         or 3 are integrated in time from the uniform start until they are stationary (include/catint_kintrans.h: to 1e12 s with rtol
         1e-2, stopped at a scaled residual of 1e-6) and the ones that get there are solved again from that state; the rows of those
         that now converge replace the failed ones and the result gains 'rescued' [n] (bool).  A point whose second solve fails as
-        well keeps its first rows and status."""
+        well keeps its first rows and status.
+        A model with lateral interactions or several site types (catint_amd.interactions.InteractingModel, or a dict with its keys)
+        goes to include/catint_interact.h instead: theta_guess is [n][T], fields come from catint_amd._interact.FIELDS (also
+        'energy_shift' [n][S] in kT), the result gains 'ramp_reached' [n], and ramp is the number of stages the interaction strength
+        is raised in (None: 10 from the uniform start, 1 from a theta_guess).  rescue=True is an error there: the transient library
+        is mean-field."""
         from . import _kinetics
+        from .interactions import has_interactions
         if rescue and theta_guess is not None:
             raise ValueError('get_kinetics: rescue=True starts from the uniform surface and excludes theta_guess')
         o = self._obs
@@ -812,12 +822,26 @@ class PnpSolver(object):
             if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
                 raise ValueError('get_kinetics: lane index outside [0, %d)' % self.B)
             phiM = np.asarray(o['phiM'], float)[idx]
-        if self._kinetics is None:
+        interacting = has_interactions(tables)
+        if interacting:
+            from . import _interact
+            if rescue:
+                raise ValueError('get_kinetics: rescue=True integrates the mean-field model (include/catint_kintrans.h); this model has '
+                                 'lateral interactions or several site types')
+            if getattr(self, '_interact', None) is None:
+                self._interact = _interact.InteractingKinetics(o['device'])
+        elif ramp is not None:
+            raise ValueError('get_kinetics: ramp belongs to a model with lateral interactions or several site types')
+        elif self._kinetics is None:
             self._kinetics = _kinetics.KineticsSolver(o['device'])
         view = None if host else self.device_view()
         common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
                       phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, tol=_kinetics.DEFAULT_TOL if tol is None else tol,
                       maxit=_kinetics.DEFAULT_MAXIT if maxit is None else maxit, fields=fields, max_waves=max_waves)
+        if interacting:
+            return self._interact.solve(view, tables, phiM, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, sigma=sigma,
+                                        off=off, gamma=gamma, theta_guess=theta_guess,
+                                        ramp=(_interact.SCF_RAMP if theta_guess is None else 1) if ramp is None else ramp, **common)
         res = self._kinetics.solve(view, tables, phiM, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, sigma=sigma, off=off,
                                    gamma=gamma, theta_guess=theta_guess, **common)
         if rescue:

@@ -118,6 +118,14 @@ EIS_LIB = os.path.join(LIB_DIR, 'libcatint_eis.so')
 EIS_SOURCES = ['cateis.hip']
 EIS_HEADERS = _POST_HEADERS + [os.path.join(CSRC, 'pnp_team.h'), os.path.join(CSRC, 'pnp_kin.h'), os.path.join(_INCLUDE, 'catint_eis.h')]
 
+# fifteenth library (include/catint_interact.h): the steady state of a microkinetic model with lateral interactions and several site types
+# -- coverage-dependent rate constants, one site row per type, the interaction strength ramped in stages inside one launch.  It includes
+# pnp_kin.h as it is.  A library of its own as the thirteen before it: the kinetics library is pinned to one kernel and six symbols
+INTERACT_DIR = os.path.join(CSRC, 'interact')
+INTERACT_LIB = os.path.join(LIB_DIR, 'libcatint_interact.so')
+INTERACT_SOURCES = ['catia.hip']
+INTERACT_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_interact.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -311,6 +319,15 @@ def eis_needs_build():
 def build_eis_library(force=False, verbose=False):
     """catint_amd/csrc/eis into catint_amd/lib/libcatint_eis.so"""
     return _build_unit(EIS_DIR, EIS_SOURCES, EIS_HEADERS, EIS_LIB, force, verbose)
+
+
+def interact_needs_build():
+    return _unit_needs_build(INTERACT_DIR, INTERACT_SOURCES, INTERACT_HEADERS, INTERACT_LIB)
+
+
+def build_interact_library(force=False, verbose=False):
+    """catint_amd/csrc/interact into catint_amd/lib/libcatint_interact.so"""
+    return _build_unit(INTERACT_DIR, INTERACT_SOURCES, INTERACT_HEADERS, INTERACT_LIB, force, verbose)
 
 
 def unittest_needs_build():

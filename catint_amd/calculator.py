@@ -330,7 +330,7 @@ class Calculator(object):
         self.surface_kinetics = list(reactions)
 
     def set_microkinetics(self, model, site_density=None, potential_drop='stern', gamma=None, scf='mixing', rate_control=False, device_loop=False,
-                          rescue=False, impedance=None):
+                          rescue=False, impedance=None, ramp=10):
         """Mean-field surface microkinetics as the kinetic half of run_scf_cycle (physical mode only): model is a
         catint_amd.microkinetics.MeanFieldModel over this transport's species (or the dict of its tables()).  With it set,
         run_scf_cycle() without a callback runs its host loop with the device kinetics (include/catint_kinetics.h) as the callback: the
@@ -340,6 +340,11 @@ class Calculator(object):
         coefficients, None: 1.  The surface charge handed to the model is C_S (phiM - phiPZC - phi(x=0)).  A lane whose coverages are not
         found (kinetic status 1: stopped at maxit, 3: bad pivot, 2: non-finite input) leaves the loop as 'failed'; the result carries
         'coverage', 'flux_scale' and 'kinetic_status'.  model=None removes it.
+        A model with lateral interactions or several site types (catint_amd.interactions.InteractingModel, or a dict with its keys) is
+        solved by include/catint_interact.h instead, under both loops: the first kinetic call of a lane ramps the interaction strength
+        in `ramp` stages from the uniform start (the reference's n_inter), later ones warm-start at full strength, and a lane that
+        then ends with status 1 or 3 is solved once more with the ramp.  rate_control, device_loop, rescue and impedance raise with
+        such a model: those libraries are mean-field.  ramp is ignored for a mean-field model.
         scf='newton' (default 'mixing': the loop above, unchanged): run_scf_cycle() runs a Newton iteration on the wall fluxes instead
         of the mixing loop -- see _run_newton_scf.  It needs the derivatives of both halves, so it excludes a host flux_callback, a
         transport_fn and set_surface_kinetics.
@@ -385,6 +390,15 @@ class Calculator(object):
             if not len(om) or not (np.isfinite(om).all() and (om >= 0.0).all()):
                 raise CalculatorError('impedance is a list of angular frequencies, each finite and >= 0')
         tables = model.tables() if hasattr(model, 'tables') else dict(model)
+        from .interactions import has_interactions
+        interacting = has_interactions(tables)
+        if interacting:
+            for name, on in (('rate_control', rate_control), ('device_loop', device_loop), ('rescue', rescue), ('impedance', impedance is not None)):
+                if on:
+                    raise CalculatorError('%s works on the mean-field model (its library is mean-field on one site type); this model has lateral '
+                                          'interactions or several site types' % name)
+            if int(ramp) < 1:
+                raise CalculatorError('ramp is the number of stages the interaction strength is raised in, at least 1')
         N = self.tp.nspecies
         nu, of = np.asarray(tables['nu']), np.asarray(tables['order_f'])
         if of.ndim != 2 or nu.shape != (of.shape[0], N) or of.shape[1] != N + len(tables['site_count']):
@@ -393,6 +407,8 @@ class Calculator(object):
             site_density = self.tp.system.get('active site density', tables['site_density'])
         tables['site_density'] = float(site_density)
         self.microkinetics = {'tables': tables, 'potential_drop': potential_drop, 'gamma': None if gamma is None else np.asarray(gamma, float)}
+        if interacting:
+            self.microkinetics['ramp'] = int(ramp)
         if scf == 'newton':
             self.microkinetics['scf'] = 'newton'
         if rate_control:
@@ -456,7 +472,12 @@ class Calculator(object):
         return out
 
     def _kinetics_solver(self):
-        """The device context of the microkinetic solves (tests replace it)"""
+        """The device context of the microkinetic solves (tests replace it).  A model with lateral interactions or several site types
+        (set_microkinetics stored its ramp) gets the context of include/catint_interact.h behind the same solve()"""
+        micro = getattr(self, 'microkinetics', None) or {}
+        if 'ramp' in micro:
+            from . import _interact
+            return _interact.RampedKinetics(self.device, micro['ramp'])
         from . import _kinetics
         return _kinetics.KineticsSolver(self.device)
 

@@ -32,6 +32,11 @@ iteration; the same iterates as the default.  The figures of both are in profile
 intermediate whose free energy control the flux most, with Campbell's coefficient -- intrinsic (fixed surface state) and, with --newton,
 apparent (the coupled electrode: mass transport of CO2 takes its share of the control, so the apparent coefficients lie below the
 intrinsic ones; on an MI355X with --lanes 16 --newton: step 2 0.50 intrinsic, 0.43 apparent, CO2* 1.00 and 0.86).
+
+--interactions EV: the same mechanism with a CO self-interaction of EV eV per unit coverage (catint_amd.interactions.InteractingModel,
+include/catint_interact.h): the binding energy of CO rises with its own coverage, the first SCF iteration ramps the interaction in ten
+stages inside one launch (the reference's n_inter), later iterations warm-start at full strength.  Works with the default loop and
+with --newton; the rate-control and device-loop libraries are mean-field and refuse such a model.
 """
 import argparse
 import os
@@ -55,7 +60,13 @@ STEPS = ['CO2_g + *_t <-> CO2*_t',
 ENERGIES = {'CO2': (0.42, 0.015, 1.0e-4), 'COOH': (0.55, 0.010, 0.0), 'CO': (0.15, 0.002, 0.0), 'COOH-ele': (1.05, 0.010, 0.0)}
 
 
-def model(tp):
+def model(tp, co_self_interaction=None):
+    if co_self_interaction is not None:
+        from catint_amd.interactions import InteractingModel
+        return InteractingModel(list(tp.species.keys()), {a: ('t', n) for a, n in ADSORBATES.items()}, STEPS, ENERGIES,
+                                interactions={('CO', 'CO'): co_self_interaction},
+                                solution={'CO2_g': 'CO2', 'CO_g': 'CO', 'OH_g': 'OH-', 'H2O_g': None}, solution_energies={'CO': 0.30},
+                                temperature=tp.system['temperature'])
     return MeanFieldModel(list(tp.species.keys()), ADSORBATES, STEPS, ENERGIES, solution={'CO2_g': 'CO2', 'CO_g': 'CO', 'OH_g': 'OH-', 'H2O_g': None},
                           solution_energies={'CO': 0.30}, temperature=tp.system['temperature'])
 
@@ -71,13 +82,16 @@ def main():
     ap.add_argument('--newton', action='store_true', help='Newton iteration on the wall fluxes instead of the mixing loop')
     ap.add_argument('--device-loop', action='store_true', help='the mixing loop on the device, no host round trip per iteration')
     ap.add_argument('--rate-control', action='store_true', help='degree of rate control of the CO flux at the final state of every lane')
+    ap.add_argument('--interactions', type=float, default=None, metavar='EV', help='CO self-interaction in eV per unit coverage')
     a = ap.parse_args()
+    if a.interactions is not None and (a.device_loop or a.rate_control):
+        ap.error('--device-loop and --rate-control work on the mean-field model: they exclude --interactions')
     if a.newton and a.device_loop:
         ap.error('--device-loop is the mixing loop on the device: it excludes --newton')
     tp, phis = co2r_physical_sweep.build(a.lanes, a.nx, a.phimin, a.phimax)
     tp.newton = {'tol': 1e-8, 'maxit': 80}
     calc = Calculator(transport=tp, calc='comsol', tau_scf=1e-4, mix_scf=0.1)
-    calc.set_microkinetics(model(tp), site_density=a.site_fraction * float(tp.system['active site density']), potential_drop='stern',
+    calc.set_microkinetics(model(tp, a.interactions), site_density=a.site_fraction * float(tp.system['active site density']), potential_drop='stern',
                           scf='newton' if a.newton else 'mixing', rate_control=a.rate_control, device_loop=a.device_loop)
     names = list(tp.species.keys())
     t0 = time.time()
