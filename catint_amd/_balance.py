@@ -2,16 +2,14 @@
 physical mode derived on the device (``catint_amd/lib/libcatint_balance.so``, built by ``catint_amd.build.build_balance_library()``).
 No fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _devlib
-from ._capi import flatten_reactions as reaction_table      # the arrays of pnp_set_reactions: catbal_params takes the same form
-from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
+from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _PD, _PI, _PL, _dptr, _f64, _iptr  # noqa: F401  (part of this module's interface)
+from ._medium import Medium, reaction_table  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_BALANCE_LIB') or os.path.join(_HERE, 'lib', 'libcatint_balance.so')
+LIB_PATH = _devlib.lib_path('balance')
 
 # every symbol include/catint_balance.h declares (tests/test_balance_abi.py)
 SYMBOLS = _devlib.symbols('catbal_', 'species')
@@ -25,13 +23,8 @@ FIELDS = {'flux': lambda N, nx, R, W: (N, nx - 1), 'reaction_rate': lambda N, nx
           'wall_rate': lambda N, nx, R, W: (W,), 'wall_flux': lambda N, nx, R, W: (N,), 'imbalance': lambda N, nx, R, W: (N, nx)}
 
 
-class BalanceError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_balance error %d: %s' % (code, msg))
-        self.code = code
-
-
-_PD, _PI = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+class BalanceError(_devlib.LibraryError):
+    library = 'catint_balance'
 
 
 class CatbalParams(C.Structure):
@@ -45,22 +38,7 @@ class CatbalOutputs(C.Structure):
     _fields_ = [(n, _PD) for n in tuple(FIELDS) + ('scalars',)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catbal_', 'species', CatbalParams, CatbalOutputs, BalanceError)
-    return _lib
-
-
-def _iptr(a):
-    return a.ctypes.data_as(_PI) if a is not None else None
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+load_library = _devlib.loader(globals(), 'catbal_', 'species', CatbalParams, CatbalOutputs, BalanceError)
 
 
 class Balancer(_devlib.Handle):
@@ -73,30 +51,16 @@ class Balancer(_devlib.Handle):
         a dict {'species' [n], 'nu' [n][N], 'k' [B][n], 'alpha' [n] or None, 'saturation' [n] or None}; flux [B][N], phiM [B].
         fields: names out of FIELDS (None: all); returns a dict of the requested rows and, with scalars, 'scalars' [B][N][NSCALARS]
         (columns: SCALARS)."""
-        B, N, nx = max(int(view.batch), 0), max(int(view.nspecies), 0), max(int(view.nx), 0)
-        names = list(FIELDS) if fields is None else list(fields)
-        for n in names:
-            if n not in FIELDS:
-                raise ValueError('unknown field %r (known: %s)' % (n, ', '.join(FIELDS)))
-        R, n_lhs, lhs, n_rhs, rhs, kf, kr = reaction_table(list(reactions))
-        W = 0 if not wall else len(wall['species'])
-        keep = [_f64(a) for a in (D, charges, x, mpb_radius, flux, phiM)]
-        wk = [None] * 5
-        if W:
-            wk = [np.ascontiguousarray(wall['species'], dtype=np.int32), _f64(wall['nu']), _f64(wall.get('k')), _f64(wall.get('alpha')),
-                  _f64(wall.get('saturation'))]
-        for name, a, n in (('flux', keep[4], B * N), ('phiM', keep[5], B), ('wall k', wk[2], B * W), ('wall nu', wk[1], W * N),
-                           ('wall alpha', wk[3], W), ('wall saturation', wk[4], W), ('mpb_radius', keep[3], N)):
-            if a is not None and a.size != n:
-                raise ValueError('%s has %d values, the view needs %d' % (name, a.size, n))
-        if keep[0].size < N or keep[1].size < N or keep[2].size < nx:
-            raise ValueError('D, charges or x shorter than the view')
-        p = CatbalParams(C.sizeof(CatbalParams) if struct_size is None else int(struct_size), int(max_waves), R, W,
-                         _dptr(keep[0]), _dptr(keep[1]), _dptr(keep[3]), _dptr(keep[2]), float(beta), float(velocity),
-                         _iptr(n_lhs), _iptr(lhs), _iptr(n_rhs), _iptr(rhs), _dptr(kf), _dptr(kr),
-                         _iptr(wk[0]), _dptr(wk[1]), _dptr(wk[2]), _dptr(wk[3]), _dptr(wk[4]), _dptr(keep[4]), _dptr(keep[5]))
-        dims = (N, nx, max(R, 0), max(W, 0))
-        out = {n: np.empty((B,) + tuple(max(d, 0) for d in FIELDS[n](*dims))) for n in names}
+        names = _devlib.field_names(fields, FIELDS)
+        medium = Medium(view, D, charges, x, beta, mpb_radius, velocity, reactions, max_waves=max_waves, wall=wall)
+        B, N, nx = medium.dims
+        g, pm = _f64(flux), _f64(phiM)
+        medium.check('the view needs', [('flux', g, B * N), ('phiM', pm, B)])
+        members = dict(medium.members)
+        members['species'] = members.pop('wall_species')          # (catbal_params has no other `species`)
+        p = CatbalParams(struct_size=_devlib.size_of(CatbalParams, struct_size), flux=_dptr(g), phiM=_dptr(pm), **members)
+        dims = (N, nx, members['nreactions'], members['n_wall'])
+        out = _devlib.results(None, {n: tuple(max(d, 0) for d in FIELDS[n](*dims)) for n in names}, (B,))
         if scalars:
             out['scalars'] = np.empty((B, N, NSCALARS))
         o = CatbalOutputs(**{n: _dptr(a) for n, a in out.items()})

@@ -6,6 +6,7 @@ CPU fallback: if the library is missing, or no HIP device is visible, the transp
 raises (``PnpLibraryError`` / ``PnpError``).
 """
 import ctypes as C
+import importlib
 import os
 
 import numpy as np
@@ -239,6 +240,15 @@ def flatten_reactions(reactions):
 class PnpSolver(object):
     """Thin object wrapper over one ``pnp_handle`` (one GPU)."""
 
+    # the contexts of the satellite libraries a solver opens on first use (_satellite) and close() destroys, in this order:
+    # attribute -> (module of this package, class)
+    SATELLITES = {'_observer': ('_observe', 'Observer'), '_balancer': ('_balance', 'Balancer'), '_regridder': ('_regrid', 'Regridder'),
+                  '_equilibrator': ('_equil', 'Equilibrator'), '_responder': ('_response', 'Responder'),
+                  '_kinetics': ('_kinetics', 'KineticsSolver'), '_coupler': ('_couple', 'Coupler'), '_sensitizer': ('_sens', 'Sensitizer'),
+                  '_rate_control': ('_drc', 'RateControl'), '_transient': ('_kintrans', 'TransientKinetics'),
+                  '_impedance': ('_eis', 'Impedance'), '_interact': ('_interact', 'InteractingKinetics'),
+                  '_mode_solver': ('_modes', 'ModeSolver')}
+
     def __init__(self, nspecies, nx, dx, dt, beta, eps, D, charges, method='Crank-Nicolson', pb_mode=PB_DD,
                  lax_friedrich=False, use_migration=True, batch_capacity=1, device=0):
         self._lib = load_library()
@@ -266,60 +276,27 @@ class PnpSolver(object):
                      # ... and what equilibrium / set_equilibrium hand to the equilibrium library
                      'eps': float(eps), 'dx': float(dx), 'wall_bc': 'dirichlet', 'stern_capacitance': 0.0, 'phi_pzc': 0.0,
                      'c_bulk': None, 'phi_bulk': None}
-        self._equilibrator = None
-        self._observer = None
-        self._balancer = None
-        self._regridder = None
-        self._responder = None
-        self._kinetics = None
-        self._coupler = None
-        self._sensitizer = None
-        self._rate_control = None
-        self._transient = None
-        self._impedance = None
-        self._interact = None
+        for attr in self.SATELLITES:
+            setattr(self, attr, None)
 
     def _check(self, rc):
         if rc != 0:
             raise PnpError(rc, self._lib.pnp_last_error(self._h).decode())
 
+    def _satellite(self, attr):
+        """The context of a satellite library, opened on this solver's device at its first use"""
+        handle = getattr(self, attr, None)
+        if handle is None:
+            module, cls = self.SATELLITES[attr]
+            handle = getattr(importlib.import_module('.' + module, __package__), cls)(self._obs['device'])
+            setattr(self, attr, handle)
+        return handle
+
     def close(self):
-        if getattr(self, '_observer', None) is not None:
-            self._observer.close()
-            self._observer = None
-        if getattr(self, '_balancer', None) is not None:
-            self._balancer.close()
-            self._balancer = None
-        if getattr(self, '_regridder', None) is not None:
-            self._regridder.close()
-            self._regridder = None
-        if getattr(self, '_equilibrator', None) is not None:
-            self._equilibrator.close()
-            self._equilibrator = None
-        if getattr(self, '_responder', None) is not None:
-            self._responder.close()
-            self._responder = None
-        if getattr(self, '_kinetics', None) is not None:
-            self._kinetics.close()
-            self._kinetics = None
-        if getattr(self, '_coupler', None) is not None:
-            self._coupler.close()
-            self._coupler = None
-        if getattr(self, '_sensitizer', None) is not None:
-            self._sensitizer.close()
-            self._sensitizer = None
-        if getattr(self, '_rate_control', None) is not None:
-            self._rate_control.close()
-            self._rate_control = None
-        if getattr(self, '_transient', None) is not None:
-            self._transient.close()
-            self._transient = None
-        if getattr(self, '_impedance', None) is not None:
-            self._impedance.close()
-            self._impedance = None
-        if getattr(self, '_interact', None) is not None:
-            self._interact.close()
-            self._interact = None
+        for attr in self.SATELLITES:          # (getattr: close() also ends an object whose constructor raised)
+            if getattr(self, attr, None) is not None:
+                getattr(self, attr).close()
+                setattr(self, attr, None)
         if getattr(self, '_h', None) is not None and self._h.value:
             self._lib.pnp_destroy(self._h)
             self._h = C.c_void_p()
@@ -538,12 +515,10 @@ class PnpSolver(object):
         solver was given.  to_host: (c [n][N][nx_target], phi [n][nx_target]); otherwise nothing crosses PCIe and the result is
         (c_dev, phi_dev), integer device addresses of rows with the pitch of a handle of len(x_target) points, valid until the next
         resample / resample_to / close of this solver (set_lanes_device of such a handle takes them)."""
-        from . import _regrid
-        if self._regridder is None:
-            self._regridder = _regrid.Regridder(self._obs['device'])
         o = self._obs
-        out = self._regridder.resample(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], x_target, mpb_radius=o['mpb_radius'],
-                                       velocity=o['velocity'], lanes=lanes, to_host=to_host, device=not to_host, max_waves=max_waves)
+        out = self._satellite('_regridder').resample(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], x_target,
+                                                     mpb_radius=o['mpb_radius'], velocity=o['velocity'], lanes=lanes, to_host=to_host,
+                                                     device=not to_host, max_waves=max_waves)
         return (out['c'], out['phi']) if to_host else (out['c_dev'], out['phi_dev'])
 
     def resample_to(self, other, lanes=None, dst_lanes=None):
@@ -566,20 +541,15 @@ class PnpSolver(object):
         [n] (0, or 1: not converged within maxit), 'iterations' [n]; with to_host 'c' [n][N][nx] and 'phi' [n][nx]; otherwise nothing
         but the flags crosses PCIe and 'c_dev' / 'phi_dev' are integer device addresses of rows with this handle's pitch, valid until
         the next equilibrium / set_equilibrium / close of this solver (set_lanes_device takes them)."""
-        from . import _equil
         o = self._obs
         if o['c_bulk'] is None:
             raise ValueError('equilibrium: no batch was set')
-        idx = np.arange(self.B) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-            raise ValueError('equilibrium: lane index outside [0, %d)' % self.B)
+        idx = self._lanes('equilibrium', lanes)
         pm = o['phiM'][idx] if phiM is None else np.broadcast_to(np.asarray(phiM, float), (len(idx),))
-        if self._equilibrator is None:
-            self._equilibrator = _equil.Equilibrator(o['device'])
-        return self._equilibrator.solve(self.device_view(), o['charges'], o['x'], o['beta'], o['eps'], o['dx'], pm, o['phi_bulk'][idx],
-                                        o['c_bulk'][idx], mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
-                                        stern_capacitance=o['stern_capacitance'], phi_pzc=o['phi_pzc'], tol=tol, maxit=maxit,
-                                        to_host=to_host, device=not to_host, max_waves=max_waves)
+        return self._satellite('_equilibrator').solve(self.device_view(), o['charges'], o['x'], o['beta'], o['eps'], o['dx'], pm,
+                                                      o['phi_bulk'][idx], o['c_bulk'][idx], mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
+                                                      stern_capacitance=o['stern_capacitance'], phi_pzc=o['phi_pzc'], tol=tol, maxit=maxit,
+                                                      to_host=to_host, device=not to_host, max_waves=max_waves)
 
     def set_equilibrium(self, phiM=None, lanes=None, tol=1e-10, maxit=100):
         """The device path of an equilibrium start: equilibrium(...) of the lanes `lanes` (None: all) written into those lanes by
@@ -690,21 +660,94 @@ class PnpSolver(object):
         self._check(self._lib.pnp_get_device_view(self._h, C.byref(view)))
         return view
 
+    # -- the rules the get_* methods share; `method` is the caller's name, for its messages ------
+    def _lanes(self, method, lanes):
+        """the lane list checked against the batch; None: all lanes, in order"""
+        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+            raise ValueError('%s: lane index outside [0, %d)' % (method, self.B))
+        return idx
+
+    def _wall_table(self, method):
+        """the wall table a library is given: none after scf_cycle, whose solves took the wall reactions through the prescribed flux"""
+        o = self._obs
+        wall = None if o['explicit_kinetics'] else o['wall']
+        if wall is not None and o['wall_stale']:
+            raise ValueError('%s: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall table whose rate '
+                             'constants were not recorded for this batch: call set_wall_kinetics again' % method)
+        return wall
+
+    def _recorded_flux(self, method, flux):
+        """flux, or the wall fluxes this solver was given last"""
+        if flux is None:
+            if self._obs['flux_stale']:
+                raise ValueError('%s: scf_cycle updated the wall fluxes on the device; pass flux= (state["flux"] of the loop)' % method)
+            flux = self._obs['flux']
+        return flux
+
+    @staticmethod
+    def _model_tables(model_or_tables, site_density):
+        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
+        if site_density is not None:
+            tables['site_density'] = float(site_density)
+        return tables
+
+    def _kinetic_points(self, method, lanes, phiM, csurf, phi_surface):
+        """(host, idx, phiM) of a microkinetic call: host: the surface state comes from csurf / phi_surface, not from this handle; idx:
+        the lane list (None on the host path with phiM given: one point per entry of phiM); phiM: as given, or that of the lanes"""
+        host = csurf is not None or phi_surface is not None
+        if lanes is not None:
+            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        elif host and phiM is not None:
+            idx = None
+        else:
+            idx = np.arange(self.B, dtype=np.int64)
+        if phiM is None:
+            if self._obs['phiM'] is None:
+                raise ValueError('%s: no batch was set' % method)
+            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
+                raise ValueError('%s: lane index outside [0, %d)' % (method, self.B))
+            phiM = np.asarray(self._obs['phiM'], float)[idx]
+        return host, idx, phiM
+
+    def _kinetic_common(self, potential_drop, stern_capacitance=None, phi_pzc=None, **more):
+        """the arguments every microkinetic library takes; None: the Stern layer this solver was given (set_newton)"""
+        o = self._obs
+        return dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
+                    phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, **more)
+
+    @staticmethod
+    def _impedance_of(admittance):
+        """1 / admittance, inf where it is 0"""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(admittance == 0, np.inf, 1.0 / np.where(admittance == 0, 1.0, admittance))
+
+    @staticmethod
+    def _ask(names, needed):
+        """the fields to ask a library for: `names` and what the method needs on top of them; _trim deletes the latter afterwards"""
+        return list(names) + [k for k in needed if k not in names]
+
+    @staticmethod
+    def _trim(res, ask, names):
+        for k in ask:
+            if k not in names:
+                del res[k]
+        return res
+
     def get_electrolyte(self, fields=None, scalars=True, species_H=-1, species_OH=-1, max_waves=0):
         """Electrolyte observables of the physical mode derived on the device (include/catint_observe.h): a dict of the rows named in
         `fields` (catint_amd._observe.FIELDS; None: all of them; without species_H and species_OH no 'pH') and, with scalars, 'scalars'
         [B][NSCALARS] (columns: catint_amd._observe.SCALARS).  D, charges, ion radii, grid and velocity are the ones this solver was
         given.  Only what is asked for crosses PCIe: a scalars-only call moves 80 bytes per operating point."""
         from . import _observe
-        if self._observer is None:
-            self._observer = _observe.Observer(self._obs['device'])
+        observer = self._satellite('_observer')
         names = list(_observe.FIELDS) if fields is None else list(fields)
         if species_H < 0 and species_OH < 0 and fields is None:
             names.remove('pH')
         o = self._obs
-        return self._observer.electrolyte(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], mpb_radius=o['mpb_radius'],
-                                          velocity=o['velocity'], species_H=species_H, species_OH=species_OH, fields=names,
-                                          scalars=scalars, max_waves=max_waves)
+        return observer.electrolyte(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], mpb_radius=o['mpb_radius'],
+                                    velocity=o['velocity'], species_H=species_H, species_OH=species_OH, fields=names, scalars=scalars,
+                                    max_waves=max_waves)
 
     def get_balance(self, fields=None, scalars=True, flux=None, phiM=None, max_waves=0):
         """The per-species picture of the physical mode derived on the device (include/catint_balance.h): a dict of the rows named in
@@ -717,24 +760,15 @@ class PnpSolver(object):
         next solve_stationary / solve_surface / step the balance is formed without the table: 'wall_flux' is the flux passed,
         'wall_rate' is empty.  After a set_batch with another batch size the recorded rate constants of the wall table are not the
         ones the handle applies: ValueError until set_wall_kinetics is called again."""
-        from . import _balance
         o = self._obs
-        wall = None if o['explicit_kinetics'] else o['wall']
-        if wall is not None and o['wall_stale']:
-            raise ValueError('get_balance: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall table '
-                             'whose rate constants were not recorded for this batch: call set_wall_kinetics again')
-        if flux is None:
-            if o['flux_stale']:
-                raise ValueError('get_balance: scf_cycle updated the wall fluxes on the device; pass flux= (state["flux"] of the loop)')
-            flux = o['flux']
+        wall = self._wall_table('get_balance')
+        flux = self._recorded_flux('get_balance', flux)
         phiM = o['phiM'] if phiM is None else phiM
         if flux is None or phiM is None:
             raise ValueError('get_balance: no batch was set')
-        if self._balancer is None:
-            self._balancer = _balance.Balancer(o['device'])
-        return self._balancer.species(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], flux, phiM, mpb_radius=o['mpb_radius'],
-                                      velocity=o['velocity'], reactions=o['reactions'], wall=wall, fields=fields, scalars=scalars,
-                                      max_waves=max_waves)
+        return self._satellite('_balancer').species(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], flux, phiM,
+                                                    mpb_radius=o['mpb_radius'], velocity=o['velocity'], reactions=o['reactions'], wall=wall,
+                                                    fields=fields, scalars=scalars, max_waves=max_waves)
 
     def get_response(self, omega=(0.0,), perturbation='phiM', lanes=None, profiles=False, max_waves=0):
         """The linear response of the stationary state this handle holds (include/catint_response.h), solved on the device: how the
@@ -753,25 +787,18 @@ class PnpSolver(object):
         meaning.  After scf_cycle the solves took the wall reactions through the prescribed flux, so the response is formed without
         the wall table (the rule of get_balance); after a set_batch with another batch size the recorded rate constants of the wall
         table are not the ones the handle applies: ValueError until set_wall_kinetics is called again."""
-        from . import _response
         o = self._obs
-        wall = None if o['explicit_kinetics'] else o['wall']
-        if wall is not None and o['wall_stale']:
-            raise ValueError('get_response: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall table '
-                             'whose rate constants were not recorded for this batch: call set_wall_kinetics again')
+        wall = self._wall_table('get_response')
         if o['phiM'] is None:
             raise ValueError('get_response: no batch was set')
-        if self._responder is None:
-            self._responder = _response.Responder(o['device'])
+        responder = self._satellite('_responder')
         om = np.atleast_1d(np.asarray(omega, float)).reshape(-1)
-        out = self._responder.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], omega=om,
-                                    perturbation=perturbation, lanes=lanes, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
-                                    stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], wall=wall,
-                                    profiles=profiles, max_waves=max_waves)
+        out = responder.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], omega=om,
+                              perturbation=perturbation, lanes=lanes, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
+                              stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], wall=wall,
+                              profiles=profiles, max_waves=max_waves)
         out['omega'] = om.copy()
-        with np.errstate(divide='ignore', invalid='ignore'):
-            y = out['admittance']
-            out['impedance'] = np.where(y == 0, np.inf, 1.0 / np.where(y == 0, 1.0, y))
+        out['impedance'] = self._impedance_of(out['admittance'])
         zero = np.flatnonzero(om == 0.0)
         if len(zero):
             out['differential_capacitance'] = out['dsigma'][:, zero[0]].real.copy()
@@ -805,56 +832,31 @@ class PnpSolver(object):
         from .interactions import has_interactions
         if rescue and theta_guess is not None:
             raise ValueError('get_kinetics: rescue=True starts from the uniform surface and excludes theta_guess')
-        o = self._obs
-        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
-        if site_density is not None:
-            tables['site_density'] = float(site_density)
-        host = csurf is not None or phi_surface is not None
-        if lanes is not None:
-            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        elif host and phiM is not None:
-            idx = None
-        else:
-            idx = np.arange(self.B, dtype=np.int64)
-        if phiM is None:
-            if o['phiM'] is None:
-                raise ValueError('get_kinetics: no batch was set')
-            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-                raise ValueError('get_kinetics: lane index outside [0, %d)' % self.B)
-            phiM = np.asarray(o['phiM'], float)[idx]
+        tables = self._model_tables(model_or_tables, site_density)
+        host, idx, phiM = self._kinetic_points('get_kinetics', lanes, phiM, csurf, phi_surface)
         interacting = has_interactions(tables)
         if interacting:
             from . import _interact
             if rescue:
                 raise ValueError('get_kinetics: rescue=True integrates the mean-field model (include/catint_kintrans.h); this model has '
                                  'lateral interactions or several site types')
-            if getattr(self, '_interact', None) is None:
-                self._interact = _interact.InteractingKinetics(o['device'])
         elif ramp is not None:
             raise ValueError('get_kinetics: ramp belongs to a model with lateral interactions or several site types')
-        elif self._kinetics is None:
-            self._kinetics = _kinetics.KineticsSolver(o['device'])
+        solver = self._satellite('_interact' if interacting else '_kinetics')
         view = None if host else self.device_view()
-        common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
-                      phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, tol=_kinetics.DEFAULT_TOL if tol is None else tol,
-                      maxit=_kinetics.DEFAULT_MAXIT if maxit is None else maxit, fields=fields, max_waves=max_waves)
+        common = self._kinetic_common(potential_drop, stern_capacitance, phi_pzc, tol=_kinetics.DEFAULT_TOL if tol is None else tol,
+                                      maxit=_kinetics.DEFAULT_MAXIT if maxit is None else maxit, fields=fields, max_waves=max_waves)
         if interacting:
-            return self._interact.solve(view, tables, phiM, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, sigma=sigma,
-                                        off=off, gamma=gamma, theta_guess=theta_guess,
-                                        ramp=(_interact.SCF_RAMP if theta_guess is None else 1) if ramp is None else ramp, **common)
-        res = self._kinetics.solve(view, tables, phiM, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, sigma=sigma, off=off,
-                                   gamma=gamma, theta_guess=theta_guess, **common)
+            return solver.solve(view, tables, phiM, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, sigma=sigma, off=off,
+                                gamma=gamma, theta_guess=theta_guess,
+                                ramp=(_interact.SCF_RAMP if theta_guess is None else 1) if ramp is None else ramp, **common)
+        res = solver.solve(view, tables, phiM, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, sigma=sigma, off=off,
+                           gamma=gamma, theta_guess=theta_guess, **common)
         if rescue:
             from . import _kintrans
-            _kintrans.rescue(self._kinetics, self._transient_kinetics(), view, tables, phiM, res, lanes=None if host else idx,
+            _kintrans.rescue(solver, self._satellite('_transient'), view, tables, phiM, res, lanes=None if host else idx,
                              per_point=dict(csurf=csurf, phi_surface=phi_surface, sigma=sigma, off=off, gamma=gamma), **common)
         return res
-
-    def _transient_kinetics(self):
-        from . import _kintrans
-        if getattr(self, '_transient', None) is None:
-            self._transient = _kintrans.TransientKinetics(self._obs['device'])
-        return self._transient
 
     def get_kinetics_transient(self, model_or_tables, t_out, phiM=None, lanes=None, csurf=None, phi_surface=None, theta0=None, rtol=1e-4,
                                atol=1e-12, steady_tol=0.0, fields=None, potential_drop='stern', stern_capacitance=None, phi_pzc=None,
@@ -872,30 +874,15 @@ class PnpSolver(object):
         time reached; 1 stopped stationary, the remaining rows hold that state; 2 unsolved lane or non-finite input: NaN; 3 max_steps
         were not enough, the rows not reached are NaN) and 'steps' [n][3] (accepted, rejected, Newton iterations)."""
         from . import _kintrans
-        o = self._obs
-        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
-        if site_density is not None:
-            tables['site_density'] = float(site_density)
-        host = csurf is not None or phi_surface is not None
-        if lanes is not None:
-            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        elif host and phiM is not None:
-            idx = None
-        else:
-            idx = np.arange(self.B, dtype=np.int64)
-        if phiM is None:
-            if o['phiM'] is None:
-                raise ValueError('get_kinetics_transient: no batch was set')
-            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-                raise ValueError('get_kinetics_transient: lane index outside [0, %d)' % self.B)
-            phiM = np.asarray(o['phiM'], float)[idx]
-        return self._transient_kinetics().solve(
+        tables = self._model_tables(model_or_tables, site_density)
+        host, idx, phiM = self._kinetic_points('get_kinetics_transient', lanes, phiM, csurf, phi_surface)
+        return self._satellite('_transient').solve(
             None if host else self.device_view(), tables, phiM, t_out, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface,
-            potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
-            phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma, theta0=theta0, rtol=rtol, atol=atol,
-            steady_tol=steady_tol, h0=h0, newton_tol=_kintrans.DEFAULT_NEWTON_TOL if newton_tol is None else newton_tol,
+            theta0=theta0, rtol=rtol, atol=atol, steady_tol=steady_tol, h0=h0,
+            newton_tol=_kintrans.DEFAULT_NEWTON_TOL if newton_tol is None else newton_tol,
             newton_maxit=_kintrans.DEFAULT_NEWTON_MAXIT if newton_maxit is None else newton_maxit,
-            max_steps=_kintrans.DEFAULT_MAX_STEPS if max_steps is None else max_steps, fields=fields, max_waves=max_waves)
+            max_steps=_kintrans.DEFAULT_MAX_STEPS if max_steps is None else max_steps, fields=fields, max_waves=max_waves,
+            **self._kinetic_common(potential_drop, stern_capacitance, phi_pzc, sigma=sigma, off=off, gamma=gamma))
 
     def get_rate_control(self, model_or_tables, theta=None, phiM=None, lanes=None, csurf=None, phi_surface=None, fields=None,
                          potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None,
@@ -913,46 +900,24 @@ class PnpSolver(object):
         through mass transport: 'dflux_drc_apparent', 'dflux_dG_apparent' = M^-1 (rf dflux), M = I - rf (K_c T_c + K_phi (x) T_phi)
         formed per point on the host, and 'drc_apparent', 'tdrc_apparent' normalised by rf flux (NaN rows where M is singular)."""
         from . import _drc
-        o = self._obs
-        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
-        if site_density is not None:
-            tables['site_density'] = float(site_density)
+        tables = self._model_tables(model_or_tables, site_density)
         if (kin is None) != (coupling is None):
             raise ValueError('get_rate_control: kin and coupling come together')
-        host = csurf is not None or phi_surface is not None
-        if lanes is not None:
-            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        elif host and phiM is not None:
-            idx = None
-        else:
-            idx = np.arange(self.B, dtype=np.int64)
-        if phiM is None:
-            if o['phiM'] is None:
-                raise ValueError('get_rate_control: no batch was set')
-            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-                raise ValueError('get_rate_control: lane index outside [0, %d)' % self.B)
-            phiM = np.asarray(o['phiM'], float)[idx]
-        common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
-                      phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma)
+        host, idx, phiM = self._kinetic_points('get_rate_control', lanes, phiM, csurf, phi_surface)
+        common = self._kinetic_common(potential_drop, stern_capacitance, phi_pzc, sigma=sigma, off=off, gamma=gamma)
         if theta is None:
             theta = self.get_kinetics(tables, phiM=phiM, lanes=lanes, csurf=csurf, phi_surface=phi_surface, fields=('theta',), max_waves=max_waves,
                                       **common)['theta']
         names = list(_drc.DEFAULT_FIELDS) if fields is None else list(fields)
-        ask = list(names)
-        if kin is not None:
-            ask += [k for k in ('dflux_drc', 'dflux_dG', 'flux') if k not in ask]
-        if getattr(self, '_rate_control', None) is None:
-            self._rate_control = _drc.RateControl(o['device'])
-        res = self._rate_control.solve(None if host else self.device_view(), tables, phiM, theta, lanes=None if host else idx, csurf=csurf,
-                                       phi_surface=phi_surface, residual_tol=residual_tol, fields=ask, max_waves=max_waves, **common)
+        ask = self._ask(names, ('dflux_drc', 'dflux_dG', 'flux') if kin is not None else ())
+        res = self._satellite('_rate_control').solve(None if host else self.device_view(), tables, phiM, theta, lanes=None if host else idx,
+                                                     csurf=csurf, phi_surface=phi_surface, residual_tol=residual_tol, fields=ask,
+                                                     max_waves=max_waves, **common)
         if kin is not None:
             for raw, norm in (('dflux_drc', 'drc'), ('dflux_dG', 'tdrc')):
                 res[raw + '_apparent'] = _drc.apparent(res[raw], kin, coupling, rf=rf)
                 res[norm + '_apparent'] = _drc.normalised(res[raw + '_apparent'], rf * res['flux'], tables['nu'])
-        for k in ask:
-            if k not in names:
-                del res[k]
-        return res
+        return self._trim(res, ask, names)
 
     def get_coupling(self, flux, kin, rf=1.0, lanes=None, dphi_max=0.05, fields=None, max_waves=0):
         """One Newton step of the self-consistency between kinetics and transport (include/catint_couple.h), formed on the device
@@ -969,7 +934,6 @@ class PnpSolver(object):
         finite, outputs NaN; 3: the Newton matrix is singular).  D, charges, ion radii, grid, wall model, velocity and reactions are the
         ones this solver was given.  The state must have been solved with prescribed fluxes only: with a wall table set
         (set_wall_kinetics) the call raises ValueError."""
-        from . import _couple
         o = self._obs
         if o['wall'] is not None and not o['explicit_kinetics']:
             raise ValueError('get_coupling: the handle applies a wall table (set_wall_kinetics); the coupling is defined for a state solved '
@@ -979,25 +943,15 @@ class PnpSolver(object):
                 raise ValueError('get_coupling: no recorded wall fluxes; pass flux=')
             flux = o['flux']
         g = np.asarray(_f64(flux, (self.B, self.N)))
-        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-            raise ValueError('get_coupling: lane index outside [0, %d)' % self.B)
+        idx = self._lanes('get_coupling', lanes)
         n = len(idx)
         K = np.asarray(kin['flux'], float).reshape(n, self.N)
         Kc = np.asarray(kin['dflux_dc'], float).reshape(n, self.N, self.N)
         Kphi = np.ascontiguousarray(np.asarray(kin['dflux_dphi'], float).reshape(n, self.N, 2)[:, :, 1])
-        if getattr(self, '_coupler', None) is None:
-            self._coupler = _couple.Coupler(o['device'])
-        return self._coupler.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], g[idx], K, Kc, Kphi, rf=rf,
-                                   dphi_max=dphi_max, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
-                                   stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], fields=fields,
-                                   max_waves=max_waves)
-
-    def _eis_handle(self):
-        from . import _eis
-        if getattr(self, '_impedance', None) is None:
-            self._impedance = _eis.Impedance(self._obs['device'])
-        return self._impedance
+        return self._satellite('_coupler').solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], g[idx], K, Kc,
+                                                 Kphi, rf=rf, dphi_max=dphi_max, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
+                                                 stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'],
+                                                 fields=fields, max_waves=max_waves)
 
     def get_kinetic_admittance(self, model_or_tables, omega, theta=None, phiM=None, lanes=None, csurf=None, phi_surface=None, fields=None,
                                potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None,
@@ -1012,31 +966,16 @@ class PnpSolver(object):
         [n][F][S+1][N+2] = d ln theta, 'residual' [n] = max_s |G_s| / D_s, 'status' [n][F] (0; 2: unsolved lane or non-finite input,
         NaN; 3: bad pivot; 4: residual above residual_tol) and 'omega' [F].  At omega = 0 Kc and Kphi are get_kinetics' dflux_dc and
         dflux_dphi."""
-        o = self._obs
-        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
-        if site_density is not None:
-            tables['site_density'] = float(site_density)
-        host = csurf is not None or phi_surface is not None
-        if lanes is not None:
-            idx = np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        elif host and phiM is not None:
-            idx = None
-        else:
-            idx = np.arange(self.B, dtype=np.int64)
-        if phiM is None:
-            if o['phiM'] is None:
-                raise ValueError('get_kinetic_admittance: no batch was set')
-            if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-                raise ValueError('get_kinetic_admittance: lane index outside [0, %d)' % self.B)
-            phiM = np.asarray(o['phiM'], float)[idx]
-        common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'] if stern_capacitance is None else stern_capacitance,
-                      phi_pzc=o['phi_pzc'] if phi_pzc is None else phi_pzc, sigma=sigma, off=off, gamma=gamma)
+        tables = self._model_tables(model_or_tables, site_density)
+        host, idx, phiM = self._kinetic_points('get_kinetic_admittance', lanes, phiM, csurf, phi_surface)
+        common = self._kinetic_common(potential_drop, stern_capacitance, phi_pzc, sigma=sigma, off=off, gamma=gamma)
         if theta is None:
             theta = self.get_kinetics(tables, phiM=phiM, lanes=lanes, csurf=csurf, phi_surface=phi_surface, fields=('theta',), max_waves=max_waves,
                                       **common)['theta']
         om = np.atleast_1d(np.asarray(omega, float)).reshape(-1)
-        out = self._eis_handle().kinetic(None if host else self.device_view(), tables, phiM, theta, om, lanes=None if host else idx, csurf=csurf,
-                                         phi_surface=phi_surface, residual_tol=residual_tol, fields=fields, max_waves=max_waves, **common)
+        out = self._satellite('_impedance').kinetic(None if host else self.device_view(), tables, phiM, theta, om, lanes=None if host else idx,
+                                                    csurf=csurf, phi_surface=phi_surface, residual_tol=residual_tol, fields=fields,
+                                                    max_waves=max_waves, **common)
         out['omega'] = om.copy()
         return out
 
@@ -1067,44 +1006,34 @@ class PnpSolver(object):
                              'defined for a state solved with prescribed wall fluxes only')
         if o['phiM'] is None:
             raise ValueError('get_impedance: no batch was set')
-        tables = model_or_tables.tables() if hasattr(model_or_tables, 'tables') else dict(model_or_tables)
-        if site_density is not None:
-            tables['site_density'] = float(site_density)
-        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-            raise ValueError('get_impedance: lane index outside [0, %d)' % self.B)
+        tables = self._model_tables(model_or_tables, site_density)
+        idx = self._lanes('get_impedance', lanes)
         if phiM is None:
             phiM = np.asarray(o['phiM'], float)[idx]
-        common = dict(potential_drop=potential_drop, stern_capacitance=o['stern_capacitance'], phi_pzc=o['phi_pzc'], sigma=sigma, off=off,
-                      gamma=gamma)
+        common = self._kinetic_common(potential_drop, sigma=sigma, off=off, gamma=gamma)
         if theta is None:
             theta = self.get_kinetics(tables, phiM=phiM, lanes=idx, fields=('theta',), max_waves=max_waves, **common)['theta']
         om = np.atleast_1d(np.asarray(omega, float)).reshape(-1)
         from . import _eis
         names = list(_eis.DEFAULT_FIELDS) + ['dtheta'] if fields is None else list(fields)
-        ask = [k for k in names if k != 'dtheta']
-        if 'dtheta' in names:
-            ask += [k for k in ('dy', 'dc_surface', 'dphi_surface') if k not in ask]
-        out = self._eis_handle().solve(self.device_view(), tables, phiM, theta, om, o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'],
-                                       rf=rf, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'], velocity=o['velocity'],
-                                       reactions=o['reactions'], residual_tol=residual_tol, fields=ask, max_waves=max_waves, **common)
+        ask = self._ask([k for k in names if k != 'dtheta'], ('dy', 'dc_surface', 'dphi_surface') if 'dtheta' in names else ())
+        out = self._satellite('_impedance').solve(self.device_view(), tables, phiM, theta, om, o['D'], o['charges'], o['x'], o['beta'], o['eps'],
+                                                  o['dx'], rf=rf, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
+                                                  velocity=o['velocity'], reactions=o['reactions'], residual_tol=residual_tol, fields=ask,
+                                                  max_waves=max_waves, **common)
         out['omega'] = om.copy()
         if 'admittance' in out:
-            with np.errstate(divide='ignore', invalid='ignore'):
-                y = out['admittance']
-                out['impedance'] = np.where(y == 0, np.inf, 1.0 / np.where(y == 0, 1.0, y))
-                zero = np.flatnonzero(om == 0.0)
-                if len(zero):
-                    out['polarization_resistance'] = 1.0 / y[:, zero[0]].real
+            out['impedance'] = self._impedance_of(out['admittance'])
+            zero = np.flatnonzero(om == 0.0)
+            if len(zero):
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    out['polarization_resistance'] = 1.0 / out['admittance'][:, zero[0]].real
         if 'dtheta' in names:
             N = self.N
             dy = out['dy']
             th = np.asarray(theta, float).reshape(len(idx), 1, -1)
             out['dtheta'] = th * (np.einsum('nftj,nfj->nft', dy[..., :N], out['dc_surface']) + dy[..., N] + dy[..., N + 1] * out['dphi_surface'][..., None])
-        for k in ask:
-            if k not in names:
-                del out[k]
-        return out
+        return self._trim(out, ask, names)
 
     def get_sensitivities(self, parameters, lanes=None, fields=None, flux=None, max_waves=0):
         """The sensitivities of the stationary state this handle holds to its model parameters (include/catint_sens.h), solved on the
@@ -1122,20 +1051,12 @@ class PnpSolver(object):
         and the wall table is left out; after a set_batch with another batch size the wall table must be set again (ValueError)."""
         from . import _sens
         o = self._obs
-        wall = None if o['explicit_kinetics'] else o['wall']
-        if wall is not None and o['wall_stale']:
-            raise ValueError('get_sensitivities: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall '
-                             'table whose rate constants were not recorded for this batch: call set_wall_kinetics again')
-        if flux is None:
-            if o['flux_stale']:
-                raise ValueError('get_sensitivities: scf_cycle updated the wall fluxes on the device; pass flux= (state["flux"] of the loop)')
-            flux = o['flux']
+        wall = self._wall_table('get_sensitivities')
+        flux = self._recorded_flux('get_sensitivities', flux)
         if flux is None or o['phiM'] is None:
             raise ValueError('get_sensitivities: no batch was set')
         g = np.asarray(_f64(flux, (self.B, self.N)))
-        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-            raise ValueError('get_sensitivities: lane index outside [0, %d)' % self.B)
+        idx = self._lanes('get_sensitivities', lanes)
         n, N = len(idx), self.N
         names = list(_sens.FIELDS) if fields is None else list(fields)
         # the columns the device solves: one per distinct (kind, index); a direction takes the single-species columns it weighs
@@ -1161,13 +1082,11 @@ class PnpSolver(object):
                 plan.append([(column(spec[0], spec[1]), 1.0)])
         if len(cols) > _sens.MAX_PARAMS:
             raise ValueError('get_sensitivities: %d columns, at most %d in one call' % (len(cols), _sens.MAX_PARAMS))
-        if getattr(self, '_sensitizer', None) is None:
-            self._sensitizer = _sens.Sensitizer(o['device'])
+        sensitizer = self._satellite('_sensitizer')
         dev = [k if k[0] in _sens.INDEXED else k[0] for k in sorted(cols, key=cols.get)]
-        raw = self._sensitizer.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], g[idx], dev,
-                                     lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'], stern_capacitance=o['stern_capacitance'],
-                                     phi_pzc=o['phi_pzc'], velocity=o['velocity'], reactions=o['reactions'], wall=wall, fields=names,
-                                     max_waves=max_waves)
+        raw = sensitizer.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], g[idx], dev, lanes=idx,
+                               mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'], stern_capacitance=o['stern_capacitance'], phi_pzc=o['phi_pzc'],
+                               velocity=o['velocity'], reactions=o['reactions'], wall=wall, fields=names, max_waves=max_waves)
         out = {'status': raw['status'], 'parameters': specs}
         for name in names:
             a = raw[name]
@@ -1242,15 +1161,10 @@ class PnpSolver(object):
         the wall table must be set again (ValueError)."""
         from . import _modes
         o = self._obs
-        wall = None if o['explicit_kinetics'] else o['wall']
-        if wall is not None and o['wall_stale']:
-            raise ValueError('get_relaxation: set_batch changed the batch size after set_wall_kinetics; the handle still applies a wall table '
-                             'whose rate constants were not recorded for this batch: call set_wall_kinetics again')
+        wall = self._wall_table('get_relaxation')
         if o['phiM'] is None:
             raise ValueError('get_relaxation: no batch was set')
-        idx = np.arange(self.B, dtype=np.int64) if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        if len(idx) and (idx.min() < 0 or idx.max() >= self.B):
-            raise ValueError('get_relaxation: lane index outside [0, %d)' % self.B)
+        idx = self._lanes('get_relaxation', lanes)
         m, N, nx = int(subspace), self.N, self.nx
         if not 1 <= m <= min(_modes.MAX_SUBSPACE, N * (nx - 1)):
             raise ValueError('get_relaxation: subspace = %d outside [1, %d]' % (m, min(_modes.MAX_SUBSPACE, N * (nx - 1))))
@@ -1261,12 +1175,10 @@ class PnpSolver(object):
         q0 = _modes.default_start(m, N, nx, seed) if start is None else np.asarray(start, float)
         if q0.shape != (m, N + 1, nx):
             raise ValueError('get_relaxation: start has shape %r, the call needs %r' % (q0.shape, (m, N + 1, nx)))
-        if getattr(self, '_mode_solver', None) is None:
-            self._mode_solver = _modes.ModeSolver(o['device'])
-        raw = self._mode_solver.solve(self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], q0, subspace=m,
-                                      iterations=iterations, lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'],
-                                      stern_capacitance=o['stern_capacitance'], velocity=o['velocity'], reactions=o['reactions'], wall=wall,
-                                      fields=['ritz', 'gram'] + (['basis'] if profiles else []), max_waves=max_waves)
+        raw = self._satellite('_mode_solver').solve(
+            self.device_view(), o['D'], o['charges'], o['x'], o['beta'], o['eps'], o['dx'], o['phiM'], q0, subspace=m, iterations=iterations,
+            lanes=idx, mpb_radius=o['mpb_radius'], wall_bc=o['wall_bc'], stern_capacitance=o['stern_capacitance'], velocity=o['velocity'],
+            reactions=o['reactions'], wall=wall, fields=['ritz', 'gram'] + (['basis'] if profiles else []), max_waves=max_waves)
         n, k = len(idx), min(int(nmodes), m)
         rates, res = np.full((n, k), np.nan + 0j), np.full((n, k), np.nan)
         stable = np.full(n, None, dtype=object)

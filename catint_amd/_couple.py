@@ -3,36 +3,26 @@ transport per operating point -- the transport tangent d(surface state) / d(wall
 the damped step -- formed on the device (``catint_amd/lib/libcatint_couple.so``, built by ``catint_amd.build.build_couple_library()``).
 No fallback: a missing library raises."""
 import ctypes as C
-import os
-
-import numpy as np
 
 from . import _devlib
-from ._capi import flatten_reactions as reaction_table      # the arrays of pnp_set_reactions: catcpl_params takes the same form
-from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
+from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _PD, _PI, _PL, _dptr, _f64, _iptr  # noqa: F401  (part of this module's interface)
+from ._medium import WALL, Medium, reaction_table  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_COUPLE_LIB') or os.path.join(_HERE, 'lib', 'libcatint_couple.so')
+LIB_PATH = _devlib.lib_path('couple')
 
 # every symbol include/catint_couple.h declares (tests/test_couple_abi.py)
 SYMBOLS = _devlib.symbols('catcpl_', 'solve')
 
 MAX_SPECIES, MAX_NX = 8, 4098
 PIVOT_GROWTH_LIMIT, SINGULAR = 1e8, 1e-12
-WALL = {'dirichlet': 0, 'stern': 1}
 OK, PIVOT, UNSOLVED, SINGULAR_A = 0, 1, 2, 3
 # output rows: name -> shape of one operating point from N
 FIELDS = {'T_c': lambda N: (N, N), 'T_phi': lambda N: (N,), 'dflux': lambda N: (N,), 'lambda': lambda N: (), 'flux_new': lambda N: (N,),
           'dc_surface': lambda N: (N,), 'dphi_surface': lambda N: ()}
 
 
-class CoupleError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_couple error %d: %s' % (code, msg))
-        self.code = code
-
-
-_PD, _PI, _PL = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+class CoupleError(_devlib.LibraryError):
+    library = 'catint_couple'
 
 
 class CatcplParams(C.Structure):
@@ -48,22 +38,7 @@ class CatcplOutputs(C.Structure):
                 ('flux_new', _PD), ('dc_surface', _PD), ('dphi_surface', _PD), ('status', _PI)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catcpl_', 'solve', CatcplParams, CatcplOutputs, CoupleError)
-    return _lib
-
-
-def _iptr(a):
-    return a.ctypes.data_as(_PI) if a is not None else None
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+load_library = _devlib.loader(globals(), 'catcpl_', 'solve', CatcplParams, CatcplOutputs, CoupleError)
 
 
 class Coupler(_devlib.Handle):
@@ -77,31 +52,19 @@ class Coupler(_devlib.Handle):
         allowed); flux, K, Kphi [n][N] and Kc [n][N][N] are indexed by the position in the call, n = len(lanes) (None: the number of
         rows of flux); reactions: [(lhs indices, rhs indices, kf, kr)].  fields: names out of FIELDS (None: all).  Returns a dict of
         float64 arrays [n]... and 'status' [n] (int32).  out: arrays to write into instead of fresh ones (tests)."""
-        N = max(int(view.nspecies), 0)
-        names = list(FIELDS) if fields is None else list(fields)
-        for nm in names:
-            if nm not in FIELDS:
-                raise ValueError('unknown field %r (known: %s)' % (nm, ', '.join(FIELDS)))
-        R, n_lhs, lhs, n_rhs, rhs, kf, kr = reaction_table(list(reactions))
-        keep = [_f64(a) for a in (D, charges, x, mpb_radius)]
-        idx = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        names = _devlib.field_names(fields, FIELDS)
+        medium = Medium(view, D, charges, x, beta, mpb_radius, velocity, reactions, eps=eps, dx=dx, wall_bc=wall_bc,
+                        stern_capacitance=stern_capacitance, max_waves=max_waves, lanes=lanes)
+        N = medium.dims[1]
         g, k, kc, kp = (_f64(a) for a in (flux, K, Kc, Kphi))
-        n = len(idx) if idx is not None else (0 if g is None else g.size // max(N, 1))
-        for name, a, size in (('flux', g, n * N), ('K', k, n * N), ('Kc', kc, n * N * N), ('Kphi', kp, n * N), ('mpb_radius', keep[3], N)):
-            if a is not None and a.size != size:
-                raise ValueError('%s has %d values, the call needs %d' % (name, a.size, size))
-        if keep[0].size < N or keep[1].size < N or keep[2].size < max(int(view.nx), 0):
-            raise ValueError('D, charges or x shorter than the view')
-        p = CatcplParams(C.sizeof(CatcplParams) if struct_size is None else int(struct_size), int(max_waves),
-                         wall_bc if isinstance(wall_bc, int) else WALL[wall_bc], R, n, None if idx is None else idx.ctypes.data_as(_PL),
-                         _dptr(keep[0]), _dptr(keep[1]), _dptr(keep[3]), _dptr(keep[2]), float(beta), float(eps), float(dx), float(velocity),
-                         float(stern_capacitance), _iptr(n_lhs), _iptr(lhs), _iptr(n_rhs), _iptr(rhs), _dptr(kf), _dptr(kr), float(rf),
-                         float(dphi_max), _dptr(g), _dptr(k), _dptr(kc), _dptr(kp))
-        res = {} if out is None else out
-        for name in names:
-            res.setdefault(name, np.empty((n,) + FIELDS[name](N)))
-        res.setdefault('status', np.zeros(n, np.int32))
-        o = CatcplOutputs(struct_size=C.sizeof(CatcplOutputs) if out_struct_size is None else int(out_struct_size),
-                          status=_iptr(res['status']), **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
+        if medium.idx is None:
+            medium.rows(0 if g is None else g.size // max(N, 1))
+        n = medium.n
+        medium.check('the call needs', [('flux', g, n * N), ('K', k, n * N), ('Kc', kc, n * N * N), ('Kphi', kp, n * N)])
+        p = CatcplParams(struct_size=_devlib.size_of(CatcplParams, struct_size), rf=float(rf), dphi_max=float(dphi_max), flux=_dptr(g),
+                         K=_dptr(k), Kc=_dptr(kc), Kphi=_dptr(kp), **medium.members)
+        res = _devlib.results(out, {name: FIELDS[name](N) for name in names}, (n,), status=n)
+        o = CatcplOutputs(struct_size=_devlib.size_of(CatcplOutputs, out_struct_size), status=_iptr(res['status']),
+                          **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
         self._call('solve', view, p, o)
         return res

@@ -1,10 +1,14 @@
-"""What the ctypes bindings of the libraries that read a ``pnp_device_view`` (``_observe.py``, ``_balance.py``, ``_regrid.py``) share: the view's mirror,
-loading a library with its five lifecycle symbols and its entry point, and the handle class."""
+"""What the ctypes bindings of the satellite libraries (every ``_*.py`` of this package beside ``_capi.py``) share: the mirror of
+``pnp_device_view``, the pointer types and array helpers, a library's error class and its cached loader with the five lifecycle symbols
+and the entry point, the handle class, and the two steps every ``solve`` takes around its call: the check of the requested field names
+and the allocation of the result arrays."""
 import ctypes as C
 import os
 
+import numpy as np
+
 EINVAL, ENOMEM, EDEVICE = -1, -2, -3
-_PD = C.POINTER(C.c_double)
+_PD, _PI, _PL = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 
 
 class PnpDeviceView(C.Structure):
@@ -17,9 +21,73 @@ def _dptr(a):
     return a.ctypes.data_as(_PD) if a is not None else None
 
 
+def _iptr(a):
+    return a.ctypes.data_as(_PI) if a is not None else None
+
+
+def _lptr(a):
+    return a.ctypes.data_as(_PL) if a is not None else None
+
+
+_cptr = _dptr          # a complex128 array as the (re, im) pairs of doubles the libraries write
+
+
+def _f64(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+
+def lane_list(lanes):
+    """lanes as the contiguous int64 list the libraries take, None as it is"""
+    return None if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+
+
+def size_of(struct, given):
+    """struct_size of a call: that of the mirror unless a test gives another"""
+    return C.sizeof(struct) if given is None else int(given)
+
+
+def field_names(fields, known, default=None):
+    """the requested names as a list (None: `default`, or all of `known`), every one checked against `known`"""
+    names = list(known if default is None else default) if fields is None else list(fields)
+    for name in names:
+        if name not in known:
+            raise ValueError('unknown field %r (known: %s)' % (name, ', '.join(known)))
+    return names
+
+
+def results(out, shapes, lead, dtype=np.float64, status=None):
+    """the dict a solve returns: `out` or a new one, with an array [lead..][shapes[name]..] of `dtype` for every name of `shapes` that
+    has none and, with status = its shape, the int32 'status' row"""
+    res = {} if out is None else out
+    for name, shape in shapes.items():
+        res.setdefault(name, np.empty(tuple(lead) + tuple(shape), dtype))
+    if status is not None:
+        res.setdefault('status', np.zeros(status, np.int32))
+    return res
+
+
+def lib_path(name):
+    """Where libcatint_<name>.so is looked for: CATINT_<NAME>_LIB (diagnosis builds of tools/probe) or this package's lib/"""
+    return os.environ.get('CATINT_%s_LIB' % name.upper()) or os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib',
+                                                                           'libcatint_%s.so' % name)
+
+
 def symbols(prefix, entry):
     """Every symbol the library's header declares"""
     return [prefix + n for n in ('create', 'destroy', 'last_error', 'last_kernel', 'last_kernel_ms', entry)]
+
+
+class LibraryError(RuntimeError):
+    """A library's error: a binding module derives its own and names the library ('catint_response')"""
+    library = None
+
+    def __init__(self, code, msg):
+        super().__init__('%s error %d: %s' % (self.library, code, msg))
+        self.code = code
 
 
 def load(path, prefix, entry, params, outputs, error):
@@ -35,6 +103,22 @@ def load(path, prefix, entry, params, outputs, error):
         f = getattr(lib, prefix + name)
         f.argtypes, f.restype = argtypes, restype
     return lib
+
+
+def loader(ns, prefix, entry, params, outputs, error, more=()):
+    """The load_library of a binding module, ns = its globals(): `load` of the module's LIB_PATH (as it stands at the first call) once,
+    kept in the module's `_lib`.  more: further entry points with the signature of `entry` (cateis_solve)."""
+    ns.setdefault('_lib', None)
+
+    def load_library():
+        if ns['_lib'] is None:
+            lib = load(ns['LIB_PATH'], prefix, entry, params, outputs, error)
+            for name in more:
+                f = getattr(lib, prefix + name)
+                f.argtypes, f.restype = getattr(lib, prefix + entry).argtypes, C.c_int
+            ns['_lib'] = lib
+        return ns['_lib']
+    return load_library
 
 
 class Handle(object):

@@ -2,7 +2,6 @@
 derivatives of the wall fluxes with respect to every rate constant, transition state and adsorbate energy, computed on the device
 (``catint_amd/lib/libcatint_drc.so``, built by ``catint_amd.build.build_drc_library()``).  No fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -10,8 +9,7 @@ from . import _devlib, _microkin
 from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
 from ._microkin import DROP, MAX_ADSORBATES, MAX_ORDER, MAX_SITES, MAX_SPECIES, MAX_STEPS, MIN_LOG, _PD, _PI, _PL, _iptr  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_DRC_LIB') or os.path.join(_HERE, 'lib', 'libcatint_drc.so')
+LIB_PATH = _devlib.lib_path('drc')
 
 # every symbol include/catint_drc.h declares (tests/test_drc_abi.py)
 SYMBOLS = _devlib.symbols('catdrc_', 'solve')
@@ -25,10 +23,8 @@ FIELDS = {'dflux_dlnkf': lambda N, S, R: (R, N), 'dflux_dlnkb': lambda N, S, R: 
 DEFAULT_FIELDS = ('drc', 'tdrc', 'dflux_drc', 'dflux_dG', 'flux', 'flux_scale')
 
 
-class DrcError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_drc error %d: %s' % (code, msg))
-        self.code = code
+class DrcError(_devlib.LibraryError):
+    library = 'catint_drc'
 
 
 class CatdrcParams(C.Structure):
@@ -45,14 +41,7 @@ class CatdrcOutputs(C.Structure):
                 ('status', _PI)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catdrc_', 'solve', CatdrcParams, CatdrcOutputs, DrcError)
-    return _lib
+load_library = _devlib.loader(globals(), 'catdrc_', 'solve', CatdrcParams, CatdrcOutputs, DrcError)
 
 
 class RateControl(_devlib.Handle):
@@ -72,12 +61,12 @@ class RateControl(_devlib.Handle):
         touch): their number of digits is what flux / flux_scale leaves of 16.  out: arrays to write into (tests)."""
         per_point = {'sigma': sigma, 'off': off, 'gamma': gamma, 'theta': theta, 'csurf': csurf, 'phi_surface': phi_surface}
         call = _microkin.Call(tables, phiM, lanes, per_point, fields, FIELDS, DEFAULT_FIELDS, potential_drop, stern_capacitance, phi_pzc, max_waves)
-        p = CatdrcParams(struct_size=C.sizeof(CatdrcParams) if struct_size is None else int(struct_size), residual_tol=float(residual_tol),
+        p = CatdrcParams(struct_size=_devlib.size_of(CatdrcParams, struct_size), residual_tol=float(residual_tol),
                          **call.members)
         res = call.results(FIELDS, out)
         res.setdefault('status', np.zeros(call.n, np.int32))
         res.setdefault('residual', np.zeros(call.n))
-        o = CatdrcOutputs(struct_size=C.sizeof(CatdrcOutputs) if out_struct_size is None else int(out_struct_size),
+        o = CatdrcOutputs(struct_size=_devlib.size_of(CatdrcOutputs, out_struct_size),
                           status=_iptr(res['status']), residual=_dptr(res['residual']),
                           **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
         self._call('solve', view, p, o)

@@ -2,24 +2,22 @@
 with adsorbate storage, the transport transfer functions at the same frequency and the Stern layer, closed at the wall -- formed on the
 device (``catint_amd/lib/libcatint_eis.so``, built by ``catint_amd.build.build_eis_library()``).  No fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _devlib, _microkin
-from ._capi import flatten_reactions as reaction_table      # the arrays of pnp_set_reactions: cateis_params takes the same form
 from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
-from ._microkin import DROP, _PD, _PI, _PL, _f64, _iptr  # noqa: F401  (the same)
+from ._devlib import _PD, _PI, _PL, _f64, _iptr  # noqa: F401  (the same)
+from ._medium import WALL, Medium, reaction_table  # noqa: F401  (the same)
+from ._microkin import DROP  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_EIS_LIB') or os.path.join(_HERE, 'lib', 'libcatint_eis.so')
+LIB_PATH = _devlib.lib_path('eis')
 
 # every symbol include/catint_eis.h declares (tests/test_eis_abi.py)
 SYMBOLS = _devlib.symbols('cateis_', 'kinetic') + ['cateis_solve']
 
 MAX_FREQ, MAX_NX = 256, 4098
 PIVOT_GROWTH_LIMIT, SINGULAR = 1e8, 1e-12
-WALL = {'dirichlet': 0, 'stern': 1}
 OK, PIVOT, INPUT, SINGULAR_A, RESIDUAL = 0, 1, 2, 3, 4
 # output rows: name -> (shape of one (point, frequency) pair from (N, S), complex?); 'residual' is per point
 KINETIC_FIELDS = {'Kc': lambda N, S: (N, N), 'Kphi': lambda N, S: (N, 2), 'dy': lambda N, S: (S + 1, N + 2)}
@@ -32,10 +30,8 @@ DEFAULT_KINETIC_FIELDS = ('Kc', 'Kphi', 'residual')
 DEFAULT_FIELDS = ('admittance', 'faradaic', 'double_layer', 'dflux', 'dc_surface', 'dphi_surface', 'dsigma', 'residual')
 
 
-class EisError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_eis error %d: %s' % (code, msg))
-        self.code = code
+class EisError(_devlib.LibraryError):
+    library = 'catint_eis'
 
 
 class CateisParams(C.Structure):
@@ -56,16 +52,7 @@ class CateisOutputs(C.Structure):
                 ('dphi_surface', _PD), ('dsigma', _PD), ('Tc', _PD), ('Tphi', _PD), ('tc', _PD), ('tphi', _PD)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'cateis_', 'kinetic', CateisParams, CateisOutputs, EisError)
-        f = _lib.cateis_solve
-        f.argtypes, f.restype = _lib.cateis_kinetic.argtypes, C.c_int
-    return _lib
+load_library = _devlib.loader(globals(), 'cateis_', 'kinetic', CateisParams, CateisOutputs, EisError, more=('solve',))
 
 
 class Impedance(_devlib.Handle):
@@ -81,10 +68,8 @@ class Impedance(_devlib.Handle):
         pp['theta'] = theta
         call = _microkin.Call(tables, phiM, lanes, pp, fields, shapes, default, potential_drop, stern_capacitance, phi_pzc, max_waves)
         N, S, _ = (max(v, 0) for v in call.dims)
-        p = CateisParams(struct_size=C.sizeof(CateisParams) if struct_size is None else int(struct_size), nfreq=F, omega=_dptr(om),
-                         residual_tol=float(residual_tol), **call.members)
-        for k, v in extra.items():
-            setattr(p, k, v)
+        p = CateisParams(struct_size=_devlib.size_of(CateisParams, struct_size), nfreq=F, omega=_dptr(om), residual_tol=float(residual_tol),
+                         **call.members, **extra)
         res = {} if out is None else out
         for name in call.names:
             if name == 'residual':
@@ -92,7 +77,7 @@ class Impedance(_devlib.Handle):
             else:
                 res.setdefault(name, np.empty((call.n, F) + FIELDS[name](N, S), np.complex128))
         res.setdefault('status', np.zeros((call.n, F), np.int32))
-        o = CateisOutputs(struct_size=C.sizeof(CateisOutputs) if out_struct_size is None else int(out_struct_size), status=_iptr(res['status']))
+        o = CateisOutputs(struct_size=_devlib.size_of(CateisOutputs, out_struct_size), status=_iptr(res['status']))
         for name, a in res.items():
             if name in FIELDS:
                 setattr(o, name, C.cast(a.ctypes.data, _PD))
@@ -120,15 +105,8 @@ class Impedance(_devlib.Handle):
         roughness factor (0: the blocking electrode).  fields: names out of FIELDS (None: DEFAULT_FIELDS).  Returns complex128 arrays
         [n][F]..., 'residual' [n] and 'status' [n][F] (0; 1 failed pivot check in the transport elimination; 2 unsolved lane or
         non-finite input, NaN; 3 singular A(omega); 4 the coverages are not stationary)."""
-        N = max(int(view.nspecies), 0)
-        R, n_lhs, lhs, n_rhs, rhs, kf, kr = reaction_table(list(reactions))
-        keep = [_f64(a) for a in (D, charges, x, mpb_radius)]
-        if keep[3] is not None and keep[3].size != N:
-            raise ValueError('mpb_radius has %d values, the call needs %d' % (keep[3].size, N))
-        if keep[0].size < N or keep[1].size < N or keep[2].size < max(int(view.nx), 0):
-            raise ValueError('D, charges or x shorter than the view')
-        extra = dict(wall_bc=wall_bc if isinstance(wall_bc, int) else WALL[wall_bc], nreactions=R, D=_dptr(keep[0]), charges=_dptr(keep[1]),
-                     mpb_radius=_dptr(keep[3]), x=_dptr(keep[2]), beta=float(beta), eps=float(eps), dx=float(dx), velocity=float(velocity),
-                     n_lhs=_iptr(n_lhs), lhs=_iptr(lhs), n_rhs=_iptr(n_rhs), rhs=_iptr(rhs), kf=_dptr(kf), kr=_dptr(kr), rf=float(rf))
+        medium = Medium(view, D, charges, x, beta, mpb_radius, velocity, reactions, eps=eps, dx=dx, wall_bc=wall_bc)
+        medium.check('the call needs')
+        extra = dict(medium.members, rf=float(rf))
         return self._run('solve', FIELDS, DEFAULT_FIELDS, view, tables, phiM, theta, omega, lanes, {'sigma': sigma, 'off': off, 'gamma': gamma},
                          fields, potential_drop, stern_capacitance, phi_pzc, residual_tol, max_waves, extra, struct_size, out_struct_size, out)

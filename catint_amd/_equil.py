@@ -2,30 +2,23 @@
 Poisson-Boltzmann problem (``catint_amd/lib/libcatint_equil.so``, built by ``catint_amd.build.build_equil_library()``).
 No fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _devlib
-from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
+from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _PD, _PI, _PL, _dptr, _f64, _iptr  # noqa: F401  (part of this module's interface)
+from ._medium import WALL  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_EQUIL_LIB') or os.path.join(_HERE, 'lib', 'libcatint_equil.so')
+LIB_PATH = _devlib.lib_path('equil')
 
 # every symbol include/catint_equil.h declares (tests/test_equil_abi.py)
 SYMBOLS = _devlib.symbols('cateq_', 'solve')
 
 MAX_SPECIES, MAX_NX, MAX_EXPONENT, MAX_ITERATIONS = 8, 4098, 500.0, 1000
-WALL = {'dirichlet': 0, 'stern': 1}
 
 
-class EquilError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_equil error %d: %s' % (code, msg))
-        self.code = code
-
-
-_PD, _PI = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+class EquilError(_devlib.LibraryError):
+    library = 'catint_equil'
 
 
 class CateqParams(C.Structure):
@@ -40,18 +33,7 @@ class CateqOutputs(C.Structure):
                 ('phi_dev', C.POINTER(C.c_void_p))]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'cateq_', 'solve', CateqParams, CateqOutputs, EquilError)
-    return _lib
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+load_library = _devlib.loader(globals(), 'cateq_', 'solve', CateqParams, CateqOutputs, EquilError)
 
 
 class Equilibrator(_devlib.Handle):
@@ -74,9 +56,11 @@ class Equilibrator(_devlib.Handle):
         n = len(pm)
         pbk = np.ascontiguousarray(np.broadcast_to(_f64(phi_bulk), (n,)))
         cb = np.ascontiguousarray(np.broadcast_to(_f64(c_bulk), (n, N)))
-        p = CateqParams(C.sizeof(CateqParams) if struct_size is None else int(struct_size), int(max_waves), _dptr(keep[0]), _dptr(keep[2]),
-                        _dptr(keep[1]), float(beta), float(eps), float(dx), wall_bc if isinstance(wall_bc, int) else WALL[wall_bc],
-                        int(maxit), float(stern_capacitance), float(phi_pzc), float(tol), _dptr(pm), _dptr(pbk), _dptr(cb), n)
+        p = CateqParams(struct_size=_devlib.size_of(CateqParams, struct_size), max_waves=int(max_waves), charges=_dptr(keep[0]),
+                        mpb_radius=_dptr(keep[2]), x=_dptr(keep[1]), beta=float(beta), eps=float(eps), dx=float(dx),
+                        wall_bc=wall_bc if isinstance(wall_bc, int) else WALL[wall_bc], maxit=int(maxit),
+                        stern_capacitance=float(stern_capacitance), phi_pzc=float(phi_pzc), tol=float(tol), phiM=_dptr(pm), phi_bulk=_dptr(pbk),
+                        c_bulk=_dptr(cb), nlanes=n)
         out = {'status': np.zeros(n, np.int32), 'iterations': np.zeros(n, np.int32)}
         if to_host:
             out['c'], out['phi'] = np.empty((n, N, nx)), np.empty((n, nx))

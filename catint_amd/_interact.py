@@ -3,7 +3,6 @@ site types per operating point, the interaction strength ramped in stages inside
 solved on the device (``catint_amd/lib/libcatint_interact.so``, built by ``catint_amd.build.build_interact_library()``).  No fallback: a
 missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -11,8 +10,7 @@ from . import _devlib, _microkin
 from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
 from ._microkin import DROP, MAX_ORDER, MAX_SITES, MAX_SPECIES, MAX_STEPS, MIN_LOG, _PD, _PI, _PL, _f64, _i32, _iptr  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_INTERACT_LIB') or os.path.join(_HERE, 'lib', 'libcatint_interact.so')
+LIB_PATH = _devlib.lib_path('interact')
 
 # every symbol include/catint_interact.h declares (tests/test_interact_abi.py)
 SYMBOLS = _devlib.symbols('catia_', 'solve')
@@ -30,10 +28,8 @@ DEFAULT_FIELDS = ('theta', 'rate', 'rate_gross', 'flux', 'flux_scale', 'energy_s
 FLAGS = ('status', 'iterations', 'ramp_reached')
 
 
-class InteractError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_interact error %d: %s' % (code, msg))
-        self.code = code
+class InteractError(_devlib.LibraryError):
+    library = 'catint_interact'
 
 
 class CatiaParams(C.Structure):
@@ -52,14 +48,7 @@ class CatiaOutputs(C.Structure):
                 ('ramp_reached', _PI)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catia_', 'solve', CatiaParams, CatiaOutputs, InteractError)
-    return _lib
+load_library = _devlib.loader(globals(), 'catia_', 'solve', CatiaParams, CatiaOutputs, InteractError)
 
 
 class InteractingKinetics(_devlib.Handle):
@@ -94,14 +83,14 @@ class InteractingKinetics(_devlib.Handle):
         cutoff = _f64(np.broadcast_to(np.asarray(tables['cutoff'], float), (G,))) if tables.get('cutoff') is not None else None
         smoothing = _f64(np.broadcast_to(np.asarray(tables['smoothing'], float), (G,))) if tables.get('smoothing') is not None else None
         members = dict(call.members, nadsorbates=S)
-        p = CatiaParams(struct_size=C.sizeof(CatiaParams) if struct_size is None else int(struct_size), maxit=int(maxit), tol=float(tol),
+        p = CatiaParams(struct_size=_devlib.size_of(CatiaParams, struct_size), maxit=int(maxit), tol=float(tol),
                         nsitetypes=G, response=response if isinstance(response, int) else RESPONSE[response], ramp=int(ramp),
                         site_of=_iptr(site_of), site_fraction=_dptr(frac), eps=_dptr(eps), eps_ts=_dptr(eps_ts), cutoff=_dptr(cutoff),
                         smoothing=_dptr(smoothing), strength=float(tables.get('strength', 1.0) if strength is None else strength), **members)
         res = call.results(known, out)
         for k in FLAGS:
             res.setdefault(k, np.zeros(call.n, np.int32))
-        o = CatiaOutputs(struct_size=C.sizeof(CatiaOutputs) if out_struct_size is None else int(out_struct_size),
+        o = CatiaOutputs(struct_size=_devlib.size_of(CatiaOutputs, out_struct_size),
                          **dict({k: _iptr(res[k]) for k in FLAGS}, **{name: _dptr(a) for name, a in res.items() if name in FIELDS}))
         self._call('solve', view, p, o)
         return res

@@ -2,7 +2,6 @@
 its wall fluxes and their sensitivities, solved on the device (``catint_amd/lib/libcatint_kinetics.so``, built by
 ``catint_amd.build.build_kinetics_library()``).  No fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -10,8 +9,7 @@ from . import _devlib, _microkin
 from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
 from ._microkin import DROP, MAX_ADSORBATES, MAX_ORDER, MAX_SITES, MAX_SPECIES, MAX_STEPS, MIN_LOG, _PD, _PI, _PL, _iptr  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_KINETICS_LIB') or os.path.join(_HERE, 'lib', 'libcatint_kinetics.so')
+LIB_PATH = _devlib.lib_path('kinetics')
 
 # every symbol include/catint_kinetics.h declares (tests/test_kinetics_abi.py)
 SYMBOLS = _devlib.symbols('catkin_', 'solve')
@@ -24,10 +22,8 @@ FIELDS = {'theta': lambda N, S, R: (S + 1,), 'rate': lambda N, S, R: (R,), 'rate
 DEFAULT_FIELDS = ('theta', 'rate', 'rate_gross', 'flux', 'flux_scale')
 
 
-class KineticsError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_kinetics error %d: %s' % (code, msg))
-        self.code = code
+class KineticsError(_devlib.LibraryError):
+    library = 'catint_kinetics'
 
 
 class CatkinParams(C.Structure):
@@ -44,14 +40,7 @@ class CatkinOutputs(C.Structure):
                 ('flux_scale', _PD), ('dflux_dc', _PD), ('dflux_dphi', _PD), ('status', _PI), ('iterations', _PI)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catkin_', 'solve', CatkinParams, CatkinOutputs, KineticsError)
-    return _lib
+load_library = _devlib.loader(globals(), 'catkin_', 'solve', CatkinParams, CatkinOutputs, KineticsError)
 
 
 class KineticsSolver(_devlib.Handle):
@@ -70,12 +59,12 @@ class KineticsSolver(_devlib.Handle):
         (int32).  The number of digits of 'flux' is what flux / flux_scale leaves of 16.  out: arrays to write into (tests)."""
         per_point = {'sigma': sigma, 'off': off, 'gamma': gamma, 'theta_guess': theta_guess, 'csurf': csurf, 'phi_surface': phi_surface}
         call = _microkin.Call(tables, phiM, lanes, per_point, fields, FIELDS, DEFAULT_FIELDS, potential_drop, stern_capacitance, phi_pzc, max_waves)
-        p = CatkinParams(struct_size=C.sizeof(CatkinParams) if struct_size is None else int(struct_size), maxit=int(maxit), tol=float(tol),
+        p = CatkinParams(struct_size=_devlib.size_of(CatkinParams, struct_size), maxit=int(maxit), tol=float(tol),
                          **call.members)
         res = call.results(FIELDS, out)
         res.setdefault('status', np.zeros(call.n, np.int32))
         res.setdefault('iterations', np.zeros(call.n, np.int32))
-        o = CatkinOutputs(struct_size=C.sizeof(CatkinOutputs) if out_struct_size is None else int(out_struct_size),
+        o = CatkinOutputs(struct_size=_devlib.size_of(CatkinOutputs, out_struct_size),
                           status=_iptr(res['status']), iterations=_iptr(res['iterations']),
                           **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
         self._call('solve', view, p, o)

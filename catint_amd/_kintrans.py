@@ -3,7 +3,6 @@ implicit Euler with step doubling, every point with its own step size -- integra
 (``catint_amd/lib/libcatint_kintrans.so``, built by ``catint_amd.build.build_kintrans_library()``), and the rescue of steady-state solves
 that rests on it.  No fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -11,8 +10,7 @@ from . import _devlib, _microkin
 from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
 from ._microkin import DROP, _PD, _PI, _PL, _f64, _iptr  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_KINTRANS_LIB') or os.path.join(_HERE, 'lib', 'libcatint_kintrans.so')
+LIB_PATH = _devlib.lib_path('kintrans')
 
 # every symbol include/catint_kintrans.h declares (tests/test_kintrans_abi.py)
 SYMBOLS = _devlib.symbols('catkt_', 'solve')
@@ -28,10 +26,8 @@ DEFAULT_FIELDS = ('theta', 'flux', 'flux_scale', 'drift', 't_reached')
 RESCUE_T_OUT, RESCUE_RTOL, RESCUE_STEADY_TOL = 1e12, 1e-2, 1e-6
 
 
-class KintransError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_kintrans error %d: %s' % (code, msg))
-        self.code = code
+class KintransError(_devlib.LibraryError):
+    library = 'catint_kintrans'
 
 
 class CatktParams(C.Structure):
@@ -49,14 +45,7 @@ class CatktOutputs(C.Structure):
                 ('t_reached', _PD), ('status', _PI), ('steps', _PI)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catkt_', 'solve', CatktParams, CatktOutputs, KintransError)
-    return _lib
+load_library = _devlib.loader(globals(), 'catkt_', 'solve', CatktParams, CatktOutputs, KintransError)
 
 
 class TransientKinetics(_devlib.Handle):
@@ -81,13 +70,13 @@ class TransientKinetics(_devlib.Handle):
         known = {name: (lambda N, S, R, f=f: f(N, S, R, K)) for name, f in FIELDS.items()}
         per_point = {'sigma': sigma, 'off': off, 'gamma': gamma, 'theta0': theta0, 'csurf': csurf, 'phi_surface': phi_surface}
         call = _microkin.Call(tables, phiM, lanes, per_point, fields, known, DEFAULT_FIELDS, potential_drop, stern_capacitance, phi_pzc, max_waves)
-        p = CatktParams(struct_size=C.sizeof(CatktParams) if struct_size is None else int(struct_size), newton_maxit=int(newton_maxit),
+        p = CatktParams(struct_size=_devlib.size_of(CatktParams, struct_size), newton_maxit=int(newton_maxit),
                         max_steps=int(max_steps), t_out=_dptr(tt), n_out=K, rtol=float(rtol), atol=float(atol), newton_tol=float(newton_tol),
                         steady_tol=float(steady_tol), h0=float(h0), **call.members)
         res = call.results(known, out)
         res.setdefault('status', np.zeros(call.n, np.int32))
         res.setdefault('steps', np.zeros((call.n, 3), np.int32))
-        o = CatktOutputs(struct_size=C.sizeof(CatktOutputs) if out_struct_size is None else int(out_struct_size),
+        o = CatktOutputs(struct_size=_devlib.size_of(CatktOutputs, out_struct_size),
                          status=_iptr(res['status']), steps=_iptr(res['steps']), **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
         self._call('solve', view, p, o)
         return res

@@ -1,32 +1,18 @@
-"""What the ctypes bindings of the two libraries that work on a mean-field microkinetic model (``_kinetics.py``, ``_drc.py``) share: the
-limits of ``include/catint_kinetics.h`` (``include/catint_drc.h`` repeats them), the pointer and array helpers, and the marshalling of
-the tables and the per-point arrays of a call into the members the two parameter structs have in common."""
-import ctypes as C
-
+"""What the ctypes bindings of the libraries that work on a surface microkinetic model (``_kinetics.py``, ``_drc.py``, ``_kintrans.py``,
+``_eis.py``, ``_interact.py``, ``_scfkin.py``) share: the limits of ``include/catint_kinetics.h`` (the other headers repeat them) and
+``Call``, the marshalling of the tables and the per-point arrays of a call into the members the parameter structs have in common.  The
+libraries that take the medium have the counterpart in ``_medium.py``."""
 import numpy as np
 
-from ._devlib import _dptr
+from ._devlib import _PD, _PI, _PL, _dptr, _f64, _i32, _iptr, _lptr, field_names, lane_list, results  # noqa: F401  (_kinetics.py .. import them here)
 
 MAX_SPECIES, MAX_ADSORBATES, MAX_STEPS, MAX_ORDER, MAX_SITES = 8, 8, 16, 3, 3
 MIN_LOG = -700.0
 DROP = {'full': 0, 'stern': 1}
 
-_PD, _PI, _PL = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 # values per operating point from (N, T, R)
 _PER_POINT = {'sigma': lambda N, T, R: 1, 'off': lambda N, T, R: R * 2, 'gamma': lambda N, T, R: max(N, 0), 'theta_guess': lambda N, T, R: T,
               'theta': lambda N, T, R: T, 'theta0': lambda N, T, R: T, 'csurf': lambda N, T, R: max(N, 0), 'phi_surface': lambda N, T, R: 1}
-
-
-def _iptr(a):
-    return a.ctypes.data_as(_PI) if a is not None else None
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
 
 
 class Call(object):
@@ -41,13 +27,10 @@ class Call(object):
         S = T - 1
         R = of.shape[0] if of.ndim == 2 else 0
         N = (of.shape[1] - T) if of.ndim == 2 else 0
-        self.names = list(default) if fields is None else list(fields)
-        for nm in self.names:
-            if nm not in known:
-                raise ValueError('unknown field %r (known: %s)' % (nm, ', '.join(known)))
+        self.names = field_names(fields, known, default)
         pm = _f64(np.atleast_1d(np.asarray(phiM, float))).reshape(-1)
         n = len(pm)
-        idx = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        idx = lane_list(lanes)
         if idx is not None and len(idx) != n:
             raise ValueError('lanes has %d entries, phiM %d' % (len(idx), n))
         nu, cref, dG, Ea, lnA = (_f64(tables[k]) for k in ('nu', 'cref', 'dG', 'Ea', 'lnA'))
@@ -64,15 +47,12 @@ class Call(object):
         self.arrays = [site_count, of, ob, pm, idx, nu, cref, dG, Ea, lnA] + list(pp.values())
         self.members = dict(max_waves=int(max_waves), nspecies=N, nadsorbates=S, nsteps=R,
                             potential_drop=potential_drop if isinstance(potential_drop, int) else DROP[potential_drop], n=n,
-                            lanes=None if idx is None else idx.ctypes.data_as(_PL), order_f=_iptr(of), order_b=_iptr(ob), nu=_dptr(nu),
+                            lanes=_lptr(idx), order_f=_iptr(of), order_b=_iptr(ob), nu=_dptr(nu),
                             cref=_dptr(cref), site_count=_dptr(site_count), dG=_dptr(dG), Ea=_dptr(Ea), lnA=_dptr(lnA),
                             site_density=float(tables['site_density']), stern_capacitance=float(stern_capacitance), phi_pzc=float(phi_pzc),
                             phiM=_dptr(pm), **{name: _dptr(a) for name, a in pp.items()})
 
     def results(self, known, out):
         """the dict a solve returns: `out` or a new one, with an array of the field's shape for every requested name that has none"""
-        res = {} if out is None else out
         N, S, R = (max(v, 0) for v in self.dims)
-        for name in self.names:
-            res.setdefault(name, np.empty((self.n,) + known[name](N, S, R)))
-        return res
+        return results(out, {name: known[name](N, S, R) for name in self.names}, (self.n,))

@@ -3,35 +3,27 @@ J^-1 S per operating point, all passes in one launch on the device (``catint_amd
 ``catint_amd.build.build_modes_library()``) -- and the small eigenproblem that stays on the host.  No fallback: a missing library
 raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _devlib
-from ._capi import flatten_reactions as reaction_table      # the arrays of pnp_set_reactions: catmodes_params takes the same form
-from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
+from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _PD, _PI, _PL, _dptr, _f64, _iptr  # noqa: F401  (part of this module's interface)
+from ._medium import WALL, Medium, reaction_table  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_MODES_LIB') or os.path.join(_HERE, 'lib', 'libcatint_modes.so')
+LIB_PATH = _devlib.lib_path('modes')
 
 # every symbol include/catint_modes.h declares (tests/test_modes_abi.py)
 SYMBOLS = _devlib.symbols('catmodes_', 'solve')
 
 MAX_SPECIES, MAX_NX, MAX_SUBSPACE, MAX_ITERATIONS = 8, 4098, 8, 64
 PIVOT_GROWTH_LIMIT, BREAKDOWN = 1e8, 1e-10
-WALL = {'dirichlet': 0, 'stern': 1}
 OK, PIVOT, UNSOLVED, BREAKDOWN_STATUS = 0, 1, 2, 3
 # output rows: name -> shape of one operating point from (m, N, nx)
 FIELDS = {'ritz': lambda m, N, nx: (m, m), 'gram': lambda m, N, nx: (m, m), 'basis': lambda m, N, nx: (m, N + 1, nx)}
 
 
-class ModesError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_modes error %d: %s' % (code, msg))
-        self.code = code
-
-
-_PD, _PI, _PL = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+class ModesError(_devlib.LibraryError):
+    library = 'catint_modes'
 
 
 class CatmodesParams(C.Structure):
@@ -48,22 +40,7 @@ class CatmodesOutputs(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('ritz', _PD), ('gram', _PD), ('basis', _PD), ('status', _PI)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catmodes_', 'solve', CatmodesParams, CatmodesOutputs, ModesError)
-    return _lib
-
-
-def _iptr(a):
-    return a.ctypes.data_as(_PI) if a is not None else None
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+load_library = _devlib.loader(globals(), 'catmodes_', 'solve', CatmodesParams, CatmodesOutputs, ModesError)
 
 
 def default_start(m, N, nx, seed=0):
@@ -103,40 +80,19 @@ class ModeSolver(_devlib.Handle):
         wall: None or a dict {'species' [n_wall], 'nu' [n_wall][N], 'k' [B][n_wall], 'alpha' [n_wall] or None, 'saturation' [n_wall] or
         None}.  fields: names out of FIELDS (None: 'ritz' and 'gram').  Returns a dict of float64 arrays [n]... and 'status' [n] (int32).
         out: arrays to write into instead of fresh ones (tests)."""
-        B, N, nx = max(int(view.batch), 0), max(int(view.nspecies), 0), max(int(view.nx), 0)
-        names = ['ritz', 'gram'] if fields is None else list(fields)
-        for nm in names:
-            if nm not in FIELDS:
-                raise ValueError('unknown field %r (known: %s)' % (nm, ', '.join(FIELDS)))
-        q0 = _f64(start)
+        names = _devlib.field_names(fields, FIELDS, ('ritz', 'gram'))
+        q0, pm = _f64(start), _f64(phiM)
         m = int(subspace) if subspace is not None else (0 if q0 is None else int(q0.shape[0]))
-        R, n_lhs, lhs, n_rhs, rhs, kf, kr = reaction_table(list(reactions))
-        W = 0 if not wall else len(wall['species'])
-        wk = [None] * 5
-        if W:
-            wk = [np.ascontiguousarray(wall['species'], dtype=np.int32), _f64(wall['nu']), _f64(wall.get('k')), _f64(wall.get('alpha')),
-                  _f64(wall.get('saturation'))]
-        keep = [_f64(a) for a in (D, charges, x, mpb_radius, phiM)]
-        idx = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        n = len(idx) if idx is not None else B
+        medium = Medium(view, D, charges, x, beta, mpb_radius, velocity, reactions, eps=eps, dx=dx, wall_bc=wall_bc,
+                        stern_capacitance=stern_capacitance, max_waves=max_waves, wall=wall, lanes=lanes)
+        B, N, nx = medium.dims
         ms = min(max(m, 0), MAX_SUBSPACE)
-        for name, a, size in (('start', q0, ms * (N + 1) * nx), ('phiM', keep[4], B), ('wall k', wk[2], B * W), ('wall nu', wk[1], W * N),
-                              ('wall alpha', wk[3], W), ('wall saturation', wk[4], W), ('mpb_radius', keep[3], N)):
-            if a is not None and a.size != size and not (name == 'start' and not 1 <= m <= MAX_SUBSPACE):
-                raise ValueError('%s has %d values, the call needs %d' % (name, a.size, size))
-        if keep[0].size < N or keep[1].size < N or keep[2].size < nx:
-            raise ValueError('D, charges or x shorter than the view')
-        p = CatmodesParams(C.sizeof(CatmodesParams) if struct_size is None else int(struct_size), int(max_waves),
-                           wall_bc if isinstance(wall_bc, int) else WALL[wall_bc], R, W, m, int(iterations), 0, n,
-                           None if idx is None else idx.ctypes.data_as(_PL),
-                           _dptr(keep[0]), _dptr(keep[1]), _dptr(keep[3]), _dptr(keep[2]), float(beta), float(eps), float(dx), float(velocity),
-                           float(stern_capacitance), _iptr(n_lhs), _iptr(lhs), _iptr(n_rhs), _iptr(rhs), _dptr(kf), _dptr(kr),
-                           _iptr(wk[0]), _dptr(wk[1]), _dptr(wk[2]), _dptr(wk[3]), _dptr(wk[4]), _dptr(keep[4]), _dptr(q0))
-        res = {} if out is None else out
-        for name in names:
-            res.setdefault(name, np.empty((n,) + FIELDS[name](ms, N, nx)))
-        res.setdefault('status', np.zeros(n, np.int32))
-        o = CatmodesOutputs(struct_size=C.sizeof(CatmodesOutputs) if out_struct_size is None else int(out_struct_size),
-                            status=_iptr(res['status']), **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
+        # (a subspace outside 1 .. MAX_SUBSPACE is the library's to refuse: `start` has no size to be checked against then)
+        medium.check('the call needs', ([('start', q0, ms * (N + 1) * nx)] if 1 <= m <= MAX_SUBSPACE else []) + [('phiM', pm, B)])
+        p = CatmodesParams(struct_size=_devlib.size_of(CatmodesParams, struct_size), subspace=m, iterations=int(iterations), phiM=_dptr(pm),
+                           start=_dptr(q0), **medium.members)
+        res = _devlib.results(out, {name: FIELDS[name](ms, N, nx) for name in names}, (medium.n,), status=medium.n)
+        o = CatmodesOutputs(struct_size=_devlib.size_of(CatmodesOutputs, out_struct_size), status=_iptr(res['status']),
+                            **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
         self._call('solve', view, p, o)
         return res

@@ -2,15 +2,13 @@
 Scharfetter-Gummel interpolant (``catint_amd/lib/libcatint_regrid.so``, built by ``catint_amd.build.build_regrid_library()``).
 No fallback: a missing library raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _devlib
-from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
+from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _PD, _PI, _PL, _dptr, _f64, _iptr  # noqa: F401  (part of this module's interface)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_REGRID_LIB') or os.path.join(_HERE, 'lib', 'libcatint_regrid.so')
+LIB_PATH = _devlib.lib_path('regrid')
 
 # every symbol include/catint_regrid.h declares (tests/test_regrid_abi.py)
 SYMBOLS = _devlib.symbols('catgrid_', 'resample')
@@ -18,13 +16,8 @@ SYMBOLS = _devlib.symbols('catgrid_', 'resample')
 MAX_SPECIES, MAX_NX, MAX_U = 8, 4098, 500.0
 
 
-class RegridError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_regrid error %d: %s' % (code, msg))
-        self.code = code
-
-
-_PD, _PL = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+class RegridError(_devlib.LibraryError):
+    library = 'catint_regrid'
 
 
 class CatgridParams(C.Structure):
@@ -37,23 +30,12 @@ class CatgridOutputs(C.Structure):
     _fields_ = [('c', _PD), ('phi', _PD), ('c_dev', C.POINTER(C.c_void_p)), ('phi_dev', C.POINTER(C.c_void_p))]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catgrid_', 'resample', CatgridParams, CatgridOutputs, RegridError)
-    return _lib
+load_library = _devlib.loader(globals(), 'catgrid_', 'resample', CatgridParams, CatgridOutputs, RegridError)
 
 
 def row_pitch(nx):
     """Row pitch (doubles) of a handle of nx points, and of the device result of a resample onto such a grid"""
     return (int(nx) + 15) // 16 * 16
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
 
 
 class Regridder(_devlib.Handle):
@@ -74,11 +56,11 @@ class Regridder(_devlib.Handle):
             raise ValueError('D, charges or x shorter than the view')
         if keep[3] is not None and keep[3].size != N:
             raise ValueError('mpb_radius has %d values, the view needs %d' % (keep[3].size, N))
-        idx = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
+        idx = _devlib.lane_list(lanes)
         n = B if idx is None else len(idx)
-        p = CatgridParams(C.sizeof(CatgridParams) if struct_size is None else int(struct_size), int(max_waves), _dptr(keep[0]),
-                          _dptr(keep[1]), _dptr(keep[3]), float(beta), float(velocity), _dptr(keep[2]), nxt, 0, _dptr(xt), n,
-                          None if idx is None else idx.ctypes.data_as(_PL))
+        p = CatgridParams(struct_size=_devlib.size_of(CatgridParams, struct_size), max_waves=int(max_waves), D=_dptr(keep[0]),
+                          charges=_dptr(keep[1]), mpb_radius=_dptr(keep[3]), beta=float(beta), velocity=float(velocity), x=_dptr(keep[2]),
+                          nx_target=nxt, x_target=_dptr(xt), nlanes=n, lanes=_devlib._lptr(idx))
         out = {}
         if to_host:
             out['c'], out['phi'] = np.empty((n, N, nxt)), np.empty((n, nxt))

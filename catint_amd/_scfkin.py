@@ -10,8 +10,7 @@ from . import _devlib, _microkin
 from ._devlib import EDEVICE, EINVAL, ENOMEM, _dptr  # noqa: F401  (part of this module's interface)
 from ._microkin import DROP, MAX_ADSORBATES, MAX_SPECIES, MAX_STEPS, MIN_LOG, _PD, _PI, _iptr  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_SCFKIN_LIB') or os.path.join(_HERE, 'lib', 'libcatint_scfkin.so')
+LIB_PATH = _devlib.lib_path('scfkin')
 
 # every symbol include/catint_scfkin.h declares (tests/test_scfkin_abi.py)
 SYMBOLS = ['catsk_' + n for n in ('create', 'destroy', 'last_error', 'last_kernel', 'begin', 'flux_fn', 'step_host', 'end')]
@@ -25,10 +24,8 @@ FIELDS = {'theta': (lambda N, S: (S + 1,), np.float64), 'flux_scale': (lambda N,
           'calls': (lambda N, S: (), np.int32)}
 
 
-class ScfKineticsError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_scfkin error %d: %s' % (code, msg))
-        self.code = code
+class ScfKineticsError(_devlib.LibraryError):
+    library = 'catint_scfkin'
 
 
 class CatskParams(C.Structure):
@@ -94,7 +91,7 @@ class ScfKinetics(_devlib.Handle):
                               phi_pzc, max_waves)
         members = dict(call.members)
         members.pop('lanes')
-        p = CatskParams(struct_size=C.sizeof(CatskParams) if struct_size is None else int(struct_size), maxit=int(maxit), tol=float(tol),
+        p = CatskParams(struct_size=_devlib.size_of(CatskParams, struct_size), maxit=int(maxit), tol=float(tol),
                         batch=members.pop('n'), **members)
         self._check(self._sym('begin')(self._h, C.byref(p)))
         self.B, self.dims = call.n, call.dims
@@ -113,14 +110,12 @@ class ScfKinetics(_devlib.Handle):
     def end(self, fields=None, out_struct_size=None):
         """catsk_end: a dict of the requested arrays (names out of FIELDS, None: all)"""
         N, S = max(self.dims[0], 0), self.dims[1]
-        names = list(FIELDS) if fields is None else list(fields)
+        names = _devlib.field_names(fields, FIELDS)
         res = {}
         for name in names:
-            if name not in FIELDS:
-                raise ValueError('unknown field %r (known: %s)' % (name, ', '.join(FIELDS)))
             shape, dtype = FIELDS[name]
             res[name] = np.zeros((self.B,) + shape(N, S), dtype)
-        o = CatskOutputs(struct_size=C.sizeof(CatskOutputs) if out_struct_size is None else int(out_struct_size),
+        o = CatskOutputs(struct_size=_devlib.size_of(CatskOutputs, out_struct_size),
                          **{name: (_dptr(a) if a.dtype == np.float64 else _iptr(a)) for name, a in res.items()})
         self._check(self._sym('end')(self._h, C.byref(o)))
         return res

@@ -4,23 +4,20 @@ velocity, next to the electrode potential and the prescribed wall fluxes -- from
 device (``catint_amd/lib/libcatint_sens.so``, built by ``catint_amd.build.build_sens_library()``).  No fallback: a missing library
 raises."""
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _devlib
-from ._capi import flatten_reactions as reaction_table      # the arrays of pnp_set_reactions: catsens_params takes the same form
-from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _dptr  # noqa: F401  (part of this module's interface)
+from ._devlib import EDEVICE, EINVAL, ENOMEM, PnpDeviceView, _PD, _PI, _PL, _dptr, _f64, _iptr  # noqa: F401  (part of this module's interface)
+from ._medium import WALL, Medium, reaction_table  # noqa: F401  (the same)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('CATINT_SENS_LIB') or os.path.join(_HERE, 'lib', 'libcatint_sens.so')
+LIB_PATH = _devlib.lib_path('sens')
 
 # every symbol include/catint_sens.h declares (tests/test_sens_abi.py)
 SYMBOLS = _devlib.symbols('catsens_', 'solve')
 
 MAX_SPECIES, MAX_NX, MAX_PARAMS, CHUNK = 8, 4098, 64, 8
 PIVOT_GROWTH_LIMIT = 1e8
-WALL = {'dirichlet': 0, 'stern': 1}
 OK, PIVOT, UNSOLVED = 0, 1, 2
 # kinds of parameter: name -> CATSENS_* code
 KINDS = {'phiM': 0, 'flux': 1, 'c_bulk': 2, 'D': 3, 'kf': 4, 'kr': 5, 'wall_k': 6, 'stern_capacitance': 7, 'velocity': 8}
@@ -30,13 +27,8 @@ FIELDS = {'dphi_surface': lambda N: (), 'dc_surface': lambda N: (N,), 'dsigma': 
           'dcurrent': lambda N: ()}
 
 
-class SensError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__('catint_sens error %d: %s' % (code, msg))
-        self.code = code
-
-
-_PD, _PI, _PL = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+class SensError(_devlib.LibraryError):
+    library = 'catint_sens'
 
 
 class CatsensParams(C.Structure):
@@ -55,22 +47,7 @@ class CatsensOutputs(C.Structure):
                 ('dwall_flux', _PD), ('dcurrent', _PD), ('status', _PI)]
 
 
-_lib = None
-
-
-def load_library():
-    global _lib
-    if _lib is None:
-        _lib = _devlib.load(LIB_PATH, 'catsens_', 'solve', CatsensParams, CatsensOutputs, SensError)
-    return _lib
-
-
-def _iptr(a):
-    return a.ctypes.data_as(_PI) if a is not None else None
-
-
-def _f64(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+load_library = _devlib.loader(globals(), 'catsens_', 'solve', CatsensParams, CatsensOutputs, SensError)
 
 
 def encode(parameters):
@@ -103,41 +80,22 @@ class Sensitizer(_devlib.Handle):
         flux); phiM [B]; reactions: [(lhs indices, rhs indices, kf, kr)]; wall: None or a dict {'species' [n_wall], 'nu' [n_wall][N],
         'k' [B][n_wall], 'alpha' [n_wall] or None, 'saturation' [n_wall] or None}.  fields: names out of FIELDS (None: all).  Returns a
         dict of float64 arrays [n][P]... and 'status' [n] (int32).  out: arrays to write into instead of fresh ones (tests)."""
-        B, N = max(int(view.batch), 0), max(int(view.nspecies), 0)
-        names = list(FIELDS) if fields is None else list(fields)
-        for nm in names:
-            if nm not in FIELDS:
-                raise ValueError('unknown field %r (known: %s)' % (nm, ', '.join(FIELDS)))
+        names = _devlib.field_names(fields, FIELDS)
         kind, index = encode(parameters)
         P = len(kind) if nparams is None else int(nparams)
-        R, n_lhs, lhs, n_rhs, rhs, kf, kr = reaction_table(list(reactions))
-        W = 0 if not wall else len(wall['species'])
-        wk = [None] * 5
-        if W:
-            wk = [np.ascontiguousarray(wall['species'], dtype=np.int32), _f64(wall['nu']), _f64(wall.get('k')), _f64(wall.get('alpha')),
-                  _f64(wall.get('saturation'))]
-        keep = [_f64(a) for a in (D, charges, x, mpb_radius, phiM)]
-        idx = None if lanes is None else np.ascontiguousarray(lanes, dtype=np.int64).reshape(-1)
-        g = _f64(flux)
-        n = len(idx) if idx is not None else (0 if g is None else g.size // max(N, 1))
-        for name, a, size in (('flux', g, n * N), ('phiM', keep[4], B), ('wall k', wk[2], B * W), ('wall nu', wk[1], W * N),
-                              ('wall alpha', wk[3], W), ('wall saturation', wk[4], W), ('mpb_radius', keep[3], N)):
-            if a is not None and a.size != size:
-                raise ValueError('%s has %d values, the call needs %d' % (name, a.size, size))
-        if keep[0].size < N or keep[1].size < N or keep[2].size < max(int(view.nx), 0):
-            raise ValueError('D, charges or x shorter than the view')
-        p = CatsensParams(C.sizeof(CatsensParams) if struct_size is None else int(struct_size), int(max_waves),
-                          wall_bc if isinstance(wall_bc, int) else WALL[wall_bc], R, W, P, n, None if idx is None else idx.ctypes.data_as(_PL),
-                          _dptr(keep[0]), _dptr(keep[1]), _dptr(keep[3]), _dptr(keep[2]), float(beta), float(eps), float(dx), float(velocity),
-                          float(stern_capacitance), float(phi_pzc), _iptr(n_lhs), _iptr(lhs), _iptr(n_rhs), _iptr(rhs), _dptr(kf), _dptr(kr),
-                          _iptr(wk[0]), _dptr(wk[1]), _dptr(wk[2]), _dptr(wk[3]), _dptr(wk[4]), _dptr(keep[4]), _dptr(g),
-                          _iptr(kind) if len(kind) else None, _iptr(index) if len(index) else None)
-        Ps = min(max(P, 0), len(kind))
-        res = {} if out is None else out
-        for name in names:
-            res.setdefault(name, np.empty((n, Ps) + FIELDS[name](N)))
-        res.setdefault('status', np.zeros(n, np.int32))
-        o = CatsensOutputs(struct_size=C.sizeof(CatsensOutputs) if out_struct_size is None else int(out_struct_size),
-                           status=_iptr(res['status']), **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
+        medium = Medium(view, D, charges, x, beta, mpb_radius, velocity, reactions, eps=eps, dx=dx, wall_bc=wall_bc,
+                        stern_capacitance=stern_capacitance, max_waves=max_waves, wall=wall, lanes=lanes)
+        B, N, _ = medium.dims
+        pm, g = _f64(phiM), _f64(flux)
+        if medium.idx is None:
+            medium.rows(0 if g is None else g.size // max(N, 1))
+        n = medium.n
+        medium.check('the call needs', [('flux', g, n * N), ('phiM', pm, B)])
+        p = CatsensParams(struct_size=_devlib.size_of(CatsensParams, struct_size), nparams=P, phi_pzc=float(phi_pzc), phiM=_dptr(pm),
+                          flux=_dptr(g), kind=_iptr(kind) if len(kind) else None, index=_iptr(index) if len(index) else None,
+                          **medium.members)
+        res = _devlib.results(out, {name: FIELDS[name](N) for name in names}, (n, min(max(P, 0), len(kind))), status=n)
+        o = CatsensOutputs(struct_size=_devlib.size_of(CatsensOutputs, out_struct_size), status=_iptr(res['status']),
+                           **{name: _dptr(a) for name, a in res.items() if name in FIELDS})
         self._call('solve', view, p, o)
         return res

@@ -624,19 +624,24 @@ CHUNK_ENV = {'get_response': 'CATRESP_WORKSPACE_BYTES', 'get_relaxation': 'CATMO
 _SAT = {}
 
 
-def satellite_handle(nx, B):
+def make_satellite_handle(nx, B):
     """tests/test_gpu_kinetics.py's handle (cation, anion and a neutral species at a Stern wall, |phiM| <= 0.12 V) at nx points, solved"""
+    from tests.test_gpu_newton import BETA, EPS, F
+    D, q, cb = np.array([1.957e-9, 1.185e-9, 1.9e-9]), np.array([F, -F, 0.0]), np.array([10.0, 10.0, 1.0])
+    dx = np.sqrt(EPS / BETA / (q ** 2 * cb).sum()) / 6.0
+    s = _capi.PnpSolver(3, nx, dx, 1.0, BETA, EPS, D, q, method='Newton', batch_capacity=B)
+    s.set_newton(wall_bc='stern', stern_capacitance=0.2, phi_pzc=0.0)
+    pb = np.zeros((B, 4))
+    pb[:, 0] = np.linspace(-0.12, 0.06, B)
+    s.set_batch(np.repeat(np.repeat(cb[None, :, None], nx, axis=2), B, axis=0), pb, np.zeros(B), np.zeros((B, 3)))
+    assert (s.solve_stationary() == 0).all()
+    return s
+
+
+def satellite_handle(nx, B):
+    """make_satellite_handle(nx, B), one per nx for the module"""
     if nx not in _SAT:
-        from tests.test_gpu_newton import BETA, EPS, F
-        D, q, cb = np.array([1.957e-9, 1.185e-9, 1.9e-9]), np.array([F, -F, 0.0]), np.array([10.0, 10.0, 1.0])
-        dx = np.sqrt(EPS / BETA / (q ** 2 * cb).sum()) / 6.0
-        s = _capi.PnpSolver(3, nx, dx, 1.0, BETA, EPS, D, q, method='Newton', batch_capacity=B)
-        s.set_newton(wall_bc='stern', stern_capacitance=0.2, phi_pzc=0.0)
-        pb = np.zeros((B, 4))
-        pb[:, 0] = np.linspace(-0.12, 0.06, B)
-        s.set_batch(np.repeat(np.repeat(cb[None, :, None], nx, axis=2), B, axis=0), pb, np.zeros(B), np.zeros((B, 3)))
-        assert (s.solve_stationary() == 0).all()
-        _SAT[nx] = s
+        _SAT[nx] = make_satellite_handle(nx, B)
     return _SAT[nx]
 
 
@@ -710,3 +715,29 @@ def test_satellite_library_objects_carry_nothing_over(name, chunked, satellite_h
     for res in (large, want):                                 # (both cases were solved: the comparison is not one of NaN rows)
         if 'status' in res:
             assert (res['status'] == 0).all(), (name, res['status'])
+
+
+def test_close_destroys_every_satellite_context():
+    """Every entry point that opens a library object, once, on a handle of this test's own (66 points, seven lanes): the ten of
+    satellite_call, then the transient, the kinetic admittance, the impedance and the steady state of an interacting model.  All thirteen
+    attributes of PnpSolver.SATELLITES then hold a context; after close() every one is None and the context behind it is destroyed."""
+    from tests import interact_cases as IC
+    from tests import kinetics_cases as KC
+    table = _capi.PnpSolver.SATELLITES
+    assert {a for attrs in SATELLITES.values() for a in attrs} <= set(table)
+    assert len(table) == 13
+    lanes, model = [5, 0, 3], KC.co2r_model('two_site')
+    s = make_satellite_handle(66, 7)
+    try:
+        for name in SATELLITES:
+            assert len(satellite_call(name, s, None if name in ('get_electrolyte', 'get_balance') else lanes)) >= 2, name
+        assert s.get_kinetics_transient(model, [1e-6, 1e-3], lanes=lanes)['flux'].shape == (3, 2, 3)
+        assert s.get_kinetic_admittance(model, (0.0, 1e3), lanes=lanes)['Kc'].shape == (3, 2, 3, 3)
+        assert s.get_impedance(model, (0.0, 1e3), lanes=lanes)['impedance'].shape == (3, 2)
+        assert s.get_kinetics(IC.case('co2r_one_site_weak').tables, lanes=lanes)['ramp_reached'].shape == (3,)
+        handles = {a: getattr(s, a) for a in table}
+        assert all(h is not None and h._h.value for h in handles.values()), [a for a, h in handles.items() if h is None]
+    finally:
+        s.close()
+    for a, h in handles.items():
+        assert getattr(s, a) is None and not h._h.value, a

@@ -7,8 +7,12 @@ libcatint_kinetics and libcatint_eis (cateis_solve) one series is REPEATS calls 
 median wall time of a call (host clock around the call, which ends in a stream synchronise) and the median of last_kernel_ms.
 
     python tools/probe/host_frame_probe.py --old DIR [--series 6] [--out FILE]
+    python tools/probe/host_frame_probe.py --old-tree DIR [--series 6] [--out FILE]
 
-DIR holds the libraries of the build to compare with (libcatint_*.so); the tree's own build is the other.  The series run in the order
+DIR holds the libraries of the build to compare with (libcatint_*.so); the tree's own build is the other.  With --old-tree the two sides
+differ in their Python instead: DIR holds the catint_amd package of another checkout (its *.py; no lib/ is needed), both sides load this
+tree's libraries, and the calls go through the PnpSolver entry points (get_response, get_coupling, get_kinetics, get_impedance), where
+the Python share of a call sits.  The series run in the order
 old new new old old new ..., so that neither build always follows the other, and each build has --series independent series.  The
 noise of the comparison is the spread between the medians of the old build's own series; the table puts the difference of the two
 builds' medians beside it.  No figure is fixed in advance."""
@@ -27,10 +31,14 @@ sys.path.insert(0, R)
 REPEATS, WARMUPS = 300, 20
 N_POINTS, NX = 64, 33
 LIBS = ('response', 'couple', 'kinetics', 'eis')
+ENTRIES = {'response': ('get_response', '_responder'), 'couple': ('get_coupling', '_coupler'), 'kinetics': ('get_kinetics', '_kinetics'),
+           'eis': ('get_impedance', '_impedance')}
 
 
-def series():
-    """one series of every library on the libraries the environment names; a JSON line"""
+def series(solver=False):
+    """one series of every library on the libraries the environment names; a JSON line.  solver: through the PnpSolver entry points"""
+    if os.environ.get('CATINT_PROBE_TREE'):
+        sys.path.insert(0, os.environ['CATINT_PROBE_TREE'])
     from catint_amd import _couple, _eis, _kinetics, _response
     from tests import eis_cases as EC
     from tests import response_cases as RC
@@ -59,6 +67,14 @@ def series():
         'eis': lambda: handles['eis'].solve(view, tables, phis, kin['theta'], omega, *medium, rf=1.0, lanes=lanes, out=out['eis'], **wall,
                                             phi_pzc=o['phi_pzc']),
     }
+    if solver:
+        kin = s.get_kinetics(tables, fields=('theta', 'flux', 'dflux_dc', 'dflux_dphi'))
+        calls = {'response': lambda: s.get_response(omega=omega), 'couple': lambda: s.get_coupling(None, kin),
+                 'kinetics': lambda: s.get_kinetics(tables), 'eis': lambda: s.get_impedance(tables, omega, theta=kin['theta'])}
+        for name in LIBS:
+            calls[name]()
+            handles[name].close()
+            handles[name] = getattr(s, ENTRIES[name][1])
     res = {}
     for name in LIBS:
         f, h = calls[name], handles[name]
@@ -71,7 +87,7 @@ def series():
                 wall_ms.append(1e3 * (t1 - t0)), kern_ms.append(h.last_kernel_ms)
         res[name] = {'wall_ms': float(np.median(wall_ms)), 'kernel_ms': float(np.median(kern_ms)), 'kernel': h.last_kernel}
     for h in handles.values():
-        h.close()
+        h.close()          # (a solver's own library objects are closed a second time by s.close(): nothing happens)
     s.close()
     print('SERIES ' + json.dumps(res))
 
@@ -79,20 +95,27 @@ def series():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--old', help='directory with the libraries of the build to compare with')
+    ap.add_argument('--old-tree', help='directory with the catint_amd package (Python) of the checkout to compare with')
+    ap.add_argument('--solver', action='store_true', help='(internal, with --one) call through the PnpSolver entry points')
     ap.add_argument('--series', type=int, default=6)
     ap.add_argument('--out', default=None, help='also write the table to this file')
     ap.add_argument('--one', action='store_true', help='(internal) run one series in this process')
     a = ap.parse_args()
     if a.one:
-        return series()
+        return series(a.solver)
     runs = {'old': [], 'new': []}
     for k in range(a.series):
         for build in (('old', 'new') if k % 2 == 0 else ('new', 'old')):
             env = dict(os.environ)
-            if build == 'old':
+            if build == 'old' and a.old_tree:
+                env['CATINT_PROBE_TREE'] = os.path.abspath(a.old_tree)
+                for lib in LIBS + ('pnp',):
+                    env['CATINT_%s_LIB' % lib.upper()] = os.path.join(os.path.abspath(R), 'catint_amd', 'lib', 'libcatint_%s.so' % lib)
+            elif build == 'old':
                 for lib in LIBS:
                     env['CATINT_%s_LIB' % lib.upper()] = os.path.join(os.path.abspath(a.old), 'libcatint_%s.so' % lib)
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--one'], env=env, capture_output=True, text=True, timeout=280)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), '--one'] + (['--solver'] if a.old_tree else []), env=env,
+                               capture_output=True, text=True, timeout=280)
             if r.returncode != 0:          # a series that failed ends the probe: nothing more is started on the device
                 sys.stderr.write(r.stdout + r.stderr)
                 sys.exit(r.returncode or 1)
