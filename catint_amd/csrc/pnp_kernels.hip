@@ -281,6 +281,14 @@ __device__ __forceinline__ double uniform_f64(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// Instances whose Crank-Nicolson stencil forms two coefficient arrays instead of four (see there).  The three left out keep the four:
+// with two, <4,3,1> and <4,4,1> need 97 vector registers, one more than five waves per SIMD allow, and <16,1,3>, which spills
+// already, spills 52 bytes more (profiles/step_diet_isa.md).
+template <int P, int W, int G>
+constexpr bool step_two_coefficients() {
+  return !(P == 4 && W >= 3) && !(P == 16 && W == 1 && G == 3);
+}
+
 // The body of step_kernel: every instance compiles it with FAST = false, the instances of step_has_fast_body() with FAST = true as well.
 //   FAST = false: the general body.  Method, Poisson branch, migration, rate terms and the number of staging rounds are run-time
 //     flags, and every launch constant is read where it is used.
@@ -297,6 +305,7 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
   constexpr int NR = W * G;              // species rows staged per round
   constexpr int V1SLOT = RB - 2;         // v[1] broadcast slot inside GV
   constexpr int IT2 = P / (2 * W) + 1;   // coalesced 16-byte chunks owned by one thread
+  constexpr bool TWO_COEF = step_two_coefficients<P, W, G>();
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -492,25 +501,52 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
               // from the species table, so the unit-diagonal rows cost no extra multiplies
               const double hsr = FAST ? k_hsr[g] : S.hsr, e4r = FAST ? k_e4r[g] : S.e4r;
               const double eer = FAST ? k_eer[g] : S.eer, omsr = FAST ? k_omsr[g] : S.omsr;
-              double cc[P + 2], g4[P + 2];
+              double cc[P + 2];
 #pragma unroll
               for (int t = 0; t < P + 2; ++t) cc[t] = ROW[pidx<P>(r0 + t)];
+              if constexpr (TWO_COEF) {
+                // The stencil coefficients of a point, each rounded once (the products e4r*grad_v contracted into them):
+                //   sp[t] = hsr + e4r*grad_v,  sm[t] = hsr - e4r*grad_v   at entry r0 + t of GV.
+                // B1's off-diagonals are sp and sm; A's are their negatives, -hsr + e4r*grad_v = -sm and -hsr - e4r*grad_v = -sp
+                // (:487, :490): round-to-nearest is symmetric, so the negation of the rounded value is the rounded value of the
+                // negated sum, and a negated fp64 operand costs nothing.  2(P+1) fused multiply-adds instead of 4P.
+                double sp[P + 1], sm[P + 2];
 #pragma unroll
-              for (int t = 0; t < P + 2; ++t) g4[t] = e4r * GV[pidx<P>(r0 + t)];
+                for (int t = 0; t < P + 2; ++t) {
+                  const double gv = GV[pidx<P>(r0 + t)];
+                  if (t <= P) sp[t] = __builtin_fma(e4r, gv, hsr);
+                  sm[t] = __builtin_fma(-e4r, gv, hsr);     // (sm[0] is not used)
+                }
 #pragma unroll
-              for (int j = 0; j < P; ++j) {
-                // B = C[k,1:-1] . B1  (row-vector x matrix, :553):
-                //   B[r] = c[r-1]*B1[r-1,r] + c[r]*B1[r,r] + c[r+1]*B1[r+1,r]
-                const double lq = LV[pidx<P>(r0 + j)];
-                const double left = cc[j] * (hsr + g4[j]);
-                const double right = cc[j + 2] * (hsr - g4[j + 2]);
-                x[g][j] = left + cc[j + 1] * (omsr + eer * lq) + right;
-                ta[g][j] = -hsr + g4[j + 1];                               // A[r,r-1], :487
-                tc[g][j] = -hsr - g4[j + 1];                               // A[r,r+1], :490
-                if (j == jmu) tc[g][j] = in_lm ? 0.0 : tc[g][j];           // ... which the last real row lacks
-                // rows r >= m only see finite inputs and row m-1 has no super-diagonal, so they form a
-                // benign trailing block that never feeds back into the real unknowns
+                for (int j = 0; j < P; ++j) {
+                  // B = C[k,1:-1] . B1  (row-vector x matrix, :553):
+                  //   B[r] = c[r-1]*B1[r-1,r] + c[r]*B1[r,r] + c[r+1]*B1[r+1,r]
+                  // The contraction is written out (as for FTCS below), the way the compiler contracts the statement of the other
+                  // branch: the middle product stays a product of its own, the outer two are fused into the sum from left to right.
+                  const double lq = LV[pidx<P>(r0 + j)];
+                  const double mid = cc[j + 1] * __builtin_fma(eer, lq, omsr);
+                  x[g][j] = __builtin_fma(cc[j + 2], sm[j + 2], __builtin_fma(cc[j], sp[j], mid));
+                  ta[g][j] = -sm[j + 1];                                     // A[r,r-1], :487
+                  tc[g][j] = -sp[j + 1];                                     // A[r,r+1], :490
+                  if (j == jmu) tc[g][j] = in_lm ? 0.0 : tc[g][j];           // ... which the last real row lacks
+                }
+              } else {
+                double g4[P + 2];
+#pragma unroll
+                for (int t = 0; t < P + 2; ++t) g4[t] = e4r * GV[pidx<P>(r0 + t)];
+#pragma unroll
+                for (int j = 0; j < P; ++j) {
+                  const double lq = LV[pidx<P>(r0 + j)];
+                  const double left = cc[j] * (hsr + g4[j]);
+                  const double right = cc[j + 2] * (hsr - g4[j + 2]);
+                  x[g][j] = left + cc[j + 1] * (omsr + eer * lq) + right;
+                  ta[g][j] = -hsr + g4[j + 1];                               // A[r,r-1], :487
+                  tc[g][j] = -hsr - g4[j + 1];                               // A[r,r+1], :490
+                  if (j == jmu) tc[g][j] = in_lm ? 0.0 : tc[g][j];           // ... which the last real row lacks
+                }
               }
+              // rows r >= m only see finite inputs and row m-1 has no super-diagonal, so they form a
+              // benign trailing block that never feeds back into the real unknowns
               if (lane == 0) ta[g][0] = 0.0;                               // first row has no sub-diagonal
             }
           }
@@ -570,16 +606,12 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
       wg_sync<W>();
       // ---- 3. cooperative epilogue: store the round's rows, fold them into the next charge row ----
       const int nk = min(NR, N - k0);
-      auto store_and_fold = [&](int w2, double qe) {
+      auto store_and_fold = [&](int w2, double qe) {   // (the general body's; the fast body's epilogue is below)
         const double* R2 = ROWS + w2 * RB;
         double* grow = crow0 + (int64_t)(k0 + w2) * ldx;
         const __amdgpu_buffer_rsrc_t rs = row_rsrc(grow, ldx);
 #pragma unroll
         for (int it = 0; it < IT2; ++it) {
-          // Fast body: a wave whose whole 1-KiB chunk of this iteration lies beyond the pitch skips it (wave-uniform): everything
-          // below would be don't-care reads, dropped stores and sums that nobody uses (headline shape: the second iteration
-          // holds 128 doubles, all of them wave 0's).  The first iteration is left alone: one branch less on every wave's path.
-          if (FAST && W > 1 && it > 0 && 128 * (W * it + wave) >= ldx) continue;
           // threads past the staged row (W > 1: the workgroup spans more than one row buffer) read a
           // clamped, don't-care slot; their global store is dropped by the range check
           const int sl = min(pair_slot<P>(ls2, W * it), RB - 4);
@@ -599,9 +631,33 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
         }
       };
       if constexpr (FAST) {
+        // Fast body: chunk by chunk, the staged rows' pairs of a chunk are read together, ahead of the chunk's stores, instead of
+        // one LDS round trip per row and store, and the status is taken behind the time loop (see there).  A row that no
+        // species uses (w2 >= nk) is read as well and its values dropped (finite ones: the zeros it was initialised with, or a short last
+        // group's recomputed species N-1).  The fold into a chunk's charge values runs in species order, as in the general body.
 #pragma unroll
-        for (int w2 = 0; w2 < NR; ++w2)
-          if (w2 < nk) store_and_fold(w2, k_qe[w2]);
+        for (int it = 0; it < IT2; ++it) {
+          // a wave whose whole 1-KiB chunk of this iteration lies beyond the pitch skips it (wave-uniform): everything below would be
+          // don't-care reads, dropped stores and sums that nobody uses (headline shape: the second iteration holds 128 doubles, all
+          // of them wave 0's).  The first iteration is left alone: one branch less on every wave's path.
+          if (W > 1 && it > 0 && 128 * (W * it + wave) >= ldx) continue;
+          const int sl = min(pair_slot<P>(ls2, W * it), RB - 4);   // (clamped as in store_and_fold)
+          d2 t[NR];
+#pragma unroll
+          for (int w2 = 0; w2 < NR; ++w2) {
+            t[w2].x = ROWS[w2 * RB + sl];
+            t[w2].y = ROWS[w2 * RB + sl + PAIR_STEP<P>];
+          }
+#pragma unroll
+          for (int w2 = 0; w2 < NR; ++w2) {
+            if (w2 < nk) {
+              const __amdgpu_buffer_rsrc_t rs = row_rsrc(crow0 + (int64_t)w2 * ldx, ldx);
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, t[w2]), rs, tid * 16 + it * (1024 * W), 0, 0);
+              accp[it].x = __builtin_fma(-t[w2].x, k_qe[w2], accp[it].x);
+              accp[it].y = __builtin_fma(-t[w2].y, k_qe[w2], accp[it].y);
+            }
+          }
+        }
       } else {
         for (int w2 = 0; w2 < nk; ++w2) store_and_fold(w2, A.spec[k0 + w2].qe);
         // the staged rows are free for the next round's loads
@@ -638,6 +694,25 @@ __device__ __forceinline__ void step_body(const DevArgs& A, double* lds) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if constexpr (W > 1) __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      }
+    }
+  }
+  if constexpr (FAST) {
+    // Fast body: status of the state this launch leaves behind (the reference tests after the solve, calculator.py:409-414), from the
+    // staged rows: they are complete since the barrier in front of the last step's epilogue and nothing has written to them since.
+    // Every thread evaluates the chunks it stored, in the epilogue's order; a chunk skipped there lies beyond the pitch (no inrow
+    // pair).  A launch of no step leaves no state behind and reports nothing.
+    if (A.nsteps > 0) {
+      const int nk = min(NR, N);
+      for (int w2 = 0; w2 < nk; ++w2) {
+#pragma unroll
+        for (int it = 0; it < IT2; ++it) {
+          const int sl = min(pair_slot<P>(ls2, W * it), RB - 4);
+          const bool inrow = 2 * tid + 128 * W * it < ldx;
+          const double sx = inrow ? ROWS[w2 * RB + sl] : 0.0, sy = inrow ? ROWS[w2 * RB + sl + PAIR_STEP<P>] : 0.0;
+          chk += (sx - sx) + (sy - sy);
+          mn = fmin(mn, fmin(sx, sy));
+        }
       }
     }
   }
