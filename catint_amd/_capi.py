@@ -884,6 +884,45 @@ class PnpSolver(object):
             max_steps=_kintrans.DEFAULT_MAX_STEPS if max_steps is None else max_steps, fields=fields, max_waves=max_waves,
             **self._kinetic_common(potential_drop, stern_capacitance, phi_pzc, sigma=sigma, off=off, gamma=gamma))
 
+    def get_voltammogram(self, model_or_tables, E_start, E_vertex, scan_rate, n_segments=2, samples=200, electrons=None, lanes=None, csurf=None,
+                         phi_surface=None, theta0=None, rtol=None, atol=None, rate_floor=None, kT=None, fields=None, potential_drop='stern',
+                         stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None, h0=0.0, newton_tol=None,
+                         newton_maxit=None, max_steps=None, max_waves=0):
+        """The voltammogram of the microkinetic model at a constant surface state (include/catint_voltam.h) integrated on the device,
+        one operating point per entry of `lanes`, every point with its own potential program and step size: the adsorption and
+        desorption peaks of a linear or cyclic sweep, their shift with the scan rate and the charge under them.  The model, the surface
+        state (this handle's, or csurf and phi_surface), stern_capacitance, phi_pzc, sigma, off, gamma and the handling of lanes are
+        those of get_kinetics_transient; the electrode potential of the lanes is replaced by the program: E_start, E_vertex [n] in V
+        (a scalar: the same for every point), scan_rate [n] in V/s, n_segments segments of `samples` output times each.  electrons [R]:
+        None takes the model's electrons() (a dict of tables needs them given).  Everything else, and the dict returned ('theta',
+        'current', 'current_scale', 'charge', 'E_out', 't_reached', 'mean_current', 'status', 'steps'), is that of
+        catint_amd.voltammetry.Voltammetry.sweep.  The electrolyte does not answer the sweep: its surface concentrations and surface
+        potential stay what they are.
+        The context of the library is opened for this call and closed after it: for repeated sweeps hold a
+        catint_amd.voltammetry.Voltammetry and call its sweep with device_view()."""
+        from . import voltammetry
+        model = model_or_tables if hasattr(model_or_tables, 'tables') else None
+        tables = self._model_tables(model_or_tables, site_density)
+        if electrons is None and model is not None:
+            electrons = model.electrons()
+        if kT is None and model is not None:
+            kT = model.kT
+        if lanes is None and csurf is None and phi_surface is None:
+            n = self.B
+        elif lanes is not None:
+            n = np.size(lanes)
+        else:
+            n = np.size(phi_surface) if phi_surface is not None else np.size(E_start)
+        es = np.broadcast_to(np.asarray(E_start, float).reshape(-1), (n,)) if np.size(E_start) == 1 else np.asarray(E_start, float).reshape(-1)
+        host, idx, es = self._kinetic_points('get_voltammogram', lanes, es, csurf, phi_surface)
+        opts = {k: v for k, v in dict(rtol=rtol, atol=atol, newton_tol=newton_tol, newton_maxit=newton_maxit, max_steps=max_steps).items()
+                if v is not None}
+        with voltammetry.Voltammetry(self._obs['device']) as vm:
+            return vm.sweep(None if host else self.device_view(), tables, electrons, es, E_vertex, scan_rate, n_segments=n_segments,
+                            samples=samples, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, theta0=theta0,
+                            rate_floor=rate_floor, kT=kT, h0=h0, fields=fields, max_waves=max_waves,
+                            **self._kinetic_common(potential_drop, stern_capacitance, phi_pzc, sigma=sigma, off=off, gamma=gamma), **opts)
+
     def get_rate_control(self, model_or_tables, theta=None, phiM=None, lanes=None, csurf=None, phi_surface=None, fields=None,
                          potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None,
                          residual_tol=1e-8, max_waves=0, kin=None, coupling=None, rf=1.0):

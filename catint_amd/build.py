@@ -126,6 +126,15 @@ INTERACT_LIB = os.path.join(LIB_DIR, 'libcatint_interact.so')
 INTERACT_SOURCES = ['catia.hip']
 INTERACT_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_interact.h')]
 
+# sixteenth library (include/catint_voltam.h): the voltammogram of the microkinetic model -- the implicit Euler integrator of the thirteenth
+# along a linear potential program, the current in the error norm and the extrapolated state accepted, with current and charge as outputs.
+# It includes pnp_kin.h as it is.  A library of its own as the fourteen before it: the method's definition differs from the thirteenth's,
+# whose bits are pinned
+VOLTAM_DIR = os.path.join(CSRC, 'voltam')
+VOLTAM_LIB = os.path.join(LIB_DIR, 'libcatint_voltam.so')
+VOLTAM_SOURCES = ['catvm.hip']
+VOLTAM_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h'), os.path.join(_INCLUDE, 'catint_voltam.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -328,6 +337,15 @@ def interact_needs_build():
 def build_interact_library(force=False, verbose=False):
     """catint_amd/csrc/interact into catint_amd/lib/libcatint_interact.so"""
     return _build_unit(INTERACT_DIR, INTERACT_SOURCES, INTERACT_HEADERS, INTERACT_LIB, force, verbose)
+
+
+def voltam_needs_build():
+    return _unit_needs_build(VOLTAM_DIR, VOLTAM_SOURCES, VOLTAM_HEADERS, VOLTAM_LIB)
+
+
+def build_voltam_library(force=False, verbose=False):
+    """catint_amd/csrc/voltam into catint_amd/lib/libcatint_voltam.so"""
+    return _build_unit(VOLTAM_DIR, VOLTAM_SOURCES, VOLTAM_HEADERS, VOLTAM_LIB, force, verbose)
 
 
 def unittest_needs_build():

@@ -154,6 +154,11 @@ class MeanFieldModel(object):
         """eV"""
         return unit_kB * self.temperature / unit_e
 
+    def electrons(self):
+        """[R]: the electrons on the reactant side of every step (negative: released), the n_e that tables() puts into dG and Ea; what
+        catint_amd.voltammetry.Voltammetry.sweep counts the current with"""
+        return np.array([float(st['electrons']) for st in self.steps])
+
     def tables(self, site_density=None):
         N, T, R = len(self.species), len(self.site_count), len(self.steps)
         kT = self.kT
