@@ -4,5 +4,6 @@ from ._capi import (PnpSolver, PnpError, PnpLibraryError, load_library, LIB_PATH
                     PB_DD, PB_VWALL_GBULK, PB_GWALL_VBULK, PB_VWALL_GWALL, PB_VBULK_GBULK,
                     STATUS_OK, STATUS_NAN, STATUS_NEGATIVE)
 from .voltammetry import Voltammetry  # noqa: F401
+from .iasweep import InteractingVoltammetry  # noqa: F401
 
 __version__ = '0.1.0'

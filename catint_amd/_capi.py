@@ -887,7 +887,7 @@ class PnpSolver(object):
     def get_voltammogram(self, model_or_tables, E_start, E_vertex, scan_rate, n_segments=2, samples=200, electrons=None, lanes=None, csurf=None,
                          phi_surface=None, theta0=None, rtol=None, atol=None, rate_floor=None, kT=None, fields=None, potential_drop='stern',
                          stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None, h0=0.0, newton_tol=None,
-                         newton_maxit=None, max_steps=None, max_waves=0):
+                         newton_maxit=None, max_steps=None, max_waves=0, hold_time=None, start_ramp=None):
         """The voltammogram of the microkinetic model at a constant surface state (include/catint_voltam.h) integrated on the device,
         one operating point per entry of `lanes`, every point with its own potential program and step size: the adsorption and
         desorption peaks of a linear or cyclic sweep, their shift with the scan rate and the charge under them.  The model, the surface
@@ -898,9 +898,15 @@ class PnpSolver(object):
         'current', 'current_scale', 'charge', 'E_out', 't_reached', 'mean_current', 'status', 'steps'), is that of
         catint_amd.voltammetry.Voltammetry.sweep.  The electrolyte does not answer the sweep: its surface concentrations and surface
         potential stay what they are.
+        A model with lateral interactions or several site types (catint_amd.interactions.InteractingModel, or a dict with its keys)
+        goes to include/catint_iasweep.h instead (catint_amd.iasweep.InteractingVoltammetry.sweep): theta0 and 'theta' have T = G + S
+        columns, fields may name 'energy_shift' [n][n_out][S], hold_time [n] holds the points whose E_vertex equals E_start at that
+        potential, and start_ramp is the number of stages of the steady solve at E_start (None: 10 from the uniform start, 1 with
+        theta0).  hold_time and start_ramp are errors for a mean-field model.
         The context of the library is opened for this call and closed after it: for repeated sweeps hold a
-        catint_amd.voltammetry.Voltammetry and call its sweep with device_view()."""
+        catint_amd.voltammetry.Voltammetry (catint_amd.iasweep.InteractingVoltammetry) and call its sweep with device_view()."""
         from . import voltammetry
+        from .interactions import has_interactions
         model = model_or_tables if hasattr(model_or_tables, 'tables') else None
         tables = self._model_tables(model_or_tables, site_density)
         if electrons is None and model is not None:
@@ -917,11 +923,21 @@ class PnpSolver(object):
         host, idx, es = self._kinetic_points('get_voltammogram', lanes, es, csurf, phi_surface)
         opts = {k: v for k, v in dict(rtol=rtol, atol=atol, newton_tol=newton_tol, newton_maxit=newton_maxit, max_steps=max_steps).items()
                 if v is not None}
-        with voltammetry.Voltammetry(self._obs['device']) as vm:
+        more = {}
+        if has_interactions(tables):
+            from . import iasweep
+            opened = iasweep.InteractingVoltammetry
+            more = dict(hold_time=hold_time, start_ramp=start_ramp)
+        elif hold_time is not None or start_ramp is not None:
+            raise ValueError('get_voltammogram: hold_time and start_ramp belong to a model with lateral interactions or several site types')
+        else:
+            opened = voltammetry.Voltammetry
+        with opened(self._obs['device']) as vm:
             return vm.sweep(None if host else self.device_view(), tables, electrons, es, E_vertex, scan_rate, n_segments=n_segments,
                             samples=samples, lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, theta0=theta0,
                             rate_floor=rate_floor, kT=kT, h0=h0, fields=fields, max_waves=max_waves,
-                            **self._kinetic_common(potential_drop, stern_capacitance, phi_pzc, sigma=sigma, off=off, gamma=gamma), **opts)
+                            **self._kinetic_common(potential_drop, stern_capacitance, phi_pzc, sigma=sigma, off=off, gamma=gamma), **opts,
+                            **more)
 
     def get_rate_control(self, model_or_tables, theta=None, phiM=None, lanes=None, csurf=None, phi_surface=None, fields=None,
                          potential_drop='stern', stern_capacitance=None, phi_pzc=None, sigma=None, off=None, gamma=None, site_density=None,

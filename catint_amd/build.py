@@ -135,6 +135,14 @@ VOLTAM_LIB = os.path.join(LIB_DIR, 'libcatint_voltam.so')
 VOLTAM_SOURCES = ['catvm.hip']
 VOLTAM_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_kinetics.h'), os.path.join(_INCLUDE, 'catint_voltam.h')]
 
+# seventeenth library (include/catint_iasweep.h): the voltammogram of the model of the fifteenth library -- the step loop of the sixteenth
+# over coverage-dependent rate constants and one site row per type, and a hold at constant potential.  It includes pnp_kin.h as it is and
+# restates what it takes from the two.  A library of its own as the fifteen before it: the bits and the kernel sets of both are pinned
+IASWEEP_DIR = os.path.join(CSRC, 'iasweep')
+IASWEEP_LIB = os.path.join(LIB_DIR, 'libcatint_iasweep.so')
+IASWEEP_SOURCES = ['catis.hip']
+IASWEEP_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, h) for h in ('catint_kinetics.h', 'catint_interact.h', 'catint_voltam.h', 'catint_iasweep.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -346,6 +354,15 @@ def voltam_needs_build():
 def build_voltam_library(force=False, verbose=False):
     """catint_amd/csrc/voltam into catint_amd/lib/libcatint_voltam.so"""
     return _build_unit(VOLTAM_DIR, VOLTAM_SOURCES, VOLTAM_HEADERS, VOLTAM_LIB, force, verbose)
+
+
+def iasweep_needs_build():
+    return _unit_needs_build(IASWEEP_DIR, IASWEEP_SOURCES, IASWEEP_HEADERS, IASWEEP_LIB)
+
+
+def build_iasweep_library(force=False, verbose=False):
+    """catint_amd/csrc/iasweep into catint_amd/lib/libcatint_iasweep.so"""
+    return _build_unit(IASWEEP_DIR, IASWEEP_SOURCES, IASWEEP_HEADERS, IASWEEP_LIB, force, verbose)
 
 
 def unittest_needs_build():

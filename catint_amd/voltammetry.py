@@ -80,7 +80,7 @@ class Voltammetry(_devlib.Handle):
         KineticsSolver.solve; the surface concentrations and the surface potential are constant over the sweep (the electrolyte does
         not answer).  tables: a catint_amd.microkinetics.MeanFieldModel or the dict of its tables(); electrons [R]: the electrons on the
         reactant side of every step (None: the model's electrons()).  A model with lateral interactions or several site types is
-        refused: the integrator is mean-field on one site type.
+        refused: the integrator is mean-field on one site type (catint_amd.iasweep.InteractingVoltammetry takes such a model).
         E_start, E_vertex [n] in V and scan_rate [n] in V/s: segment 0 runs from E_start to E_vertex, segment 1 back, and so on for
         n_segments segments (1: a linear sweep, 2: one cycle); every segment has `samples` equidistant output times, the last of them
         its end.  sigma [n]: a surface charge held constant over the sweep (None: it follows the potential through the Stern
