@@ -5,5 +5,6 @@ from ._capi import (PnpSolver, PnpError, PnpLibraryError, load_library, LIB_PATH
                     STATUS_OK, STATUS_NAN, STATUS_NEGATIVE)
 from .voltammetry import Voltammetry  # noqa: F401
 from .iasweep import InteractingVoltammetry  # noqa: F401
+from .iacontrol import InteractingRateControl  # noqa: F401
 
 __version__ = '0.1.0'

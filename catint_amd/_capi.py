@@ -953,8 +953,16 @@ class PnpSolver(object):
         state.  With kin (get_kinetics(..., fields=('dflux_dc', 'dflux_dphi')) and coupling (get_coupling's 'T_c', 'T_phi') for the
         same lanes the result also carries the APPARENT ones of the coupled electrode, where the surface state answers the flux
         through mass transport: 'dflux_drc_apparent', 'dflux_dG_apparent' = M^-1 (rf dflux), M = I - rf (K_c T_c + K_phi (x) T_phi)
-        formed per point on the host, and 'drc_apparent', 'tdrc_apparent' normalised by rf flux (NaN rows where M is singular)."""
+        formed per point on the host, and 'drc_apparent', 'tdrc_apparent' normalised by rf flux (NaN rows where M is singular).
+        A model with lateral interactions or several site types (catint_amd.interactions.InteractingModel, or a dict with its keys)
+        goes to include/catint_iacontrol.h instead (catint_amd.iacontrol.InteractingRateControl.solve): the Jacobian carries the
+        coverage dependence of the energies, theta and 'dy_drc' have T = G + S columns, fields come from
+        catint_amd.iacontrol.FIELDS, which add 'dflux_dstrength' [n][N], 'dy_dstrength' [n][T] and 'strength_control' [n][N] =
+        strength dflux_dstrength / flux, the share of each flux owed to the interactions (with kin and coupling also
+        'dflux_dstrength_apparent', 'strength_control_apparent').  The context of that library is opened for this call and closed
+        after it: for repeated calls hold a catint_amd.iacontrol.InteractingRateControl and call its solve with device_view()."""
         from . import _drc
+        from .interactions import has_interactions
         tables = self._model_tables(model_or_tables, site_density)
         if (kin is None) != (coupling is None):
             raise ValueError('get_rate_control: kin and coupling come together')
@@ -963,15 +971,28 @@ class PnpSolver(object):
         if theta is None:
             theta = self.get_kinetics(tables, phiM=phiM, lanes=lanes, csurf=csurf, phi_surface=phi_surface, fields=('theta',), max_waves=max_waves,
                                       **common)['theta']
-        names = list(_drc.DEFAULT_FIELDS) if fields is None else list(fields)
-        ask = self._ask(names, ('dflux_drc', 'dflux_dG', 'flux') if kin is not None else ())
-        res = self._satellite('_rate_control').solve(None if host else self.device_view(), tables, phiM, theta, lanes=None if host else idx,
-                                                     csurf=csurf, phi_surface=phi_surface, residual_tol=residual_tol, fields=ask,
-                                                     max_waves=max_waves, **common)
+        interacting = has_interactions(tables)
+        if interacting:
+            from . import iacontrol
+        names = list((iacontrol if interacting else _drc).DEFAULT_FIELDS) if fields is None else list(fields)
+        needed = ('dflux_drc', 'dflux_dG', 'flux') + (('dflux_dstrength',) if interacting else ())
+        ask = self._ask(names, needed if kin is not None else ())
+        args = (None if host else self.device_view(), tables, phiM, theta)
+        kw = dict(lanes=None if host else idx, csurf=csurf, phi_surface=phi_surface, residual_tol=residual_tol, fields=ask, max_waves=max_waves,
+                  **common)
+        if interacting:
+            with iacontrol.InteractingRateControl(self._obs['device']) as rc:
+                res = rc.solve(*args, **kw)
+        else:
+            res = self._satellite('_rate_control').solve(*args, **kw)
         if kin is not None:
             for raw, norm in (('dflux_drc', 'drc'), ('dflux_dG', 'tdrc')):
                 res[raw + '_apparent'] = _drc.apparent(res[raw], kin, coupling, rf=rf)
                 res[norm + '_apparent'] = _drc.normalised(res[raw + '_apparent'], rf * res['flux'], tables['nu'])
+            if interacting:
+                one = _drc.apparent(res['dflux_dstrength'][:, None, :], kin, coupling, rf=rf)
+                res['dflux_dstrength_apparent'] = one[:, 0, :]
+                res['strength_control_apparent'] = float(tables.get('strength', 1.0)) * _drc.normalised(one, rf * res['flux'], tables['nu'])[:, 0, :]
         return self._trim(res, ask, names)
 
     def get_coupling(self, flux, kin, rf=1.0, lanes=None, dphi_max=0.05, fields=None, max_waves=0):

@@ -143,6 +143,15 @@ IASWEEP_LIB = os.path.join(LIB_DIR, 'libcatint_iasweep.so')
 IASWEEP_SOURCES = ['catis.hip']
 IASWEEP_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, h) for h in ('catint_kinetics.h', 'catint_interact.h', 'catint_voltam.h', 'catint_iasweep.h')]
 
+# eighteenth library (include/catint_iacontrol.h): the degree of rate control of the model of the fifteenth library -- the columns and the
+# refinement step of the tenth over the full Jacobian of the fifteenth, and a column for the interaction strength.  It includes pnp_kin.h as
+# it is and restates what it takes from the two.  A library of its own as the seventeen before it: the bits and the kernel sets of both are
+# pinned
+IACONTROL_DIR = os.path.join(CSRC, 'iacontrol')
+IACONTROL_LIB = os.path.join(LIB_DIR, 'libcatint_iacontrol.so')
+IACONTROL_SOURCES = ['catic.hip']
+IACONTROL_HEADERS = _KIN_HEADERS + [os.path.join(_INCLUDE, 'catint_iacontrol.h')]
+
 # test-only harness (tests/csrc/primitives_harness.hip): the shared device functions of the headers below, each behind a kernel of its own
 # in namespace catunit (tests/test_gpu_primitives.py).  Not part of the product: nothing links against it and no package module loads it
 UNITTEST_DIR = os.path.join(_HERE, '..', 'tests', 'csrc')
@@ -363,6 +372,15 @@ def iasweep_needs_build():
 def build_iasweep_library(force=False, verbose=False):
     """catint_amd/csrc/iasweep into catint_amd/lib/libcatint_iasweep.so"""
     return _build_unit(IASWEEP_DIR, IASWEEP_SOURCES, IASWEEP_HEADERS, IASWEEP_LIB, force, verbose)
+
+
+def iacontrol_needs_build():
+    return _unit_needs_build(IACONTROL_DIR, IACONTROL_SOURCES, IACONTROL_HEADERS, IACONTROL_LIB)
+
+
+def build_iacontrol_library(force=False, verbose=False):
+    """catint_amd/csrc/iacontrol into catint_amd/lib/libcatint_iacontrol.so"""
+    return _build_unit(IACONTROL_DIR, IACONTROL_SOURCES, IACONTROL_HEADERS, IACONTROL_LIB, force, verbose)
 
 
 def unittest_needs_build():

@@ -36,7 +36,13 @@ intrinsic ones; on an MI355X with --lanes 16 --newton: step 2 0.50 intrinsic, 0.
 --interactions EV: the same mechanism with a CO self-interaction of EV eV per unit coverage (catint_amd.interactions.InteractingModel,
 include/catint_interact.h): the binding energy of CO rises with its own coverage, the first SCF iteration ramps the interaction in ten
 stages inside one launch (the reference's n_inter), later iterations warm-start at full strength.  Works with the default loop and
-with --newton; the rate-control and device-loop libraries are mean-field and refuse such a model.
+with --newton; the device-loop library is mean-field and refuses such a model, and so does the calculator's own rate_control option.
+
+--interactions EV --rate-control: after the loop, one call of catint_amd.iacontrol.InteractingRateControl.solve
+(include/catint_iacontrol.h) at the final surface concentrations, surface potentials and coverages of every voltage: the intrinsic
+degree of rate control with the coverage dependence of the CO binding energy in the Jacobian, and the share of the CO flux that is owed
+to the interaction (strength_control; on an MI355X with --lanes 16 --newton --interactions 0.3: step 2 0.50, CO2* 0.99 to 1.00, and
++0.020 of the CO flux at -0.6 V falling to +0.002 at -1.2 V as the CO coverage falls from 0.054 to 0.014).
 """
 import argparse
 import os
@@ -84,15 +90,17 @@ def main():
     ap.add_argument('--rate-control', action='store_true', help='degree of rate control of the CO flux at the final state of every lane')
     ap.add_argument('--interactions', type=float, default=None, metavar='EV', help='CO self-interaction in eV per unit coverage')
     a = ap.parse_args()
-    if a.interactions is not None and (a.device_loop or a.rate_control):
-        ap.error('--device-loop and --rate-control work on the mean-field model: they exclude --interactions')
+    if a.interactions is not None and a.device_loop:
+        ap.error('--device-loop works on the mean-field model: it excludes --interactions')
     if a.newton and a.device_loop:
         ap.error('--device-loop is the mixing loop on the device: it excludes --newton')
     tp, phis = co2r_physical_sweep.build(a.lanes, a.nx, a.phimin, a.phimax)
     tp.newton = {'tol': 1e-8, 'maxit': 80}
     calc = Calculator(transport=tp, calc='comsol', tau_scf=1e-4, mix_scf=0.1)
-    calc.set_microkinetics(model(tp, a.interactions), site_density=a.site_fraction * float(tp.system['active site density']), potential_drop='stern',
-                          scf='newton' if a.newton else 'mixing', rate_control=a.rate_control, device_loop=a.device_loop)
+    site_density = a.site_fraction * float(tp.system['active site density'])
+    interacting = a.interactions is not None
+    calc.set_microkinetics(model(tp, a.interactions), site_density=site_density, potential_drop='stern',
+                          scf='newton' if a.newton else 'mixing', rate_control=a.rate_control and not interacting, device_loop=a.device_loop)
     names = list(tp.species.keys())
     t0 = time.time()
     out = calc.run_scf_cycle(nel=[2.0 if sp == 'CO' else 1.0 for sp in names], max_iter=a.max_iter)
@@ -108,7 +116,23 @@ def main():
             digits = 16.0 + np.log10(abs(out['flux'][i, iCO]) / out['flux_scale'][i, iCO])
         print('%7.3f   %12.5e   %6.1f   %8.4f   %s' % (phis[i], out['flux'][i, iCO] * 2 * unit_F / 10.0, digits, out['surface_concentration'][i, iCO2],
                                                      '   '.join('%9.3e' % v for v in out['coverage'][i])))
-    if a.rate_control:
+    if a.rate_control and interacting:
+        # the calculator's rate_control option is mean-field: one call on the host-surface path at the state the loop ended with
+        from catint_amd.iacontrol import InteractingRateControl
+        ads = list(ADSORBATES)
+        vs = np.array([tp.alldata[i]['system']['surface_potential'] for i in range(a.lanes)])
+        tables = dict(model(tp, a.interactions).tables(), site_density=site_density)
+        with InteractingRateControl() as irc:
+            rc = irc.solve(None, tables, phis, out['coverage'], csurf=out['surface_concentration'], phi_surface=vs, potential_drop='stern',
+                           stern_capacitance=float(tp.system.get('Stern capacitance', 0.0)) * 1e-2, phi_pzc=float(tp.system.get('phiPZC', 0.0)),
+                           fields=('drc', 'tdrc', 'strength_control'), residual_tol=1e-3)
+        print('degree of rate control of the CO flux with the CO self-interaction in the Jacobian: controlling step (X_rc), intermediate '
+              '(X_trc) and the share of the flux owed to the interaction')
+        for i in range(a.lanes):
+            r, s = int(np.argmax(np.nan_to_num(np.abs(rc['drc'][i][:, iCO])))), int(np.argmax(np.nan_to_num(np.abs(rc['tdrc'][i][:, iCO]))))
+            print('%7.3f   status %d   step %d %+.3f, %s* %+.3f, interaction %+.3f' % (phis[i], rc['status'][i], r + 1, rc['drc'][i][r, iCO], ads[s],
+                                                                                      rc['tdrc'][i][s, iCO], rc['strength_control'][i, iCO]))
+    elif a.rate_control:
         rc = out['rate_control']
         ads = list(ADSORBATES)
         kinds = [('intrinsic', 'drc', 'tdrc')] + ([('apparent', 'drc_apparent', 'tdrc_apparent')] if a.newton else [])
